@@ -48,6 +48,9 @@ def parse_args():
                          "is one of the warm-up / timed steps")
     ap.add_argument("--streams", type=int, default=1,
                     help="batches in flight in the timed loop (default 1: one batch at a time, the headline definition)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (u0, status, iters; rank 0's batch) "
+                         "as DIR/<name>.npy in float64")
     return ap.parse_args()
 
 
@@ -171,6 +174,8 @@ def pmc_summary():
 
 def main():
     a = parse_args()
+    if a.steps < 1:
+        raise SystemExit(f"bench.py: --steps {a.steps}: at least one timed step is needed")
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and a.gpus > 1:
         sys.exit(spawn_ranks(a))
@@ -178,11 +183,6 @@ def main():
     if world != a.gpus:
         raise SystemExit(f"bench.py: --gpus {a.gpus} but WORLD_SIZE={world}: launch with torchrun --nproc-per-node {a.gpus} "
                          f"or plainly as `python bench.py --gpus {a.gpus}`")
-    # read when the HIP runtime starts: with the default of 4 hardware queues, streams carrying independent batches can
-    # end up sharing a queue and serialise (the in_flight side measurement); multi-rank runs keep the runtime's default
-    if world == 1:
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -269,6 +269,8 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, outs_s[(a.steps - 1) % n_str])
     kern = np.array([s.elapsed_time(e) for s, e in ev])
     # with several batches in flight the events of one stream bracket a kernel that shares the GPU: not a kernel time
     kern_ms = float(kern.mean()) if n_str == 1 else None
@@ -408,6 +410,15 @@ def main():
     eng.close()
     if use_dist:
         dist.destroy_process_group()
+
+
+def dump_outputs(path, out):
+    """What the last timed step returned to its caller (rank 0's batch: u0 [B, 2], status [B], iters [B]), as float64 .npy
+    files; the inputs are the same on every run (synth.solver_inputs, seed = rank), so two builds compare file by file."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(path, f"{name}.npy"), v.cpu().numpy().astype(np.float64))
 
 
 def side_measurements(a, eng, args, inp, out, dev):
@@ -559,11 +570,11 @@ def side_measurements(a, eng, args, inp, out, dev):
                          "calls_per_s": 1e3 / float(np.median(lat_ms))}
     # batches in flight: the straggler tail of one batch overlaps with the bulk of the next ones (same kernel, same inputs,
     # identical outputs) - what a serving loop with several independent environment groups would run
-    n_fl = 8       # = GPU_MAX_HW_QUEUES above: streams that share a hardware queue serialise (tools/gpu_inflight.py, round 5),
-    # and which of torch's pool streams share one is the runtime's choice: each is probed (round 6, mpc_streams_overlap)
+    n_fl = 4       # = the runtime's default of 4 hardware queues: streams that share a hardware queue serialise (tools/gpu_inflight.py,
+    # round 5), and which of torch's pool streams share one is the runtime's choice: each is probed (round 6, mpc_streams_overlap)
     try:
         streams, probed = engine.concurrent_streams(n_fl, dev), True
-    except engine.EngineError:          # fewer than eight hardware queues in this process (GPU_MAX_HW_QUEUES set from outside)
+    except engine.EngineError:          # fewer hardware queues than streams in this process
         streams, probed = [torch.cuda.Stream(dev) for _ in range(n_fl)], False
     outs = []
     for sq in streams:
@@ -598,15 +609,13 @@ def side_measurements(a, eng, args, inp, out, dev):
                           "counts": "all instances"}
     del a_b, o_b
     # BASELINE configs[4]'s total (2048 environments, 8 GPUs x 256 there) on ONE GPU: two groups of 1024 environments stepped on two
-    # streams that run side by side (rollout.PipelinedCollector, engine.concurrent_streams).  In a child process with the
-    # runtime's default of 4 hardware queues: with more than 4 (this process runs with 8 for the in_flight measurement above) the
-    # same two groups are 20 % slower - 1.80 against 2.22 M env-steps/s for 5, 6, 7, 8 or 16 queues against 2, 3 or 4
-    # (profiles/r06_hw_queues_scan.txt) - although the streams pass the overlap probe
+    # streams that run side by side (rollout.PipelinedCollector, engine.concurrent_streams), in a child process: with more than
+    # the runtime's default of 4 hardware queues the same two groups are 20 % slower - 1.80 against 2.22 M env-steps/s for 5, 6,
+    # 7, 8 or 16 queues against 2, 3 or 4 (profiles/r06_hw_queues_scan.txt) - although the streams pass the overlap probe
     import subprocess
-    env5 = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
     try:      # a side measurement in another process must not cost the run its line
         r5 = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_rollout.py"), "--envs", "2048", "--groups", "2", "--steps", "64"],
-                            env=env5, capture_output=True, text=True, timeout=600)
+                            capture_output=True, text=True, timeout=600)
         if r5.returncode != 0:
             raise RuntimeError(f"exit code {r5.returncode}: " + r5.stderr[-1500:])
         d5 = json.loads(r5.stdout.strip().splitlines()[-1])

@@ -46,3 +46,10 @@ def test_plain_multi_gpu_launch_spawns_the_ranks(monkeypatch):
     assert seen["cmd"][-4:] == ["--gpus", "4", "--steps", "5"] and "127.0.0.1" in seen["cmd"]
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
     assert ("torch" in sys.modules) == was_loaded
+
+
+def test_zero_steps_is_an_error():
+    """--steps is the number of timed steps: there is no ms_per_step without one."""
+    env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], env=env, capture_output=True, text=True)
+    assert r.returncode != 0 and "--steps 0" in r.stderr and "ms_per_step" not in r.stdout
