@@ -33,6 +33,15 @@ struct SolveParams {
     int strict_kink;    // MPC_FLAG_STRICT_DISCONTINUITY: a solve that ends on the d = 1 discontinuity is reported unsolved
 };
 
+// First row of an instance's reference window.  Stage k reads row min(max(ego_index + k, 0), M - 1) for k = 0..N (and the
+// launch order looks 5 rows behind): ego_index is saturated ONCE to [-(64 + 1), M - 1] before any offset is added, so the
+// sum cannot overflow int for any ego_index a caller passes.  Every window stays what it was: below -(64 + 1) all rows of a
+// horizon <= 64 are row 0 either way, from M - 1 on all rows are M - 1.
+constexpr int kEgoRowFloor = -(64 + 1);
+MPC_HD int ego_row0(int ego_index, int M) {
+    return ego_index < kEgoRowFloor ? kEgoRowFloor : (ego_index > M - 1 ? M - 1 : ego_index);
+}
+
 // single v_max_f64 / v_min_f64 on the device (a compare + two v_cndmask otherwise)
 MPC_HD double fmax2(double a, double b) { return __builtin_fmax(a, b); }
 MPC_HD double fmin2(double a, double b) { return __builtin_fmin(a, b); }

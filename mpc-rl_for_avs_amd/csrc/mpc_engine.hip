@@ -72,7 +72,7 @@ struct WaveCtx : mpc::wave::WaveOpsT<RELAX> {
     const double *table;  // [M][REF_COLS] in global memory (wave-uniform index in the serial parts -> scalar loads)
     int e0, M;
     __device__ __forceinline__ WaveCtx(mpc::wave::lds_double_t *l, const double *t, int e, int m)
-        : mpc::wave::WaveOpsT<RELAX>{l}, table(t), e0(e), M(m) {}
+        : mpc::wave::WaveOpsT<RELAX>{l}, table(t), e0(mpc::ego_row0(e, m)), M(m) {}
     __device__ __forceinline__ void tick(int) const {}  // section timing hook, used by tools/ubench only
     __device__ __forceinline__ double ref(int k, int c) const {
         int idx = e0 + k;
@@ -212,7 +212,7 @@ __device__ __forceinline__ int order_tier(const uint8_t *is_collide, const doubl
     const double *x = state + (size_t)i * 4;
     if (x[3] < kOrderStanding) return 0;
     if (is_collide[i] != 0) {
-        const int e0 = ego[i];
+        const int e0 = mpc::ego_row0(ego[i], M);
         const int a = min(M - 1, max(0, e0 - kOrderBehind)), b = min(M - 1, max(0, e0 + N));
         const double d = ref5[(size_t)b * mpc::REF_COLS + mpc::R_H] - ref5[(size_t)a * mpc::REF_COLS + mpc::R_H];
         return fabs(remainder(d, 6.283185307179586)) > kOrderTurn ? 2 : 3;      // (NaN compares false: tier 3)

@@ -105,7 +105,7 @@ def objective_scale(p: nb.Batch):
         f, _ = dyn(X0[:, k:k + 1], U0[:, k:k + 1])
         X0[:, k + 1] = X0[:, k] + dt * f[:, 0]
     gX, gU = nb.cost_grad(p, X0, U0)
-    gmax = np.maximum(np.abs(gX[:, 1:N]).max(axis=(1, 2)), np.abs(gU[:, 0, 0]))
+    gmax = np.maximum(np.abs(gX[:, 1:N]).max(axis=(1, 2), initial=0.0), np.abs(gU[:, 0, 0]))     # N = 1: no free state
     return 100.0 / np.clip(gmax, 100.0, 1e4)
 
 

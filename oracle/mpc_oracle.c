@@ -992,8 +992,10 @@ int oracle_solve_batch_warm(int B, int N, double dt, const double *ref_table, in
         p.V = (flags & 1u) ? V : 0;
         p.cc = (flags & 1u) ? 1 : 0;
         for (int i = 0; i < 4; ++i) p.x0[i] = state[4 * b + i];
+        /* first row saturated before the stage offsets are added (no int overflow for any ego_index; the same rows) */
+        const int e0 = ego_index[b] < -(NMAX + 1) ? -(NMAX + 1) : (ego_index[b] > M - 1 ? M - 1 : ego_index[b]);
         for (int k = 0; k <= N; ++k) {
-            int idx = ego_index[b] + k;
+            int idx = e0 + k;
             if (idx > M - 1) idx = M - 1;
             if (idx < 0) idx = 0;
             p.rx[k] = ref_table[4 * idx + 0];

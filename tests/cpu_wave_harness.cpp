@@ -70,7 +70,7 @@ extern "C" int wave_solve_batch_warm(int B, int N, double dt, const double *ref_
         ctx.M = M;
         ctx.nwords = nd;   // the kernel source must stay inside lds_doubles() for every horizon / vehicle count
         for (int k = 0; k <= N; ++k) {
-            int idx = ego_index[b] + k;
+            int idx = mpc::ego_row0(ego_index[b], M) + k;
             idx = idx > M - 1 ? M - 1 : idx;
             idx = idx < 0 ? 0 : idx;
             L[k * SL + mpc::wave::W_RV] = vref ? vref[(size_t)b * (N + 1) + k] : ref_table[idx * 4 + 2];
@@ -144,7 +144,7 @@ extern "C" int wave_eval_batch(int B, int N, double dt, const double *ref_table,
         ctx.M = M;
         ctx.nwords = nd;
         for (int k = 0; k <= N; ++k) {
-            int idx = ego_index[b] + k;
+            int idx = mpc::ego_row0(ego_index[b], M) + k;
             idx = idx > M - 1 ? M - 1 : idx;
             idx = idx < 0 ? 0 : idx;
             L[k * SL + mpc::wave::W_RV] = vref ? vref[(size_t)b * (N + 1) + k] : ref_table[idx * 4 + 2];

@@ -143,13 +143,13 @@ struct HostCtx {
             }
     }
     double refv(int k) const {
-        int idx = e0 + k;
+        int idx = mpc::ego_row0(e0, M) + k;
         idx = idx > M - 1 ? M - 1 : idx;
         idx = idx < 0 ? 0 : idx;
         return speeds[idx];
     }
     double ref(int k, int c) const {
-        int idx = e0 + k;
+        int idx = mpc::ego_row0(e0, M) + k;
         idx = idx > M - 1 ? M - 1 : idx;
         idx = idx < 0 ? 0 : idx;
         return table[idx * mpc::REF_COLS + c];

@@ -36,6 +36,15 @@ for N, V, cc, B in ((20, 8, True, 24), (20, 4, False, 24), (16, 3, True, 8), (1,
     both = conftest.converged(got["status"]) & conftest.converged(want["status"])
     assert both.sum() >= 1 and conftest.rel_u0_err(got["u0"], want["u0"])[both].max() < 1e-4, (N, V, cc)
     n += B
+# ego_index at both ends of int32 (the window rows are computed from a saturated first row: no signed overflow)
+for N, cc in ((20, True), (33, False)):
+    inp = synth.solver_inputs(4, 4, seed=7, N=N)
+    inp["vref"] = None
+    inp["ego_index"] = np.array([2 ** 31 - 1, 2 ** 31 - 1 - N, -2 ** 31, -1000], np.int32)
+    wave(ref, inp, N=N, collision_cost=cc, max_iter=20)
+    oracle_lib.solve_batch(ref, inp["state"], inp["ego_index"], inp["weights"], inp["is_collide"], others=inp["others"],
+                           collision_cost=cc, N=N, max_iter=20, xy_bounds=False)
+    n += 4
 # warm start path
 inp = synth.solver_inputs(8, 4, seed=3)
 cold = wave(ref, inp, collision_cost=True, max_iter=60)
