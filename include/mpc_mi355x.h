@@ -296,6 +296,17 @@ int mpc_synth_env_step(int32_t device, int32_t B, int32_t K, double dt, double s
  * action: version_v1 == 0 -> mpc_ref_speed [B] f64 = action 0 (agents/ppo_mpc.py:410-414), else mpc_weights [B][3] f64 =
  * actions 0..2 (:416-420); clip != 0 clips to the Box(-1, 1) action space first (PPO, :399-407; A2C does not, a2c_mpc.py:138-144).
  *
+ * mpc_policy_act_sde: the same step with gSDE exploration (stable-baselines3's StateDependentNoiseDistribution as
+ * ActorCriticPolicy(use_sde=True) builds it, the PPO agents' default, agents/ppo_mpc.py:114-115).  Same network and weight layout,
+ * but sde_std [H][A] = exp(log_std) replaces std / c0.  With latent = the H policy units after layer 2 and E = sde_std * Z the
+ * environment's exploration matrix [H][A]: actions = mean + latent @ E, log_probs = Normal(mean, sqrt(latent^2 @ sde_std^2 +
+ * 1e-6)).log_prob(actions) summed over the components.  Z: with sde_noise [B][H][A] given, read from the caller (sde_epoch NULL);
+ * otherwise DRAWN - counter-based, keyed by (noise_seed, env_offset + b, epoch, h * A + a) with epoch = sde_epoch[0] +
+ * (sde_sample_freq > 0 ? sde_step[0] / sde_sample_freq : 0) (sde_step NULL reads as 0), so one matrix serves a whole epoch and is
+ * never stored.  The caller advances sde_epoch[0] at every rollout start (far enough to pass the epochs the last rollout used);
+ * sde_step is the policy steps taken in the rollout (the buffer position mpc_rollout_record advances).  Clip and MPC inputs as
+ * mpc_policy_act.
+ *
  * mpc_rollout_record: row pos_dev[0] of the rollout buffer row [T][B][cols] = [obs 80 | action A | reward | episode_start |
  * value | log_prob | (terminal_obs 80 | truncated)] (rollout_buffer.add, agents/ppo_mpc.py:462-469) and of mpc_actions_buf
  * [T][B][2]; last_obs <- new_obs, last_starts <- done; counts [4] += finished / crashed / arrived episodes and solves whose
@@ -318,6 +329,11 @@ int mpc_policy_act(int32_t device, int32_t B, int32_t A, int32_t H2, const float
                    float *noise, uint64_t noise_seed, int32_t env_offset, const int64_t *noise_step, int32_t version_v1,
                    int32_t clip, float *actions, float *values, float *log_probs, double *mpc_weights, double *mpc_ref_speed,
                    void *stream);
+int mpc_policy_act_sde(int32_t device, int32_t B, int32_t A, int32_t H2, const float *obs, const float *w1, const float *b1,
+                       const float *w2, const float *b2, const float *wh, const float *bh, const float *sde_std,
+                       const float *sde_noise, uint64_t noise_seed, int32_t env_offset, const int64_t *sde_epoch,
+                       const int64_t *sde_step, int32_t sde_sample_freq, int32_t version_v1, int32_t clip, float *actions,
+                       float *values, float *log_probs, double *mpc_weights, double *mpc_ref_speed, void *stream);
 int mpc_rollout_record(int32_t device, int32_t T, int32_t B, int32_t A, int32_t cols, int32_t keep_terminal, float *row,
                        double *mpc_actions_buf, int64_t *pos_dev, int32_t *ticket, float *last_obs, float *last_starts,
                        const float *actions, const float *values, const float *log_probs, const double *mpc_act,

@@ -653,6 +653,48 @@ __global__ __launch_bounds__(mpc::glue::kMaxHidden2) void mpc_policy_act_kernel(
                             mpc_ref_speed ? mpc_ref_speed + b : nullptr);
 }
 
+// the gSDE form of the same step (mpc_rollout_glue.hpp): thread h < H also holds row h of the environment's exploration matrix
+// E = std * Z in LDS (Z drawn here, A Box-Muller draws per thread, or read from the caller); after layer 2 the H policy units
+// are the latent, and threads 64 .. 64 + 2A (the second wave, next to the heads on the first) reduce the noise latent @ E and
+// the variance latent^2 @ std^2 in index order
+__global__ __launch_bounds__(mpc::glue::kMaxHidden2) void mpc_policy_act_sde_kernel(
+    int B, int A, int H2, const float *__restrict__ obs, mpc::glue::PolicyWeights W, const float *__restrict__ sde_noise,
+    unsigned long long noise_seed, int env_offset, const long long *__restrict__ sde_epoch,
+    const long long *__restrict__ sde_step, int sde_sample_freq, int version_v1, int clip, float *__restrict__ actions,
+    float *__restrict__ values, float *__restrict__ log_probs, double *__restrict__ mpc_weights,
+    double *__restrict__ mpc_ref_speed) {
+    namespace glue = mpc::glue;
+    __shared__ float s_x[glue::kObsDim];
+    __shared__ float s_h1[glue::kMaxHidden2], s_h2[glue::kMaxHidden2];
+    __shared__ float s_head[glue::kMaxAction + 1];
+    __shared__ float s_e[glue::kMaxHidden2 / 2 * glue::kMaxAction];
+    __shared__ float s_sum[2 * glue::kMaxAction];
+    const int b = blockIdx.x, j = threadIdx.x, H = H2 / 2;
+    if (b >= B) return;
+    if (j < glue::kObsDim) s_x[j] = obs[(size_t)b * glue::kObsDim + j];
+    if (j < H) {
+        float z[glue::kMaxAction];
+        if (sde_noise) {
+            for (int a = 0; a < A; ++a) z[a] = sde_noise[((size_t)b * H + j) * A + a];
+        } else {
+            const long long e = glue::sde_draw_epoch(*sde_epoch, sde_step ? *sde_step : 0, sde_sample_freq);
+            for (int a = 0; a < A; ++a) z[a] = glue::sde_noise(noise_seed, env_offset + b, e, j * A + a);
+        }
+        glue::sde_row(W.std, A, j, z, s_e + j * A);
+    }
+    __syncthreads();
+    if (j < H2) s_h1[j] = glue::layer1_unit(W, H2, s_x, j);
+    __syncthreads();
+    if (j < H2) s_h2[j] = glue::layer2_unit(W, H2, s_h1, j);
+    __syncthreads();
+    if (j <= A) s_head[j] = glue::head_unit(W, H2, A, s_h2, j);
+    if (j >= 64 && j < 64 + 2 * A) s_sum[j - 64] = glue::sde_sum(W.std, H, A, s_h2, s_e, j - 64);
+    __syncthreads();
+    if (j == 0)
+        glue::finish_action_sde(A, s_head, s_sum, version_v1, clip, nullptr, actions + (size_t)b * A, values + b, log_probs + b,
+                                mpc_weights ? mpc_weights + (size_t)b * 3 : nullptr, mpc_ref_speed ? mpc_ref_speed + b : nullptr);
+}
+
 __global__ __launch_bounds__(128) void mpc_rollout_record_kernel(mpc::glue::RecordArgs R, int T, long long *__restrict__ pos_dev,
                                                                  int32_t *__restrict__ ticket,
                                                                  unsigned long long *__restrict__ counts,
@@ -1585,6 +1627,33 @@ int mpc_policy_act(int32_t device, int32_t B, int32_t A, int32_t H2, const float
     hipLaunchKernelGGL(mpc_policy_act_kernel, dim3((unsigned)B), dim3((unsigned)((threads + 63) / 64 * 64)), 0,
                        reinterpret_cast<hipStream_t>(stream_), (int)B, (int)A, (int)H2, obs, W, noise, (unsigned long long)noise_seed,
                        (int)env_offset, reinterpret_cast<const long long *>(noise_step), (int)version_v1, (int)clip,
+                       actions, values, log_probs, version_v1 ? mpc_weights : nullptr, version_v1 ? nullptr : mpc_ref_speed);
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_policy_act_sde(int32_t device, int32_t B, int32_t A, int32_t H2, const float *obs, const float *w1, const float *b1,
+                       const float *w2, const float *b2, const float *wh, const float *bh, const float *sde_std,
+                       const float *sde_noise, uint64_t noise_seed, int32_t env_offset, const int64_t *sde_epoch,
+                       const int64_t *sde_step, int32_t sde_sample_freq, int32_t version_v1, int32_t clip, float *actions,
+                       float *values, float *log_probs, double *mpc_weights, double *mpc_ref_speed, void *stream_) {
+    if (B < 0 || A < 1 || A > mpc::glue::kMaxAction || H2 < 2 || H2 > mpc::glue::kMaxHidden2 || (H2 & 1))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_policy_act_sde: bad size (action_dim 1..8, 2 x hidden <= 256)");
+    if (!obs || !w1 || !b1 || !w2 || !b2 || !wh || !bh || !sde_std || !actions || !values || !log_probs)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_policy_act_sde: null pointer");
+    if (!sde_noise == !sde_epoch)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_policy_act_sde: exactly one of sde_noise (read) and sde_epoch (drawn)");
+    if (version_v1 ? (!mpc_weights || A < 3) : !mpc_ref_speed)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_policy_act_sde: v1 needs mpc_weights and >= 3 action components, v0 needs mpc_ref_speed");
+    if (B == 0) return MPC_OK;
+    HIP_TRY(hipSetDevice(device));
+    const mpc::glue::PolicyWeights W{w1, b1, w2, b2, wh, bh, sde_std, nullptr};
+    // at least two waves: the second reduces the noise and the variance while the first computes the heads
+    const int threads = H2 > 128 ? H2 : 128;
+    hipLaunchKernelGGL(mpc_policy_act_sde_kernel, dim3((unsigned)B), dim3((unsigned)((threads + 63) / 64 * 64)), 0,
+                       reinterpret_cast<hipStream_t>(stream_), (int)B, (int)A, (int)H2, obs, W, sde_noise,
+                       (unsigned long long)noise_seed, (int)env_offset, reinterpret_cast<const long long *>(sde_epoch),
+                       reinterpret_cast<const long long *>(sde_step), (int)sde_sample_freq, (int)version_v1, (int)clip,
                        actions, values, log_probs, version_v1 ? mpc_weights : nullptr, version_v1 ? nullptr : mpc_ref_speed);
     HIP_TRY(hipGetLastError());
     return MPC_OK;

@@ -73,17 +73,10 @@ MPC_HD float head_unit(const PolicyWeights &W, int H2, int A, const float *h2, i
     for (int i = lo; i < lo + H; ++i) s = fmaf(h2[i], W.wh[i * (A + 1) + o], s);
     return s;
 }
-// sample, log-probability, clip, MPC inputs of one environment.  out_mean [A + 1] = heads; noise [A]
-MPC_HD void finish_action(const PolicyWeights &W, int A, const float *heads, const float *noise, int version_v1, int clip,
-                          const double *default_weights, float *actions, float *value, float *log_prob, double *mpc_weights,
-                          double *mpc_ref_speed) {
-    float q = 0.0f;
-    for (int a = 0; a < A; ++a) {
-        actions[a] = fmaf(noise[a], W.std[a], heads[a]);      // torch.addcmul(mean, noise, std)
-        q += noise[a] * noise[a];
-    }
-    *value = heads[A];
-    *log_prob = -0.5f * q - W.c0[0];
+// the clip to the Box(-1, 1) action space (PPO) and the mapping of the action onto the MPC's inputs (v0: reference speed,
+// v1: the three cost weights)
+MPC_HD void map_action(const float *actions, int version_v1, int clip, const double *default_weights, double *mpc_weights,
+                       double *mpc_ref_speed) {
     auto clipped = [&](int a) {
         const float v = actions[a];
         return (double)(clip ? (v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v)) : v);
@@ -96,6 +89,69 @@ MPC_HD void finish_action(const PolicyWeights &W, int A, const float *heads, con
             for (int a = 0; a < 3; ++a) mpc_weights[a] = default_weights[a];
         if (mpc_ref_speed) *mpc_ref_speed = clipped(0);
     }
+}
+// sample, log-probability, clip, MPC inputs of one environment.  out_mean [A + 1] = heads; noise [A]
+MPC_HD void finish_action(const PolicyWeights &W, int A, const float *heads, const float *noise, int version_v1, int clip,
+                          const double *default_weights, float *actions, float *value, float *log_prob, double *mpc_weights,
+                          double *mpc_ref_speed) {
+    float q = 0.0f;
+    for (int a = 0; a < A; ++a) {
+        actions[a] = fmaf(noise[a], W.std[a], heads[a]);      // torch.addcmul(mean, noise, std)
+        q += noise[a] * noise[a];
+    }
+    *value = heads[A];
+    *log_prob = -0.5f * q - W.c0[0];
+    map_action(actions, version_v1, clip, default_weights, mpc_weights, mpc_ref_speed);
+}
+
+// ---- gSDE (generalized State-Dependent Exploration, stable-baselines3's StateDependentNoiseDistribution at the settings of
+//      ActorCriticPolicy: full_std, no expln, no squashing, detached latent, epsilon 1e-6; the PPO agents' default,
+//      agents/ppo_mpc.py:114-115).  The sample is mean + latent @ E with one exploration matrix E = std * Z [H][A] per
+//      environment, std = exp(log_std) [H][A], and the Gaussian's variance latent^2 @ std^2 + 1e-6 depends on the state
+//      (ActorCritic(use_sde=True) is the torch statement).
+// Z [h][a] of environment `env` (its GLOBAL id) in exploration epoch `epoch`: counter-based like policy_noise, entry k = h A + a,
+// so the matrix is never stored - every step of an epoch draws it again from its key
+MPC_HD float sde_noise(uint64_t seed, int env, long long epoch, int k) {
+    const env::Rng r(seed ^ 0x67534445ull, env, epoch);
+    return (float)r.normal(2 * k);
+}
+// the epoch a step draws from: the device counter `epoch` (advanced by the caller at every rollout start) plus, with a positive
+// sample frequency, one per `freq` policy steps of the rollout (agents/ppo_mpc.py:380-388)
+MPC_HD long long sde_draw_epoch(long long epoch, long long step, int freq) { return freq > 0 ? epoch + step / freq : epoch; }
+// row h of E (thread h < H of the policy tower): e_row[a] = std[h][a] * z_row[a]
+MPC_HD void sde_row(const float *sde_std, int A, int h, const float *z_row, float *e_row) {
+    for (int a = 0; a < A; ++a) e_row[a] = sde_std[h * A + a] * z_row[a];
+}
+// o < A: the noise sum_h latent_h E[h][o];  A <= o < 2A: the variance sum_h latent_h^2 std[h][o - A]^2 - in index order
+MPC_HD float sde_sum(const float *sde_std, int H, int A, const float *latent, const float *E, int o) {
+    float s = 0.0f;
+    if (o < A) {
+        for (int h = 0; h < H; ++h) s = fmaf(latent[h], E[h * A + o], s);
+    } else {
+        const int a = o - A;
+        for (int h = 0; h < H; ++h) {
+            const float l = latent[h], d = sde_std[h * A + a];
+            s = fmaf(l * l, d * d, s);
+        }
+    }
+    return s;
+}
+
+// the gSDE sample of one environment: heads [A + 1], sums [2A] = noise (sde_sum o < A) and variance (o >= A); log_prob is
+// torch's Normal(mean, sqrt(variance + 1e-6)).log_prob(action) summed over the components, operation by operation in float32
+MPC_HD void finish_action_sde(int A, const float *heads, const float *sums, int version_v1, int clip, const double *default_weights,
+                              float *actions, float *value, float *log_prob, double *mpc_weights, double *mpc_ref_speed) {
+#pragma clang fp contract(off)
+    float lp = 0.0f;
+    for (int a = 0; a < A; ++a) {
+        const float act = heads[a] + sums[a];
+        actions[a] = act;
+        const float scale = sqrtf(sums[A + a] + 1e-6f), d = act - heads[a];
+        lp += -(d * d) / (2.0f * (scale * scale)) - logf(scale) - 0.918938533204672742f;   // log(sqrt(2 pi))
+    }
+    *value = heads[A];
+    *log_prob = lp;
+    map_action(actions, version_v1, clip, default_weights, mpc_weights, mpc_ref_speed);
 }
 
 // What thread j (0 .. 127) of environment b's workgroup writes for the buffer row `pos` (RolloutBuffer's layout: [obs 80 |

@@ -231,28 +231,75 @@ class SyntheticIntersectionEnv:
                                                arrived=arrived)
 
 
-class ActorCritic(torch.nn.Module):
-    """SB3 `MlpPolicy`-shaped actor-critic: 80 -> 64 -> 64 (tanh) twice, Gaussian head of `action_dim`."""
+SDE_EPSILON = 1e-6          # StateDependentNoiseDistribution(epsilon=1e-6): the floor of the gSDE variance
 
-    def __init__(self, action_dim: int, obs_dim: int = VEHICLES_COUNT * 8, hidden: int = 64):
+
+class ActorCritic(torch.nn.Module):
+    """SB3 `MlpPolicy`-shaped actor-critic: 80 -> 64 -> 64 (tanh) twice, Gaussian head of `action_dim`.
+
+    use_sde=False (default): SB3's DiagGaussianDistribution, a state-independent `log_std` [A].
+    use_sde=True: generalized State-Dependent Exploration, SB3 2.4's StateDependentNoiseDistribution at the settings
+    ActorCriticPolicy uses (full_std, no expln, no squashing, learn_features=False, epsilon 1e-6) - what the reference's
+    PPO agents train with (agents/ppo_mpc.py:114-115).  `log_std` is [H, A]; with latent = pi(obs) and latent_d its detached
+    copy, the distribution is Normal(action_net(latent), sqrt(latent_d^2 @ exp(log_std)^2 + 1e-6)) and a sample is
+    mean + latent_d @ E[b] with one exploration matrix E[b] = exp(log_std) * Z[b] per environment, Z ~ N(0, 1) [n, H, A]
+    redrawn by reset_noise(n)."""
+
+    def __init__(self, action_dim: int, obs_dim: int = VEHICLES_COUNT * 8, hidden: int = 64, use_sde: bool = False,
+                 log_std_init: float = 0.0):
         super().__init__()
         mk = lambda: torch.nn.Sequential(torch.nn.Linear(obs_dim, hidden), torch.nn.Tanh(),
                                          torch.nn.Linear(hidden, hidden), torch.nn.Tanh())
         self.pi, self.vf = mk(), mk()
         self.action_net = torch.nn.Linear(hidden, action_dim)
         self.value_net = torch.nn.Linear(hidden, 1)
-        self.log_std = torch.nn.Parameter(torch.zeros(action_dim))
+        self.use_sde = bool(use_sde)
+        shape = (hidden, action_dim) if self.use_sde else (action_dim,)
+        self.log_std = torch.nn.Parameter(torch.full(shape, float(log_std_init)))
         self.action_dim = action_dim
+        if self.use_sde:
+            # the matrices move with the module (.to) but are not parameters: buffers outside the state dict
+            self.register_buffer("sde_noise", torch.zeros((1,) + shape), persistent=False)
+            self.register_buffer("sde_noise_single", torch.zeros(shape), persistent=False)
+            self.reset_noise(1)
+
+    # ---- gSDE exploration matrices (StateDependentNoiseDistribution.sample_weights / get_noise) ----------------------------
+    @torch.no_grad()
+    def reset_noise(self, n: int = 1, generator=None):
+        """Redraw the standard-normal Z of the exploration matrices: `sde_noise` [n, H, A] (one per environment) and
+        `sde_noise_single` [H, A], the one matrix SB3 uses when the batch is a single observation or does not match n."""
+        if not self.use_sde:
+            raise RuntimeError("reset_noise: the policy was built without use_sde")
+        dev, dt = self.log_std.device, self.log_std.dtype
+        self.sde_noise_single = torch.randn(tuple(self.log_std.shape), generator=generator, device=dev, dtype=dt)
+        self.sde_noise = torch.randn((int(n),) + tuple(self.log_std.shape), generator=generator, device=dev, dtype=dt)
+
+    def _sde_sample_noise(self, latent_d, std, Z=None):
+        """latent_d [B, H] @ E with E = std * Z: per environment (bmm) when Z has one matrix per row of the batch, else the
+        single matrix (get_noise's default case)."""
+        if Z is None:
+            many = self.sde_noise
+            Z = many if latent_d.shape[0] != 1 and many.shape[0] == latent_d.shape[0] else self.sde_noise_single
+        if Z.dim() == 2:
+            return latent_d @ (std * Z)
+        return torch.bmm(latent_d[:, None], std * Z)[:, 0]
 
     def _dist(self, obs):
-        mean = self.action_net(self.pi(obs.flatten(1)))
+        latent = self.pi(obs.flatten(1))
+        mean = self.action_net(latent)
+        if self.use_sde:
+            latent_d = latent.detach()
+            variance = (latent_d ** 2) @ (self.log_std.exp() ** 2)
+            return torch.distributions.Normal(mean, torch.sqrt(variance + SDE_EPSILON), validate_args=False), latent_d
         # validate_args=False: the default argument checks read a device boolean back on the host (a sync per step)
-        return torch.distributions.Normal(mean, self.log_std.exp().expand_as(mean), validate_args=False)
+        return torch.distributions.Normal(mean, self.log_std.exp().expand_as(mean), validate_args=False), None
 
     def forward(self, obs, deterministic: bool = False, generator=None):
-        d = self._dist(obs)
+        d, latent_d = self._dist(obs)
         if deterministic:
             actions = d.mean
+        elif self.use_sde:
+            actions = d.mean + self._sde_sample_noise(latent_d, self.log_std.exp())
         else:
             actions = d.mean + d.stddev * torch.randn(d.mean.shape, generator=generator, device=d.mean.device,
                                                       dtype=d.mean.dtype)
@@ -265,6 +312,7 @@ class ActorCritic(torch.nn.Module):
     #      layers side by side, second layer block-diagonal, heads in one matrix) and the Gaussian sample / log-probability
     #      written out - 3 GEMMs, 2 tanh and 6 small kernels instead of 6 + 4 + 12.  Same function as forward(); the fused
     #      weights live in persistent buffers (a captured hipGraph reads them in place) refreshed by refresh_fused().
+    #      gSDE: std = exp(log_std) [H, A] and no c0.
     @torch.no_grad()
     def refresh_fused(self):
         A, H = self.action_dim, self.pi[0].out_features
@@ -272,7 +320,11 @@ class ActorCritic(torch.nn.Module):
         if getattr(self, "_fz", None) is None or self._fz["w1"].device != dev:
             z = lambda *shape: torch.zeros(shape, device=dev, dtype=dt)
             self._fz = dict(w1=z(self.pi[0].in_features, 2 * H), b1=z(2 * H), w2=z(2 * H, 2 * H), b2=z(2 * H),
-                            wh=z(2 * H, A + 1), bh=z(A + 1), std=z(A), c0=z(1)[0])
+                            wh=z(2 * H, A + 1), bh=z(A + 1))
+            if self.use_sde:
+                self._fz["std"] = z(H, A)
+            else:
+                self._fz.update(std=z(A), c0=z(1)[0])
         f = self._fz
         f["w1"][:, :H].copy_(self.pi[0].weight.t())
         f["w1"][:, H:].copy_(self.vf[0].weight.t())
@@ -287,17 +339,26 @@ class ActorCritic(torch.nn.Module):
         f["bh"][:A].copy_(self.action_net.bias)
         f["bh"][A:].copy_(self.value_net.bias)
         f["std"].copy_(self.log_std.exp())
-        f["c0"].copy_(self.log_std.sum() + 0.5 * A * math.log(2.0 * math.pi))
+        if not self.use_sde:
+            f["c0"].copy_(self.log_std.sum() + 0.5 * A * math.log(2.0 * math.pi))
 
     @torch.no_grad()
     def act(self, obs, generator=None, noise=None):
         """(actions, values, log_probs) like forward(obs), through the fused weights (call refresh_fused() after every
-        change of the parameters).  noise: the sample's standard-normal draws [B, action_dim] instead of the generator's."""
+        change of the parameters).  noise: the sample's standard-normal draws [B, action_dim] instead of the generator's;
+        with use_sde the exploration matrices' Z instead of the policy's own ([B, H, A] per environment or [H, A])."""
         f, A = self._fz, self.action_dim
         h = torch.tanh(torch.addmm(f["b1"], obs.flatten(1), f["w1"]))
         h = torch.tanh(torch.addmm(f["b2"], h, f["w2"]))
         out = torch.addmm(f["bh"], h, f["wh"])
         mean = out[:, :A]
+        if self.use_sde:
+            std = f["std"]
+            latent = h[:, :std.shape[0]]
+            actions = mean + self._sde_sample_noise(latent, std, noise)
+            scale = torch.sqrt((latent ** 2) @ (std ** 2) + SDE_EPSILON)
+            log_probs = (-((actions - mean) ** 2) / (2 * scale ** 2) - scale.log() - math.log(math.sqrt(2 * math.pi))).sum(dim=1)
+            return actions, out[:, A], log_probs
         if noise is None:
             noise = torch.randn(mean.shape, generator=generator, device=mean.device, dtype=mean.dtype)
         actions = torch.addcmul(mean, noise, f["std"])
@@ -305,8 +366,62 @@ class ActorCritic(torch.nn.Module):
         return actions, out[:, A], log_probs
 
     def evaluate_actions(self, obs, actions):
-        d = self._dist(obs)
+        d, _ = self._dist(obs)
         return self.predict_values(obs), d.log_prob(actions).sum(dim=1), d.entropy().sum(dim=1)
+
+    # ---- stable-baselines3 checkpoints ----------------------------------------------------------------------------------
+    _SB3_KEYS = {"mlp_extractor.policy_net.0.weight": "pi.0.weight", "mlp_extractor.policy_net.0.bias": "pi.0.bias",
+                 "mlp_extractor.policy_net.2.weight": "pi.2.weight", "mlp_extractor.policy_net.2.bias": "pi.2.bias",
+                 "mlp_extractor.value_net.0.weight": "vf.0.weight", "mlp_extractor.value_net.0.bias": "vf.0.bias",
+                 "mlp_extractor.value_net.2.weight": "vf.2.weight", "mlp_extractor.value_net.2.bias": "vf.2.bias",
+                 "action_net.weight": "action_net.weight", "action_net.bias": "action_net.bias",
+                 "value_net.weight": "value_net.weight", "value_net.bias": "value_net.bias", "log_std": "log_std"}
+
+    @classmethod
+    def load_sb3(cls, path, device="cpu"):
+        """An SB3 `.zip` (BaseAlgorithm.save: `data` JSON + `policy.pth` state dict) of the reference's MlpPolicy agents ->
+        (ActorCritic, meta).  `policy.pth` goes through torch.load(weights_only=True); `data` is read as JSON and none of
+        its `:serialized:` (pickled) fields is ever unpickled.  meta = dict(version, use_sde, sde_sample_freq, action_dim,
+        algorithm) - algorithm "ppo" / "a2c" from the fields PPO alone saves, None when undecidable.
+        Like SB3's load, one exploration matrix is drawn for a gSDE policy (reset_noise(1))."""
+        import io
+        import json
+        import zipfile
+        try:
+            with zipfile.ZipFile(path) as z:
+                names = set(z.namelist())
+                if "policy.pth" not in names or "data" not in names:
+                    raise ValueError(f"{path}: not an SB3 checkpoint (needs `data` and `policy.pth`, has {sorted(names)})")
+                data = json.loads(z.read("data").decode("utf-8"))
+                sd = torch.load(io.BytesIO(z.read("policy.pth")), map_location="cpu", weights_only=True)
+        except zipfile.BadZipFile as e:
+            raise ValueError(f"{path}: not a zip archive") from e
+        missing = [k for k in cls._SB3_KEYS if k not in sd]
+        extra = [k for k in sd if k not in cls._SB3_KEYS]
+        if missing or extra:
+            raise ValueError(f"{path}: not an 80 -> H -> H MlpPolicy state dict (missing {missing}, unexpected {extra})")
+        use_sde = bool(data.get("use_sde", False))
+        A, H = int(sd["action_net.weight"].shape[0]), int(sd["mlp_extractor.policy_net.0.weight"].shape[0])
+        obs_dim = int(sd["mlp_extractor.policy_net.0.weight"].shape[1])
+        want_log_std = (H, A) if use_sde else (A,)
+        if tuple(sd["log_std"].shape) != want_log_std:
+            raise ValueError(f"{path}: use_sde={use_sde} needs log_std of shape {want_log_std}, "
+                             f"the checkpoint has {tuple(sd['log_std'].shape)}")
+        pol = cls(A, obs_dim=obs_dim, hidden=H, use_sde=use_sde)
+        own = pol.state_dict()
+        for k, name in cls._SB3_KEYS.items():
+            if tuple(sd[k].shape) != tuple(own[name].shape):
+                raise ValueError(f"{path}: {k} has shape {tuple(sd[k].shape)}, expected {tuple(own[name].shape)}")
+        pol.load_state_dict({name: sd[k].to(torch.float32) for k, name in cls._SB3_KEYS.items()})
+        pol = pol.to(device)
+        if use_sde:
+            pol.reset_noise(1)
+        version = data.get("version")
+        # PPO saves its clip range and epoch count; A2C (the other on-policy algorithm with n_steps / gae_lambda) neither
+        algorithm = "ppo" if "clip_range" in data else ("a2c" if "gae_lambda" in data and "n_epochs" not in data else None)
+        meta = dict(version=version if version in ("v0", "v1") else None, use_sde=use_sde,
+                    sde_sample_freq=int(data.get("sde_sample_freq", -1)), action_dim=A, algorithm=algorithm)
+        return pol, meta
 
 
 class RolloutBuffer:
@@ -404,13 +519,19 @@ class BatchedCollector:
     one stage (`MPC_FLAG_WARM_START`).
     use_graph: replay the step as one captured hipGraph (default on a GPU; `False` runs it eagerly, ~100 launches from
     Python per step).
+    gSDE (a policy built with use_sde=True, ActorCritic): one exploration matrix per environment, redrawn at every rollout
+    start (the reference's reset_noise(env.num_envs), agents/ppo_mpc.py:380-381) and, with sde_sample_freq > 0, every
+    sde_sample_freq steps of the rollout (:386-388).  The fused step draws the matrices inside mpc_policy_act_sde from a
+    device epoch counter (never stored, replayable in the captured graph); the torch step keeps them in `sde_noise`
+    [B, H, A], drawn from the collector's generator.
     """
 
     def __init__(self, env, policy: ActorCritic, engine, version: str = "v0", algorithm: str = "ppo",
                  n_steps: int = 64, gamma: float = 0.99, gae_lambda: float = 0.95,
                  default_weights=(1.0, 1.0, 1.0), collision_cost: bool = False, reset_mpc_on_done: bool = False,
                  gather_actions: bool = False, seed: int = 0, warm_start: bool = False,
-                 use_graph: bool | None = None, throughput: bool = False, fused_glue: bool | None = None):
+                 use_graph: bool | None = None, throughput: bool = False, fused_glue: bool | None = None,
+                 sde_sample_freq: int = -1):
         if version not in ("v0", "v1") or algorithm not in ("ppo", "a2c"):
             raise ValueError("version must be v0|v1 and algorithm ppo|a2c")
         if version == "v1" and policy.action_dim < 3:
@@ -419,6 +540,8 @@ class BatchedCollector:
         self.version, self.algorithm = version, algorithm
         self.collision_cost, self.reset_mpc_on_done, self.gather_actions = collision_cost, reset_mpc_on_done, gather_actions
         self.warm_start = bool(warm_start)
+        self.use_sde = bool(getattr(policy, "use_sde", False))
+        self.sde_sample_freq = int(sde_sample_freq)
         # several collectors stepping on their own streams (PipelinedCollector): MPC_FLAG_THROUGHPUT, the build of the solve
         # kernel for four resident waves per SIMD whatever this group's batch size (include/mpc_mi355x.h)
         self._mpc_kw = dict(throughput=True) if throughput else {}
@@ -459,6 +582,15 @@ class BatchedCollector:
             self._fg = dict(act=z(B, A), val=z(B), logp=z(B), w=z(B, 3, dt=torch.float64), rs=z(B, dt=torch.float64),
                             ticket=z(1, dt=torch.int32), noise=z(B, A), step=z(1, dt=torch.int64))
             self._noise_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+            if self.use_sde:
+                # gSDE: the exploration epoch the kernel keys its matrices by; a rollout draws from epochs sde_epoch ..
+                # sde_epoch + span - 1 (one per sde_sample_freq steps), and _begin_rollout moves past them
+                self._fg["sde_epoch"] = z(1, dt=torch.int64)
+                f = self.sde_sample_freq
+                self._sde_span = 1 if f <= 0 else -(-int(n_steps) // f)
+        if self.use_sde and not self.fused_glue:
+            H = policy.log_std.shape[0]
+            self.sde_noise = torch.zeros((B, H, policy.action_dim), dtype=policy.log_std.dtype, device=dev)
         # None = the default path: on a GPU with the real engine a step (policy -> MPC -> environment -> buffer row) is
         # captured once as a hipGraph and replayed; eager on the CPU, with stand-in engines, and when the actions are
         # all-gathered (the collective stays outside the graph)
@@ -505,6 +637,15 @@ class BatchedCollector:
         self.policy.refresh_fused()        # the parameters may have been updated since the last rollout
         self.buffer.reset()
         self._roll["counts"].zero_()
+        if self.use_sde:                   # new exploration matrices (agents/ppo_mpc.py:380-381)
+            self._sde_resample()
+
+    @torch.no_grad()
+    def _sde_resample(self):
+        if self.fused_glue:
+            self._fg["sde_epoch"].add_(self._sde_span)
+        else:
+            self.sde_noise.normal_(generator=self.gen)      # in place: a captured graph reads it at this address
 
     @torch.no_grad()
     def _rollout_step_fused(self):
@@ -521,11 +662,19 @@ class BatchedCollector:
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         obs = self._last_obs
         v1 = self.version == "v1"
-        rc = lib.mpc_policy_act(dev.index, B, A, H2, p(obs), p(f["w1"]), p(f["b1"]), p(f["w2"]), p(f["b2"]), p(f["wh"]),
-                                p(f["bh"]), p(f["std"]), p(f["c0"]), p(fg["noise"]), self._noise_seed,
-                                int(getattr(env, "env_offset", 0)), p(fg["step"]), 1 if v1 else 0,
-                                1 if self.algorithm == "ppo" else 0, p(fg["act"]), p(fg["val"]), p(fg["logp"]),
-                                p(fg["w"]) if v1 else None, None if v1 else p(fg["rs"]), stream)
+        if self.use_sde:
+            # gSDE: the matrices of epoch sde_epoch + pos // sde_sample_freq, drawn in the kernel (pos: the buffer's device row)
+            rc = lib.mpc_policy_act_sde(dev.index, B, A, H2, p(obs), p(f["w1"]), p(f["b1"]), p(f["w2"]), p(f["b2"]), p(f["wh"]),
+                                        p(f["bh"]), p(f["std"]), None, self._noise_seed, int(getattr(env, "env_offset", 0)),
+                                        p(fg["sde_epoch"]), p(buf.pos_dev), self.sde_sample_freq, 1 if v1 else 0,
+                                        1 if self.algorithm == "ppo" else 0, p(fg["act"]), p(fg["val"]), p(fg["logp"]),
+                                        p(fg["w"]) if v1 else None, None if v1 else p(fg["rs"]), stream)
+        else:
+            rc = lib.mpc_policy_act(dev.index, B, A, H2, p(obs), p(f["w1"]), p(f["b1"]), p(f["w2"]), p(f["b2"]), p(f["wh"]),
+                                    p(f["bh"]), p(f["std"]), p(f["c0"]), p(fg["noise"]), self._noise_seed,
+                                    int(getattr(env, "env_offset", 0)), p(fg["step"]), 1 if v1 else 0,
+                                    1 if self.algorithm == "ppo" else 0, p(fg["act"]), p(fg["val"]), p(fg["logp"]),
+                                    p(fg["w"]) if v1 else None, None if v1 else p(fg["rs"]), stream)
         if rc != 0:
             raise RuntimeError(f"mpc_policy_act failed ({rc}): {lib.mpc_last_error().decode()}")
         weights, ref_speed = (fg["w"], None) if v1 else (self.default_weights, fg["rs"])
@@ -563,7 +712,8 @@ class BatchedCollector:
         # (noise_feed: a list of per-step draws to consume instead of the generator's - how the tests give this path the
         # draws the glue kernel made)
         feed = getattr(self, "noise_feed", None)
-        actions, values, log_probs = self.policy.act(obs, generator=self.gen, noise=feed.pop(0) if feed else None)
+        noise = feed.pop(0) if feed else (self.sde_noise if self.use_sde else None)
+        actions, values, log_probs = self.policy.act(obs, generator=self.gen, noise=noise)
         weights, ref_speed = self.mpc_inputs(actions)
         self._mpc_out = self.engine.predict_batch_torch(obs, weights, ref_speed, collision_cost=self.collision_cost,
                                                         warm_start=self.warm_start, out=self._mpc_out, **self._mpc_kw)
@@ -660,6 +810,9 @@ class BatchedCollector:
         self._roll["dones"].zero_()
 
     def _step(self):
+        f = self.sde_sample_freq
+        if self.use_sde and not self.fused_glue and f > 0 and self.buffer.pos > 0 and self.buffer.pos % f == 0:
+            self._sde_resample()           # every sde_sample_freq steps (agents/ppo_mpc.py:386-388; the fused step keys by pos)
         if self._graph is not None:
             self._graph.replay()
             self.buffer.pos += 1
@@ -792,6 +945,11 @@ class OnPolicyTrainer:
            (defaults of config/cfg.yaml:66-86: lr 3e-4, 10 epochs, clip 0.2, gamma 0.99, lambda 0.95)
       a2c  one step on the whole buffer: -mean(A logp) + vf_coef * mse + ent_coef * (-mean entropy); RMSprop
            (alpha 0.99, eps 1e-5), no advantage normalisation, lambda 1 (config/cfg.yaml:31-61)
+
+    A gSDE policy (ActorCritic(use_sde=True)) needs nothing else here: evaluate_actions carries its distribution.  SB3's PPO
+    calls reset_noise(batch_size) before every minibatch (agents/ppo_mpc.py:243-244), but the loss never reads the
+    exploration matrices - log_prob and entropy depend only on the mean and on latent^2 @ exp(log_std)^2 - so those draws
+    cannot change the loss; they only renew matrices that the next rollout start redraws anyway.
     """
 
     def __init__(self, collector, learning_rate: float | None = None, n_epochs: int = 10,
@@ -868,3 +1026,71 @@ class OnPolicyTrainer:
             log.append(dict(roll, **upd, timesteps=self.col.num_timesteps,
                             mean_reward=self.col.mean_reward()))
         return log
+
+
+class MPCRLAgent:
+    """The reference's `trainer.predict(obs)` (trainers/trainer.py:342-368) for a batch of observations: the policy forward,
+    then the MPC with its output - version "v0" hands action 0 to the MPC as the reference speed, "v1" actions 0..2 as the
+    cost weights.  Like the reference the policy output is stochastic and NOT clipped, whatever the algorithm.
+
+    gSDE policies: the reference draws ONE exploration matrix when it loads a checkpoint (agents/ppo_mpc.py:627-628) and
+    predict never resamples, so every later prediction explores with that same matrix.  reset_noise() draws it per
+    environment (one matrix per row of the batch, kept until the next reset_noise()); without it the policy's single matrix
+    serves every row, as in the reference."""
+
+    def __init__(self, policy: ActorCritic, engine, version: str = "v0", algorithm: str = "ppo",
+                 default_weights=(1.0, 1.0, 1.0), collision_cost: bool = False):
+        if version not in ("v0", "v1") or algorithm not in ("ppo", "a2c"):
+            raise ValueError("version must be v0|v1 and algorithm ppo|a2c")
+        if version == "v1" and policy.action_dim < 3:
+            raise ValueError("v1 needs an action of at least 3 components (speed, control, input_diff weights)")
+        self.policy, self.engine, self.version, self.algorithm = policy, engine, version, algorithm
+        self.default_weights = tuple(float(w) for w in default_weights)
+        self.collision_cost = bool(collision_cost)
+
+    @classmethod
+    def from_sb3(cls, path, engine, device="cpu", **kw):
+        """Load an SB3 checkpoint (ActorCritic.load_sb3) and wrap it; version / algorithm from the checkpoint unless given."""
+        pol, meta = ActorCritic.load_sb3(path, device=device)
+        kw.setdefault("version", meta["version"] or "v0")
+        kw.setdefault("algorithm", meta["algorithm"] or "ppo")
+        return cls(pol, engine, **kw), meta
+
+    @torch.no_grad()
+    def reset_noise(self, n: int, generator=None):
+        self.policy.reset_noise(n, generator=generator)
+
+    @torch.no_grad()
+    def policy_output(self, obs, deterministic: bool = False, generator=None):
+        self.policy.eval()
+        obs = torch.as_tensor(obs, dtype=torch.float32, device=self.policy.log_std.device)
+        actions, _, _ = self.policy(obs, deterministic=deterministic, generator=generator)
+        return actions
+
+    def mpc_inputs(self, actions):
+        B, dev = actions.shape[0], actions.device
+        if self.version == "v0":
+            w = torch.tensor(self.default_weights, dtype=torch.float64, device=dev).repeat(B, 1).contiguous()
+            return w, actions[:, 0].to(torch.float64).contiguous()
+        return actions[:, :3].to(torch.float64).contiguous(), None
+
+    @torch.no_grad()
+    def predict_batch(self, obs_batch, deterministic: bool = False, generator=None):
+        """obs_batch [B, 10, 8] -> dict(act [B, 2], status, iters, rl_action [B, A]).  A torch tensor on a GPU goes through
+        engine.predict_batch_torch (zero-copy, synchronised before returning); anything else through engine.predict_batch."""
+        actions = self.policy_output(obs_batch, deterministic, generator)
+        weights, ref_speed = self.mpc_inputs(actions)
+        if actions.is_cuda and hasattr(self.engine, "predict_batch_torch"):
+            obs = torch.as_tensor(obs_batch, dtype=torch.float32, device=actions.device).contiguous()
+            out = self.engine.predict_batch_torch(obs, weights, ref_speed, collision_cost=self.collision_cost, sync=True)
+        else:
+            out = self.engine.predict_batch(np.asarray(torch.as_tensor(obs_batch, dtype=torch.float32).cpu()),
+                                            weights.cpu().numpy(), None if ref_speed is None else ref_speed.cpu().numpy(),
+                                            collision_cost=self.collision_cost)
+        return dict(out, rl_action=actions)
+
+    def predict(self, obs, deterministic: bool = False, generator=None):
+        """One observation [10, 8] -> the MPC action [2] (trainer.predict)."""
+        out = self.predict_batch(torch.as_tensor(obs, dtype=torch.float32)[None], deterministic, generator)
+        act = out["act"][0]
+        return act.cpu().numpy() if isinstance(act, torch.Tensor) else act

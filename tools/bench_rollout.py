@@ -31,6 +31,9 @@ def main():
                     help="fused HIP environment step (default on a GPU) or the vectorised torch ops")
     ap.add_argument("--max-iter", type=int, default=100, help="solver iteration cap (the reference: 1000)")
     ap.add_argument("--tol", type=float, default=1e-8, help="solver tolerance (the reference: 1e-6)")
+    ap.add_argument("--sde", action="store_true",
+                    help="gSDE exploration (ActorCritic(use_sde=True)): the reference PPO agents' policy class")
+    ap.add_argument("--sde-sample-freq", type=int, default=-1, help="with --sde: new exploration matrices every k steps")
     ap.add_argument("--groups", type=int, default=1,
                     help="split this rank's environments into G groups stepped on G HIP streams (PipelinedCollector)")
     a = ap.parse_args()
@@ -51,7 +54,7 @@ def main():
         B = hi - lo
         G = max(1, min(a.groups, B))
         torch.manual_seed(1234)          # the same untrained policy in every run and on every rank: reproducible rows
-        pol = rollout.ActorCritic(3 if a.version == "v1" else 1).to(dev)
+        pol = rollout.ActorCritic(3 if a.version == "v1" else 1, use_sde=a.sde).to(dev)
         engs, cols = [], []
         for g in range(G):
             glo, ghi = sharding.shard_range(B, g, G)
@@ -61,7 +64,8 @@ def main():
             engs.append(e_g)
             cols.append(rollout.BatchedCollector(env, pol, e_g, version=a.version, algorithm=a.algorithm, n_steps=a.steps,
                                                  collision_cost=False, gather_actions=use_dist and G == 1,
-                                                 seed=g, use_graph=a.graph, throughput=G > 1))
+                                                 seed=g, use_graph=a.graph, throughput=G > 1,
+                                                 sde_sample_freq=a.sde_sample_freq))
         col = cols[0] if G == 1 else rollout.PipelinedCollector(cols)
         col.collect_rollouts()                                   # warm-up (allocations, first launches)
         events = []
@@ -105,7 +109,7 @@ def main():
         st = torch.cat([c.last_mpc["status"] for c in cols]).cpu().numpy()
         if rank == 0:
             print(json.dumps(dict(config=f"{total} envs on {world} GPU(s), {a.others} other vehicles, {a.version}/{a.algorithm}, "
-                                         f"horizon 20, max_iter {a.max_iter}, tol {a.tol:g}" + (f", {G} groups on {G} streams" if G > 1 else "") + (", hipGraph step" if graph else ", eager step") + f", {cols[0].env.backend} environment",
+                                         f"horizon 20, max_iter {a.max_iter}, tol {a.tol:g}" + (f", {G} groups on {G} streams" if G > 1 else "") + (", hipGraph step" if graph else ", eager step") + f", {cols[0].env.backend} environment" + (f", gSDE (sample freq {a.sde_sample_freq})" if a.sde else ""),
                               envs=total, n_gpus=world, distributed=dist_info, graph_fallback_reason=cols[0].graph_fallback_reason, fused_glue=cols[0].fused_glue, groups=G, graph=bool(graph), env_backend=cols[0].env.backend,
                               steps_per_env=a.steps, env_steps_per_s=total * a.steps / dt, ms_per_step=dt / a.steps * 1e3,
                               mpc_ms_per_step=(dm / a.steps * 1e3) if events else None, episodes=stats["episodes"], crashed=stats["crashed"],
