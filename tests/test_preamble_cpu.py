@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import preamble_cases
 from conftest import GOLDEN, ROOT
 from test_host import CFG, Env, FakeEngine
 
@@ -298,11 +299,8 @@ def test_wave_form_equals_the_one_thread_form_on_long_tables_and_fast_egos(pre, 
     statement `preamble_env`, every output and the whole record bit for bit."""
     rng = np.random.default_rng(M * 31 + rows)
     # a straight-arc-straight route like the reference's, M points, ~0.7 m apart (so that 30 m/s x 3 s passes 128 segments)
-    s_ = np.arange(M) * 0.7
-    th = np.clip((s_ - 0.4 * s_[-1]) / 15.0, 0.0, np.pi / 2)
-    x = 2.0 - np.concatenate([[0.0], np.cumsum(0.7 * np.sin(th[:-1]))])
-    y = 50.0 - np.concatenate([[0.0], np.cumsum(0.7 * np.cos(th[:-1]))])
-    ref = np.stack([x, y, np.full(M, 10.0) + 20.0 * (np.arange(M) % 7 == 0), -np.pi / 2 - th], axis=1)
+    ref = preamble_cases.route(M)
+    x, y = ref[:, 0], ref[:, 1]
     B = 96
     one, wav = DevicePreamble(pre, ref, N=20, wave=False), DevicePreamble(pre, ref, N=20, wave=True)
     for t in range(14):
