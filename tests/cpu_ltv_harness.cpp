@@ -73,7 +73,7 @@ static int ltv_solve_batch_t(int B, int N, double dt, const double *ref_table, i
     return 0;
 }
 
-struct HostCtxLtv : HostCtx {};   // the code path of the three-waves-per-SIMD build (relax_bits = 0)
+struct HostCtxLtv : HostCtx {};   // the code path of the throughput build (relax_bits = 0)
 
 extern "C" int ltv_solve_batch(int B, int N, double dt, const double *ref_table, int M, const double *state, int max_iter,
                                int passes, double *u0, double *U, double *X, int32_t *status, int32_t *iters, int32_t *target) {

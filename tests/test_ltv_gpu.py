@@ -71,13 +71,16 @@ def test_batch_of_one_and_permutation(eng):
 
 
 def test_two_builds_of_the_ltv_kernel_agree(eng):
-    """mpc_ltv_kernel ships in two builds (mpc_engine.hip: launch_ltv): up to two waves per SIMD deep (B <= 2048 on 256
-    CUs) the 215-register one, deeper the 165-register one that runs three waves per SIMD.  The same instances through
-    both: statuses and iteration counts equal, profiles equal to 1e-9 (same statements; the compiler may contract a
-    multiply-add differently in the two)."""
-    st = ltv_states(4096, seed=11)
-    nom = np.random.default_rng(4).uniform(-0.2, 0.2, (4096, 20, 2))
-    deep = eng.ltv_solve_batch(st, nom)                       # 4096 instances: the three-wave build
+    """mpc_ltv_kernel ships in two builds (mpc_engine.hip: launch_ltv): the latency build for batches of at most
+    kLtvLatDepth waves per SIMD (Bt = 16 waves per CU, 4096 on 256 CUs; tests/ltv_cases.py), the throughput build for
+    deeper ones.  The same instances through both - Bt + 1 instances against the first 1024 alone: statuses and
+    iteration counts within one, profiles equal to 1e-9 (same statements; the compiler may contract a multiply-add
+    differently in the two)."""
+    from ltv_cases import build_batches
+    _, deep_B = build_batches()
+    st = ltv_states(deep_B, seed=11)
+    nom = np.random.default_rng(4).uniform(-0.2, 0.2, (deep_B, 20, 2))
+    deep = eng.ltv_solve_batch(st, nom)                       # Bt + 1 instances: the throughput build
     shallow = eng.ltv_solve_batch(st[:1024], nom[:1024])      # 1024: the latency build
     assert np.array_equal(deep["status"][:1024], shallow["status"])
     ok = shallow["status"] == 0
