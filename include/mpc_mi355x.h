@@ -345,6 +345,36 @@ int mpc_rollout_finish(int32_t device, int32_t T, int32_t B, int32_t A, int32_t 
                        double gae_lambda, float *advantages, float *returns, void *stream);
 
 /*
+ * mpc_episode_stats (an addition within ABI 8: old clients never call it, nothing else changes) - per-episode accounting of
+ * a closed-loop evaluation of B environments (the reference's model comparison, main/model_comparison.py:40-100, with the
+ * per-environment update in csrc/mpc_episode_stats.hpp).  Device pointers, enqueue only on `stream`, never synchronises
+ * (capturable in a hipGraph); one thread per environment, no scratch.  One launch per policy step, after mpc_synth_env_step.
+ *
+ * Inputs of a step: done, truncated, crashed, arrived [B] u8 and reward [B] f32 (the environment's outputs), ego [B][4] f64
+ * (x, y, heading, speed after the step and its auto-reset), status and iters [B] i32 (the step's MPC solve).
+ * Running state, zero-initialised by a reset launch: state_i32 [5][B] = steps of the current episode, crashed on any step,
+ * unsolved solves (not MPC_STATUS_IS_SOLVED: right for the NLP and the LTV statuses), largest iteration count, episode
+ * ordinal j; state_f64 [3][B] = sum of the speeds before each step, return (f64 sum of the f32 rewards), carry_speed.
+ * Records, one slot per (environment b, ordinal j < Q): rec_i32 [6][B][Q] = steps, success (arrived), collision (crashed on
+ * any step of the episode; crash and arrival on one step set both, as in the reference), truncated, unsolved, max_iters;
+ * rec_f64 [2][B][Q] = average speed (speed sum / steps), return.
+ *
+ * The speed summed at a step is the ego speed BEFORE it: every launch ends by storing ego[b][3] in carry_speed, the next one
+ * adds it.  reset != 0 (issue it after the environments' reset; the step inputs may be NULL): initialise the running state and
+ * carry_speed, and recorded[0] = 0.  Otherwise, for every environment: steps += 1, speed sum += carry_speed, return +=
+ * reward, crashed |= crashed[b], unsolved += !solved, max_iters = max(max_iters, iters[b]); when done[b]: if j < Q write slot
+ * [b][j] and recorded[0] += 1; then clear the running state and j += 1 (up to Q: an environment whose Q episodes are
+ * recorded keeps stepping with the batch and writes nothing).  A fixed quota per environment keeps the evaluated episodes
+ * independent of how long other environments' episodes last and of how the batch is sharded.
+ * step_counter (optional, non-reset launches): step_counter[0] += 1 - mpc_policy_act's noise_step for a stochastic policy.
+ * Errors: B < 0, Q < 1, a NULL state / record / recorded pointer, or a NULL step input of a non-reset launch.
+ */
+int mpc_episode_stats(int32_t device, int32_t B, int32_t Q, int32_t reset, const uint8_t *done, const uint8_t *truncated,
+                      const uint8_t *crashed, const uint8_t *arrived, const float *reward, const double *ego,
+                      const int32_t *status, const int32_t *iters, int32_t *state_i32, double *state_f64, int32_t *rec_i32,
+                      double *rec_f64, int64_t *recorded, int64_t *step_counter, void *stream);
+
+/*
  * Diagnostics: the NLP's functions at GIVEN points, evaluated by the solve kernel's own code (csrc/mpc_wave.hpp:
  * Solver::evaluate - stage_terms / track / dist, which judge every line-search trial, and the model step of the rollouts),
  * so that f(z) and g(z) computed by the reference's statements (agents/pure_mpc.py:128-283; tests/golden/

@@ -28,6 +28,7 @@
 #include "mpc_preamble_wave.hpp"
 #include "mpc_synth_env.hpp"
 #include "mpc_rollout_glue.hpp"
+#include "mpc_episode_stats.hpp"
 
 namespace {
 
@@ -719,6 +720,20 @@ __global__ __launch_bounds__(128) void mpc_rollout_record_kernel(mpc::glue::Reco
             *pos_dev = pos + 1;
             if (step_counter) *step_counter += 1;      // policy steps taken so far: keys the next step's noise
         }
+    }
+}
+
+// per-episode accounting of a closed-loop evaluation (mpc_episode_stats.hpp): one thread per environment; each record slot
+// has one writer, `recorded` counts the finished episodes that wrote one (one atomic add each)
+__global__ __launch_bounds__(256) void mpc_episode_stats_kernel(mpc::stats::Accounts acc, mpc::stats::StepInputs in, int reset,
+                                                                unsigned long long *__restrict__ recorded,
+                                                                long long *__restrict__ step_counter) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= acc.B) return;
+    if (mpc::stats::episode_update(acc, in, b, reset != 0)) atomicAdd(recorded, 1ull);
+    if (b == 0) {
+        if (reset) *recorded = 0ull;                      // a reset launch writes no record: no add races with this
+        else if (step_counter) *step_counter += 1;        // policy steps taken so far: keys mpc_policy_act's next noise
     }
 }
 
@@ -1698,6 +1713,26 @@ int mpc_rollout_finish(int32_t device, int32_t T, int32_t B, int32_t A, int32_t 
                               (float)gamma, (float)(gamma * gae_lambda), advantages, returns};
     hipLaunchKernelGGL(mpc_rollout_finish_kernel, dim3((unsigned)B), dim3(256), (size_t)T * 2 * sizeof(float),
                        reinterpret_cast<hipStream_t>(stream_), g);
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_episode_stats(int32_t device, int32_t B, int32_t Q, int32_t reset, const uint8_t *done, const uint8_t *truncated,
+                      const uint8_t *crashed, const uint8_t *arrived, const float *reward, const double *ego,
+                      const int32_t *status, const int32_t *iters, int32_t *state_i32, double *state_f64, int32_t *rec_i32,
+                      double *rec_f64, int64_t *recorded, int64_t *step_counter, void *stream_) {
+    if (B < 0 || Q < 1) return fail(MPC_ERR_INVALID_ARG, "mpc_episode_stats: bad size (B >= 0, Q >= 1)");
+    if (!ego || !state_i32 || !state_f64 || !rec_i32 || !rec_f64 || !recorded)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_episode_stats: null state / record pointer");
+    if (!reset && (!done || !truncated || !crashed || !arrived || !reward || !status || !iters))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_episode_stats: null step-input pointer");
+    if (B == 0) return MPC_OK;
+    HIP_TRY(hipSetDevice(device));
+    const mpc::stats::Accounts acc{(int)B, (int)Q, state_i32, state_f64, rec_i32, rec_f64};
+    const mpc::stats::StepInputs in{done, truncated, crashed, arrived, reward, ego, status, iters};
+    hipLaunchKernelGGL(mpc_episode_stats_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream_), acc, in, (int)reset,
+                       reinterpret_cast<unsigned long long *>(recorded), reinterpret_cast<long long *>(step_counter));
     HIP_TRY(hipGetLastError());
     return MPC_OK;
 }

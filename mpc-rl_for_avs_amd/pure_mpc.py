@@ -302,6 +302,20 @@ class PureMPC_Agent:
             print(f"NOTICE: Not found solution ({bad} of {B} instances)")
         return out["act"]
 
+    def act_batch_torch(self, obs, deterministic=False, seed=0, env_offset=0):
+        """Closed-loop evaluation (evaluate.evaluate_agent): obs float32 device tensor [B, vehicles_count, 8] -> dict(act [B, 2]
+        f64, status, iters) through engine.predict_batch_torch with the agent's default weights, collision cost and warm start;
+        enqueue-only, the same output tensors every call.  deterministic / seed / env_offset: the MPC draws nothing."""
+        import torch
+        B, st = int(obs.shape[0]), getattr(self, "_act_state", None)
+        if st is None or st["w"].shape[0] != B or st["w"].device != obs.device:
+            w = [float(self.default_weights[f"weight_{k}"]) for k in PureMPC_Agent.weight_components]
+            st = self._act_state = dict(w=torch.tensor(w, dtype=torch.float64, device=obs.device).repeat(B, 1).contiguous(),
+                                        out=None)
+        st["out"] = self._engine.predict_batch_torch(obs, st["w"], None, collision_cost=self.collision_cost,
+                                                     warm_start=self.warm_start, out=st["out"])
+        return st["out"]
+
     def batch_env_state(self, B):
         """is_collide / ego_index / collision_memory / stop_index / conflict_index / conflict_points of environments
         0..B-1 after `predict_batch` (the batched counterpart of the attributes `predict` leaves on the agent)."""

@@ -1089,6 +1089,100 @@ class MPCRLAgent:
                                             collision_cost=self.collision_cost)
         return dict(out, rl_action=actions)
 
+    # ---- closed-loop evaluation (evaluate.evaluate_agent) ---------------------------------------------------------------
+    @torch.no_grad()
+    def act_batch_torch(self, obs, deterministic: bool = False, seed: int = 0, env_offset: int = 0):
+        """obs float32 device tensor [B, 10, 8] -> dict(act [B, 2] f64, status, iters, step, generator): the policy, then the
+        MPC through engine.predict_batch_torch, mapped like mpc_inputs and unclipped (trainer.predict).  Enqueue-only, the same
+        output tensors every call.  On a GPU with the real engine the policy is one launch (mpc_policy_act / _sde, the
+        collector's kernels), otherwise ActorCritic.act.
+          deterministic  the mean
+          stochastic     fused: noise keyed by (seed, env_offset + b, step), `step` the int64 [1] counter the caller
+                         advances once per step (mpc_episode_stats does); torch: drawn from `generator` (seeded by seed)
+          gSDE           one exploration matrix per environment for the whole evaluation (what reset_noise(B) draws, never
+                         resampled, agents/ppo_mpc.py:627-628): fused, keyed by (seed, env_offset + b, epoch 0); torch, drawn
+                         once from a generator seeded by seed
+        restart_actions() puts the counters / matrices back to their start."""
+        import ctypes
+        B, dev = int(obs.shape[0]), obs.device
+        key = (B, dev, bool(deterministic), int(seed), int(env_offset))
+        st = getattr(self, "_act_state", None)
+        if st is None or st["key"] != key:
+            st = self._act_init(key)
+        pol, v1 = self.policy, self.version == "v1"
+        if st["fused"]:
+            f, fg, A = pol._fz, st["fg"], pol.action_dim
+            lib = self.engine._lib
+            p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            seed64 = int(seed) & 0xFFFFFFFFFFFFFFFF
+            common = (p(fg["act"]), p(fg["val"]), p(fg["logp"]), p(fg["w"]) if v1 else None, None if v1 else p(fg["rs"]), stream)
+            if pol.use_sde:
+                rc = lib.mpc_policy_act_sde(dev.index, B, A, f["b1"].numel(), p(obs), p(f["w1"]), p(f["b1"]), p(f["w2"]),
+                                            p(f["b2"]), p(f["wh"]), p(f["bh"]), p(f["std"]), p(st["noise"]), seed64,
+                                            int(env_offset), p(fg.get("sde_epoch")), None, -1, 1 if v1 else 0, 0, *common)
+            else:
+                rc = lib.mpc_policy_act(dev.index, B, A, f["b1"].numel(), p(obs), p(f["w1"]), p(f["b1"]), p(f["w2"]), p(f["b2"]),
+                                        p(f["wh"]), p(f["bh"]), p(f["std"]), p(f["c0"]), p(fg["noise"]), seed64, int(env_offset),
+                                        p(st["step"]), 1 if v1 else 0, 0, *common)
+            if rc != 0:
+                raise RuntimeError(f"mpc_policy_act failed ({rc}): {lib.mpc_last_error().decode()}")
+            weights, ref_speed = (fg["w"], None) if v1 else (st["w"], fg["rs"])
+        else:
+            actions, _, _ = pol.act(obs, generator=st["gen"], noise=st["noise"])
+            weights, ref_speed = (actions[:, :3].to(torch.float64).contiguous(), None) if v1 else \
+                (st["w"], actions[:, 0].to(torch.float64).contiguous())
+        st["out"] = self.engine.predict_batch_torch(obs, weights, ref_speed, collision_cost=self.collision_cost, out=st["out"])
+        draws = not st["fused"] and not deterministic and not pol.use_sde
+        return dict(st["out"], step=st["step"], generator=st["gen"] if draws else None)
+
+    def _act_init(self, key):
+        B, dev, deterministic, seed, _ = key
+        pol = self.policy
+        pol.eval()
+        pol.refresh_fused()
+        A, H = pol.action_dim, pol.pi[0].out_features
+        z = lambda *sh, dt=torch.float32: torch.zeros(sh, dtype=dt, device=dev)
+        fused = (dev.type == "cuda" and hasattr(self.engine, "_lib") and hasattr(self.engine, "predict_batch_torch") and
+                 pol.pi[0].in_features == VEHICLES_COUNT * 8 and 2 * H <= 256 and A <= 8 and pol.log_std.dtype == torch.float32)
+        st = dict(key=key, fused=fused, out=None, step=None, gen=None, noise=None,
+                  w=torch.tensor(self.default_weights, dtype=torch.float64, device=dev).repeat(B, 1).contiguous())
+        if fused:
+            st["fg"] = dict(act=z(B, A), val=z(B), logp=z(B), w=z(B, 3, dt=torch.float64), rs=z(B, dt=torch.float64),
+                            noise=z(B, A))
+            if pol.use_sde:
+                if deterministic:
+                    st["noise"] = z(B, H, A)               # read by the kernel: latent @ (std * 0) = 0
+                else:
+                    st["fg"]["sde_epoch"] = z(1, dt=torch.int64)
+            elif not deterministic:
+                st["step"] = z(1, dt=torch.int64)
+        else:
+            if deterministic:
+                st["noise"] = z(B, H, A) if pol.use_sde else z(B, A)
+            else:
+                st["gen"] = torch.Generator(device=dev)
+                st["gen"].manual_seed(seed)
+                if pol.use_sde:
+                    st["noise"] = z(B, H, A, dt=pol.log_std.dtype).normal_(generator=st["gen"])
+        self._act_state = st
+        return st
+
+    @torch.no_grad()
+    def restart_actions(self):
+        """Put the evaluation's noise counter, generator and exploration matrices back to where act_batch_torch started them
+        (in place: a captured graph reads them at their addresses)."""
+        st = getattr(self, "_act_state", None)
+        if st is None:
+            return
+        self.policy.refresh_fused()
+        if st["step"] is not None:
+            st["step"].zero_()
+        if st["gen"] is not None:
+            st["gen"].manual_seed(st["key"][3])
+            if self.policy.use_sde:
+                st["noise"].normal_(generator=st["gen"])
+
     def predict(self, obs, deterministic: bool = False, generator=None):
         """One observation [10, 8] -> the MPC action [2] (trainer.predict)."""
         out = self.predict_batch(torch.as_tensor(obs, dtype=torch.float32)[None], deterministic, generator)

@@ -1,0 +1,253 @@
+"""Closed-loop evaluation on the CPU: the episode accounting of csrc/mpc_episode_stats.hpp (host build) and the evaluator's
+torch accounting against a plain-Python restatement of the reference's per-episode bookkeeping (main/model_comparison.py:
+40-100), bit for bit; evaluate_agent with the torch environment and a stub engine against a per-environment replay of the
+same steps; the loop's bound and its argument checks."""
+import numpy as np
+import pytest
+import torch
+
+import episode_stats_host as esh
+from mpc_rl_for_avs_amd import evaluate, rollout
+from mpc_rl_for_avs_amd.pure_mpc import PureMPC_Agent
+
+KEYS = evaluate.REC_I32 + evaluate.REC_F64
+
+
+def random_stream(B, T, Q, seed, reset_at=None):
+    """T steps of B environments with the termination rules of the synthetic environment: crash or arrival ends an episode,
+    200 steps truncate.  Some environments never crash nor arrive (truncation only); crash and arrival on one step occur.
+    reset_at: a restart of the evaluation (the string "reset" with the ego state) before that step."""
+    rng = np.random.default_rng(seed)
+    p_end = rng.choice([0.0, 0.004, 0.02, 0.08], size=B)
+    p_end[0] = 0.0                                               # environment 0: truncations only
+    t = np.zeros(B, np.int64)
+    ego = np.zeros((B, 4))
+    ego[:, 3] = rng.uniform(0, 30, B)
+    steps = [dict(reset=True, ego=ego.copy())]
+    for k in range(T):
+        if k == reset_at:
+            t[:] = 0
+            ego[:, 3] = rng.uniform(0, 30, B)
+            steps.append(dict(reset=True, ego=ego.copy()))
+        t += 1
+        crashed = rng.random(B) < p_end
+        arrived = rng.random(B) < p_end
+        both = rng.random(B) < p_end / 4
+        crashed |= both
+        arrived |= both
+        terminated = crashed | arrived
+        truncated = (t >= rollout.EPISODE_STEPS) & ~terminated
+        done = terminated | truncated
+        t[done] = 0
+        ego[:, 3] = np.clip(ego[:, 3] + rng.normal(0, 1, B), 0, 30)
+        ego[done, 3] = rng.uniform(5, 15, int(done.sum()))           # auto-reset: the next episode's initial speed
+        steps.append(dict(done=done, truncated=truncated, crashed=crashed, arrived=arrived,
+                          reward=rng.normal(0, 50, B).astype(np.float32), ego=ego.copy(),
+                          status=rng.integers(0, 9, B).astype(np.int32), iters=rng.integers(0, 101, B).astype(np.int32)))
+    return steps
+
+
+def _run_host(steps, B, Q):
+    h = esh.HostStats(B, Q)
+    for s in steps:
+        h.update(s, reset=bool(s.get("reset")))
+    return h
+
+
+def _expected_recorded(steps, B, Q):
+    n = np.zeros(B, np.int64)
+    for s in steps:
+        if s.get("reset"):
+            n[:] = 0
+        else:
+            n += s["done"]
+    return int(np.minimum(n, Q).sum())
+
+
+def _assert_records_equal(got, want):
+    for k in KEYS:
+        g, w = np.asarray(got[k]), np.asarray(want[k])
+        assert g.shape == w.shape, k
+        if g.dtype == np.float64:
+            assert np.array_equal(g.view(np.int64), w.view(np.int64)), k        # bit for bit
+        else:
+            assert np.array_equal(g.astype(np.int64), w.astype(np.int64)), k
+
+
+@pytest.mark.parametrize("B", [1, 63, 257])
+@pytest.mark.parametrize("Q", [1, 3])
+def test_host_build_of_the_kernel_is_the_reference_bookkeeping(B, Q):
+    T = Q * rollout.EPISODE_STEPS + 60                 # long enough for idle environments
+    steps = random_stream(B, T, Q, seed=100 * B + Q, reset_at=30)     # every quota is filled after the reset
+    h = _run_host(steps, B, Q)
+    want = esh.replay(steps, B, Q)
+    _assert_records_equal(h.records(), want)
+    assert int(h.recorded[0]) == _expected_recorded(steps, B, Q)
+    assert int(h.step_counter[0]) == T                 # one per non-reset launch
+    rec = h.records()
+    written = rec["steps"] > 0
+    assert written.any()
+    # the edge cases occurred: truncation at 200, crash + arrival in one episode, idle environments after their quota
+    assert (rec["truncated"] & written).any() and np.all(rec["steps"][rec["truncated"]] == rollout.EPISODE_STEPS)
+    assert not (rec["truncated"] & rec["success"]).any()
+    if B > 1:
+        assert (rec["success"] & rec["collision"]).any()
+    assert written.all() and np.all(h.state_i32[4] == Q)
+
+
+def test_reset_partway_restarts_the_ordinals_and_the_count():
+    B, Q = 16, 2
+    steps = random_stream(B, 150, Q, seed=5, reset_at=120)
+    h = _run_host(steps, B, Q)
+    _assert_records_equal(h.records(), esh.replay(steps, B, Q))
+    assert int(h.recorded[0]) == _expected_recorded(steps, B, Q)
+    # a reset alone: state cleared, carry speed = ego speed
+    h.update(dict(ego=steps[-1]["ego"]), reset=True)
+    assert not h.state_i32.any() and not h.state_f64[:2].any() and int(h.recorded[0]) == 0
+    assert np.array_equal(h.state_f64[2], steps[-1]["ego"][:, 3])
+
+
+@pytest.mark.parametrize("B,Q", [(1, 1), (63, 3), (257, 1)])
+def test_torch_accounting_is_the_host_build_bit_for_bit(B, Q):
+    T = Q * rollout.EPISODE_STEPS + 40
+    steps = random_stream(B, T, Q, seed=7 * B + Q, reset_at=T // 2)
+    h = _run_host(steps, B, Q)
+    s = evaluate.EpisodeStats(B, Q, "cpu", "torch")
+    ctr = torch.zeros(1, dtype=torch.int64)
+    for st in steps:
+        t = {k: torch.as_tensor(v) for k, v in st.items() if k != "reset"}
+        if st.get("reset"):
+            s.update(t["ego"], reset=True, step_counter=ctr)
+        else:
+            s.update(**t, step_counter=ctr)
+    for name in ("state_i32", "state_f64", "rec_i32", "rec_f64", "recorded"):
+        g, w = getattr(s, name).numpy(), getattr(h, name)
+        assert np.array_equal(g.view(np.uint8), np.ascontiguousarray(w).view(np.uint8)), name
+    assert int(ctr[0]) == T
+    _assert_records_equal(s.records(), esh.replay(steps, B, Q))
+
+
+class Env:
+    config = {"simulation_frequency": 30, "policy_frequency": 10, "observation": {"vehicles_count": 10}}
+
+
+CFG = dict(horizon=20, render=False, weight_speed=1, weight_control=1, weight_input_diff=1)
+
+
+class StubEngine:
+    """Stands in for MPCEngine.predict_batch_torch: a speed controller with a slight steer, and a status / iteration count
+    that vary with the observation (unsolved solves occur)."""
+
+    def __init__(self):
+        self.resets = 0
+
+    def predict_batch_torch(self, obs, weights, ref_speed=None, collision_cost=False, out=None, sync=False,
+                            warm_start=False):
+        B = obs.shape[0]
+        v = torch.hypot(obs[:, 0, 3], obs[:, 0, 4]).double()
+        target = 8.0 if ref_speed is None else 8.0 + 4.0 * ref_speed
+        act = torch.stack([torch.clamp(target - v, -5.0, 2.0), 0.02 * torch.ones_like(v)], dim=1)
+        key = (obs[:, 0, 2] * 37).floor().to(torch.int64)
+        return dict(act=act, status=(key % 9).to(torch.int32), iters=(key % 50 + 3).to(torch.int32))
+
+    def reset_env_mask_torch(self, done, warm_only=False):
+        self.resets += 1
+
+    def reset_env_state(self, env_ids=None):
+        pass
+
+
+def _replay_eval(agent, B, Q, seed=3, **kw):
+    env = rollout.SyntheticIntersectionEnv(B, device="cpu", seed=seed, n_others=4, backend="torch")
+    seen = []
+    take = lambda d: {k: (v.clone().numpy() if isinstance(v, torch.Tensor) else v) for k, v in d.items()}
+    res = evaluate.evaluate_agent(agent, env, episodes_per_env=Q, use_graph=False, poll_every=5,
+                                  on_step=lambda d: seen.append(take(d)), **kw)
+    return res, seen
+
+
+def _reference_summary(rec, dt):
+    n = rec["steps"].size
+    s = dict(successes=0, collisions=0, total_steps=0, total_speed=0.0, total_time=0.0)
+    for b in range(rec["steps"].shape[0]):                       # model_comparison.py:160-172, one episode at a time
+        for j in range(rec["steps"].shape[1]):
+            s["successes"] += int(rec["success"][b, j])
+            s["collisions"] += int(rec["collision"][b, j])
+            s["total_steps"] += int(rec["steps"][b, j])
+            s["total_speed"] += float(rec["avg_speed"][b, j])
+            s["total_time"] += int(rec["steps"][b, j]) * dt
+    return dict(success_rate=s["successes"] / n * 100, collision_rate=s["collisions"] / n * 100,
+                avg_steps=s["total_steps"] / n, avg_speed=s["total_speed"] / n, avg_travel_time=s["total_time"] / n)
+
+
+@pytest.mark.parametrize("B,Q", [(8, 1), (24, 2)])
+def test_evaluate_agent_is_a_per_environment_replay_of_its_steps(B, Q):
+    agent = PureMPC_Agent(Env(), dict(CFG), engine=StubEngine(), collision_cost=True)
+    res, seen = _replay_eval(agent, B, Q)
+    want = esh.replay(seen, B, Q)
+    _assert_records_equal(res.records, want)
+    rec = res.records
+    assert (rec["steps"] >= 1).all() and (rec["steps"] <= rollout.EPISODE_STEPS).all()
+    assert res.steps == len(seen) - 1 and res.steps <= Q * rollout.EPISODE_STEPS
+    assert res.env_steps == res.steps * B
+    summ = res.summary()
+    for k, v in _reference_summary(rec, 0.1).items():
+        assert summ[k] == pytest.approx(v, rel=1e-12, abs=1e-12), k
+    assert summ["episodes"] == B * Q
+    assert summ["unsolved_frac"] == pytest.approx(rec["unsolved"].sum() / rec["steps"].sum())
+    assert 0 < summ["unsolved_frac"] < 1
+    assert summ["mean_return"] == pytest.approx(rec["return"].mean())
+    assert np.array_equal(res.travel_time, rec["steps"] * 0.1)
+
+
+def test_evaluate_agent_resets_the_mpc_on_done_when_asked():
+    eng = StubEngine()
+    agent = PureMPC_Agent(Env(), dict(CFG), engine=eng)
+    res, _ = _replay_eval(agent, 4, 1, reset_mpc_on_done=True)
+    assert eng.resets == res.steps
+    eng2 = StubEngine()
+    _replay_eval(PureMPC_Agent(Env(), dict(CFG), engine=eng2), 4, 1)
+    assert eng2.resets == 0
+
+
+@pytest.mark.parametrize("algorithm,version,use_sde,deterministic",
+                         [("ppo", "v0", True, False), ("ppo", "v0", True, True), ("a2c", "v0", False, False),
+                          ("ppo", "v1", False, True)])
+def test_mpcrl_agent_runs_in_closed_loop_on_the_cpu(algorithm, version, use_sde, deterministic):
+    torch.manual_seed(0)
+    pol = rollout.ActorCritic(4 if version == "v1" else 1, use_sde=use_sde, log_std_init=-1.0)
+    agent = rollout.MPCRLAgent(pol, StubEngine(), version=version, algorithm=algorithm)
+    res, seen = _replay_eval(agent, 12, 1, deterministic=deterministic, seed=11)
+    _assert_records_equal(res.records, esh.replay(seen, 12, 1))
+    again, _ = _replay_eval(agent, 12, 1, deterministic=deterministic, seed=11)     # restart_actions: the same draws
+    _assert_records_equal(again.records, res.records)
+
+
+def test_the_loop_is_bounded_by_the_quota_times_200_steps():
+    class NeverDone(rollout.SyntheticIntersectionEnv):
+        calls = 0
+
+        def step(self, action):
+            NeverDone.calls += 1
+            obs, reward, done, info = super().step(action)
+            info = {k: (torch.zeros_like(v) if k != "terminal_obs" else v) for k, v in info.items()}
+            return obs, reward, torch.zeros_like(done), info
+
+    env = NeverDone(4, device="cpu", seed=1, backend="torch")
+    agent = PureMPC_Agent(Env(), dict(CFG), engine=StubEngine())
+    with pytest.raises(RuntimeError, match="episodes recorded"):
+        evaluate.evaluate_agent(agent, env, episodes_per_env=2, use_graph=False, poll_every=7)
+    assert NeverDone.calls == 2 * rollout.EPISODE_STEPS
+
+
+def test_invalid_arguments_raise_value_error():
+    env = rollout.SyntheticIntersectionEnv(4, device="cpu", backend="torch")
+    agent = PureMPC_Agent(Env(), dict(CFG), engine=StubEngine())
+    with pytest.raises(ValueError):
+        evaluate.evaluate_agent(agent, env, episodes_per_env=0)
+    with pytest.raises(ValueError):
+        evaluate.evaluate_agent(object(), env)
+    with pytest.raises(ValueError):
+        evaluate.evaluate_agent(agent, env, poll_every=0)
+    with pytest.raises(ValueError):
+        evaluate.evaluate_agent(agent, env, use_graph=True)          # the graph needs the HIP environment
