@@ -1,6 +1,7 @@
 """Build the gfx950 shared library of the engine in-tree with hipcc (no JIT cache, no pip install)."""
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -8,9 +9,8 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmpc_mi355x.so")
 _SOURCES = [os.path.join(_HERE, "csrc", "mpc_engine.hip")]
-_DEPS = _SOURCES + [os.path.join(_HERE, "csrc", f) for f in ("mpc_core.hpp", "mpc_wave.hpp", "mpc_ltv.hpp",
-                                                              "mpc_preamble.hpp", "mpc_preamble_wave.hpp", "mpc_wave_dev.hpp", "mpc_synth_env.hpp", "mpc_rollout_glue.hpp",
-                                                              "mpc_episode_stats.hpp")] + \
+# every header under csrc/ (globbed, so a new one cannot be forgotten) and the ABI header
+_DEPS = _SOURCES + sorted(glob.glob(os.path.join(_HERE, "csrc", "*.hpp"))) + \
     [os.path.join(os.path.dirname(_HERE), "include", "mpc_mi355x.h")]
 
 

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -756,43 +757,55 @@ __global__ __launch_bounds__(256) void mpc_rollout_finish_kernel(mpc::glue::GaeA
     for (int t = threadIdx.x; t < g.T; t += blockDim.x) mpc::glue::gae_store(g, b, t, delta[t]);
 }
 
+// device memory the handle owns: released when the handle is deleted (mpc_destroy), so a buffer added to mpc_handle is
+// freed without a second edit
+template <class T>
+struct DevPtr {
+    T *p = nullptr;
+    DevPtr() = default;
+    DevPtr(const DevPtr &) = delete;
+    DevPtr &operator=(const DevPtr &) = delete;
+    ~DevPtr() { if (p) (void)hipFree(p); }
+    operator T *() const { return p; }
+};
+
+// ... one that is grown on demand and reused across calls (grow() below)
+struct GrowBuf : DevPtr<void> {
+    size_t bytes = 0;
+};
+
 }  // namespace
 
 struct mpc_handle {
     mpc_config cfg;
     int device = 0;
-    double *d_ref = nullptr;  // [M][REF_COLS] x y heading sin cos, followed by the speed column [M]
+    DevPtr<double> d_ref;  // [M][REF_COLS] x y heading sin cos, followed by the speed column [M]
     int M = 0;
     int num_cu = 256;
     size_t lds_per_cu = 160 * 1024;
-    // staging buffers for host-pointer calls
-    void *d_stage = nullptr;
-    size_t stage_bytes = 0;
+    GrowBuf stage;  // staging of host-pointer calls (Staging below)
     // observation-level path (mpc_predict_batch): per-environment detector state and the problem data the
     // preamble kernel writes for the solve kernel
-    mpc::pre::EnvState *d_env = nullptr;
-    int32_t *d_ids = nullptr;   // scratch of mpc_reset_env_state
-    int ids_cap = 0;
+    DevPtr<mpc::pre::EnvState> d_env;
+    GrowBuf ids;   // scratch of mpc_reset_env_state (int32)
     int env_cap = 0;
-    double *d_warm = nullptr;        // [env_cap][N][2] last control sequence per environment (MPC_FLAG_WARM_START)
-    uint8_t *d_warm_valid = nullptr; // [env_cap] 1 = d_warm holds a solution of the current episode
-    double *d_ltv_u = nullptr;       // [env_cap][N][2] stored profile (oa, od) of the iterative-linear agent per environment
-    void *d_pre = nullptr;
-    size_t pre_bytes = 0;
+    DevPtr<double> d_warm;         // [env_cap][N][2] last control sequence per environment (MPC_FLAG_WARM_START)
+    DevPtr<uint8_t> d_warm_valid;  // [env_cap] 1 = d_warm holds a solution of the current episode
+    DevPtr<double> d_ltv_u;        // [env_cap][N][2] stored profile (oa, od) of the iterative-linear agent per environment
+    GrowBuf pre;
     int pre_B = 0, pre_V = 0;   // shape of the last preamble output (for mpc_get_last_inputs)
-    double *p_state = nullptr, *p_vref = nullptr, *p_others = nullptr;
+    double *p_state = nullptr, *p_vref = nullptr, *p_others = nullptr;   // segments of `pre`
     int32_t *p_ego = nullptr, *p_nveh = nullptr;
     uint8_t *p_coll = nullptr;
     // diagnostics (mpc_set_diagnostics): polylines of the last preamble launch
     bool diag = false;
-    void *d_diag = nullptr;
-    size_t diag_bytes = 0;
+    GrowBuf diag_buf;
     int diag_B = 0, diag_V = 0;
-    double *g_ego = nullptr;
+    double *g_ego = nullptr;   // segments of `diag_buf`
     int32_t *g_len = nullptr;
     float *g_agents = nullptr;
-    // launch order of a batch (mpc_order_kernel): sized by ensure_order / mpc_reserve_envs
-    int32_t *d_order = nullptr;
+    // launch order of a batch (mpc_order_kernel): allocated once, by mpc_create
+    DevPtr<int32_t> d_order;
     int order_cap = 0;
 };
 
@@ -807,6 +820,118 @@ size_t carve(size_t &off, size_t bytes) {
     return o;
 }
 
+// Refusal of anything that frees or moves device memory while `stream` is being captured: the graph keeps addresses.
+// `remedy` is the call site's message (each tells the user a different way out).
+int refuse_in_capture(hipStream_t stream, const char *remedy) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (stream && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return fail(MPC_ERR_INVALID_ARG, remedy);
+    return MPC_OK;
+}
+
+// Grow a handle-owned buffer to at least `bytes` (contents are not kept).  The old buffer may still be in use by enqueued
+// (MPC_FLAG_NO_SYNC) work of any stream, and a captured graph holds its address: never inside a capture, and only once the
+// device is idle.  `remedy` = nullptr: the caller is synchronous by contract (host pointers) and cannot be captured.
+// On failure the buffer is left empty.
+int grow(GrowBuf &b, size_t bytes, hipStream_t stream, const char *remedy) {
+    if (b.bytes >= bytes) return MPC_OK;
+    if (int rc = remedy ? refuse_in_capture(stream, remedy) : MPC_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    void *old = b.p;
+    b.p = nullptr;
+    b.bytes = 0;
+    if (old) HIP_TRY(hipFree(old));
+    HIP_TRY(hipMalloc(&b.p, bytes));
+    b.bytes = bytes;
+    return MPC_OK;
+}
+
+// Host-pointer calls: every argument is copied through ONE handle-owned device buffer on the caller's stream.  An entry
+// point states each argument once - pointer, bytes, direction - gets its device view from ptr(), and ends with finish().
+// With device pointers (`dev`) every method hands the caller's pointer through and nothing is copied.  Two host-pointer
+// calls on one handle share the buffer; the synchronise at the end of the first is what serialises them.
+class Staging {
+  public:
+    Staging(mpc_handle *h, hipStream_t stream, bool dev) : h_(h), stream_(stream), dev_(dev) {}
+    // Each states one argument and returns its ticket for ptr().  A null `host` takes no room and stays null, or with
+    // kReserve gets a segment that is not copied: the kernel has a place to write even if the caller does not want the result.
+    enum IfNull { kSkip, kReserve };
+    template <class T>
+    struct Arg { int i; };
+    template <class T>
+    Arg<const T> in(const T *host, size_t bytes, IfNull n = kSkip) { return {add(const_cast<T *>(host), bytes, kIn, n)}; }
+    template <class T>
+    Arg<T> out(T *host, size_t bytes, IfNull n = kSkip) { return {add(host, bytes, kOut, n)}; }
+    template <class T>
+    Arg<T> inout(T *host, size_t bytes, IfNull n = kSkip) { return {add(host, bytes, kIn | kOut, n)}; }
+
+    // size the buffer, enqueue the host-to-device copies; ptr() is valid from here on
+    int commit() {
+        if (dev_) return MPC_OK;
+        if (int rc = grow(h_->stage, off_, stream_, nullptr)) return rc;
+        for (int i = 0; i < n_; ++i)
+            if (seg_[i].staged && (seg_[i].dir & kIn) && seg_[i].host)
+                HIP_TRY(hipMemcpyAsync(device(seg_[i]), seg_[i].host, seg_[i].bytes, hipMemcpyHostToDevice, stream_));
+        return MPC_OK;
+    }
+    // the device view of an argument: its segment, or the caller's own pointer (device pointers, null)
+    template <class T>
+    T *ptr(Arg<T> a) const {
+        const Seg &s = seg_[a.i];
+        return static_cast<T *>(s.staged ? device(s) : s.host);
+    }
+    // the one synchronisation rule: host pointers always, device pointers unless MPC_FLAG_NO_SYNC
+    int sync(uint32_t flags) {
+        if (!dev_ || !(flags & MPC_FLAG_NO_SYNC)) HIP_TRY(hipStreamSynchronize(stream_));
+        return MPC_OK;
+    }
+    // enqueue the device-to-host copies, then sync()
+    int finish(uint32_t flags) {
+        for (int i = 0; i < n_; ++i)
+            if (seg_[i].staged && (seg_[i].dir & kOut) && seg_[i].host)
+                HIP_TRY(hipMemcpyAsync(seg_[i].host, device(seg_[i]), seg_[i].bytes, hipMemcpyDeviceToHost, stream_));
+        return sync(flags);
+    }
+
+  private:
+    enum { kIn = 1, kOut = 2, kMaxSeg = 12 };
+    struct Seg {
+        void *host;
+        size_t off, bytes;
+        int dir;
+        bool staged;
+    };
+    int add(void *host, size_t bytes, int dir, IfNull n) {
+        assert(n_ < kMaxSeg);
+        const bool staged = !dev_ && (host || n == kReserve);
+        seg_[n_] = Seg{host, staged ? carve(off_, bytes) : 0, bytes, dir, staged};
+        return n_++;
+    }
+    void *device(const Seg &s) const { return static_cast<char *>(h_->stage.p) + s.off; }
+
+    mpc_handle *h_;
+    hipStream_t stream_;
+    bool dev_;
+    Seg seg_[kMaxSeg];
+    int n_ = 0;
+    size_t off_ = 0;
+};
+
+// The dynamic-LDS limit of a kernel is raised once per (kernel, device), to the largest size asked for so far: the
+// attribute call is not a stream operation and must stay out of a stream capture (hipGraph) of the launch, so only the
+// first use of a size has to happen outside one.  One cache per kernel; zero-initialised (static); concurrent callers at
+// worst both set the attribute.
+using LdsLimits = std::atomic<size_t>[kMaxDevices];
+int raise_lds_limit(const void *kernel, int device, size_t bytes, LdsLimits &cache) {
+    if (device < kMaxDevices && cache[device].load(std::memory_order_acquire) >= bytes) return MPC_OK;
+    HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    if (device < kMaxDevices) {
+        size_t cur = cache[device].load(std::memory_order_relaxed);
+        while (cur < bytes && !cache[device].compare_exchange_weak(cur, bytes, std::memory_order_release)) {}
+    }
+    return MPC_OK;
+}
+
 template <bool CC, int NC, int OCC, int RELAX>
 int launch_wave(const mpc_handle *h, const mpc::SolveParams &P, int B, int V, hipStream_t stream,
                 const double *d_state, const int32_t *d_ego, const double *d_vref, const double *d_weights,
@@ -815,38 +940,12 @@ int launch_wave(const mpc_handle *h, const mpc::SolveParams &P, int B, int V, hi
                 const int32_t *d_order) {
     auto kern = mpc_solve_wave_kernel<CC, NC, OCC, RELAX>;
     const size_t lds = (size_t)mpc::wave::lds_doubles(CC, P.N, P.V) * sizeof(double);
-    // raised once per (kernel, device): the attribute call is not a stream operation and must stay out of a stream
-    // capture (hipGraph) of the launch
-    static std::atomic<size_t> lds_set[kMaxDevices];      // zero-initialised; concurrent callers at worst both set it
-    if (h->device >= kMaxDevices || lds_set[h->device].load(std::memory_order_acquire) < lds) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds));
-        if (h->device < kMaxDevices) {
-            size_t cur = lds_set[h->device].load(std::memory_order_relaxed);
-            while (cur < lds && !lds_set[h->device].compare_exchange_weak(cur, lds, std::memory_order_release)) {}
-        }
-    }
+    static LdsLimits lds_set;
+    if (int rc = raise_lds_limit(reinterpret_cast<const void *>(kern), h->device, lds, lds_set)) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kBlock), lds, stream, P, B, h->d_ref, h->M, d_state, d_ego,
                        d_vref, d_weights, d_coll, d_others, V, d_nveh, h->cfg.w_collision, d_uinit, u_shift, d_uvalid,
                        d_u0, d_U, d_X, d_status, d_iters, d_order);
     HIP_TRY(hipGetLastError());
-    return MPC_OK;
-}
-
-// the buffer of the launch order is allocated ONCE, at mpc_create, for the largest batch that is ever ordered (64 waves per SIMD:
-// 512 KB on an MI355X) and never moves: a captured hipGraph keeps its address in two kernels (ADVICE r4 - until round 4 it was
-// grown on demand, and a later, larger call on the same handle would have left such a graph replaying against freed memory)
-int ensure_order(mpc_handle *, int, hipStream_t) { return MPC_OK; }
-
-// staging buffer for host-pointer calls: grown on demand, reused across calls
-int ensure_stage(mpc_handle *h, size_t bytes) {
-    if (h->stage_bytes >= bytes) return MPC_OK;
-    HIP_TRY(hipDeviceSynchronize());     // host-pointer calls are synchronous, but be safe against work of other streams
-    if (h->d_stage) HIP_TRY(hipFree(h->d_stage));
-    h->d_stage = nullptr;
-    h->stage_bytes = 0;
-    HIP_TRY(hipMalloc(&h->d_stage, bytes));
-    h->stage_bytes = bytes;
     return MPC_OK;
 }
 
@@ -978,9 +1077,15 @@ int mpc_create(const mpc_config *cfg, mpc_handle **out) {
         }
     }
     {
-        const int cap = 64 * 4 * h->num_cu;       // dispatch_solve orders batches of up to 64 waves per SIMD (65 536 instances: 512 KB)
-        if (hipMalloc(reinterpret_cast<void **>(&h->d_order), (size_t)cap * 2 * sizeof(int32_t)) == hipSuccess) h->order_cap = cap;
-        else h->d_order = nullptr;                 // (unordered launches are correct, only slower)
+        // the buffer of the launch order is allocated ONCE, here, for the largest batch that is ever ordered (64 waves per SIMD:
+        // 512 KB on an MI355X) and never moves: a captured hipGraph keeps its address in two kernels (ADVICE r4 - until round 4
+        // it was grown on demand, and a later, larger call on the same handle would have left such a graph replaying against
+        // freed memory)
+        const int cap = 64 * 4 * h->num_cu;       // dispatch_solve orders batches of up to 64 waves per SIMD (65 536 instances)
+        if (hipMalloc(reinterpret_cast<void **>(&h->d_order.p), (size_t)cap * 2 * sizeof(int32_t)) == hipSuccess)
+            h->order_cap = cap;
+        else
+            h->d_order.p = nullptr;               // (unordered launches are correct, only slower)
     }
     *out = h;
     g_last_error.clear();
@@ -990,17 +1095,7 @@ int mpc_create(const mpc_config *cfg, mpc_handle **out) {
 void mpc_destroy(mpc_handle *h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
-    if (h->d_ref) (void)hipFree(h->d_ref);
-    if (h->d_stage) (void)hipFree(h->d_stage);
-    if (h->d_env) (void)hipFree(h->d_env);
-    if (h->d_warm) (void)hipFree(h->d_warm);
-    if (h->d_warm_valid) (void)hipFree(h->d_warm_valid);
-    if (h->d_ltv_u) (void)hipFree(h->d_ltv_u);
-    if (h->d_ids) (void)hipFree(h->d_ids);
-    if (h->d_pre) (void)hipFree(h->d_pre);
-    if (h->d_diag) (void)hipFree(h->d_diag);
-    if (h->d_order) (void)hipFree(h->d_order);
-    delete h;
+    delete h;      // every DevPtr / GrowBuf member frees its memory
 }
 
 int mpc_set_reference(mpc_handle *h, const double *ref, int32_t M) {
@@ -1017,8 +1112,8 @@ int mpc_set_reference(mpc_handle *h, const double *ref, int32_t M) {
         r6[M * mpc::REF_COLS + i] = ref[i * 4 + 2];
     }
     if (h->d_ref) HIP_TRY(hipFree(h->d_ref));
-    h->d_ref = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->d_ref), buf.size()));
+    h->d_ref.p = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->d_ref.p), buf.size()));
     HIP_TRY(hipMemcpy(h->d_ref, r6, buf.size(), hipMemcpyHostToDevice));
     h->M = M;
     return MPC_OK;
@@ -1026,9 +1121,9 @@ int mpc_set_reference(mpc_handle *h, const double *ref, int32_t M) {
 
 int64_t mpc_workspace_bytes(const mpc_handle *h, int32_t B, int32_t V) {
     if (!h || B < 0 || V < 0 || V > MPC_MAX_OTHERS) return -1;
-    // every build of the solve kernel has the same LDS layout since round 5 (mpc_wave.hpp: lds_doubles)
+    // every build of the solve kernel has the same LDS layout since round 5 (mpc_wave.hpp: lds_doubles); the workspace is
+    // per instance, so B is checked and otherwise unused by design
     const int N = h->cfg.horizon;
-    (void)B;
     return (int64_t)mpc::wave::lds_doubles(V > 0, N, V) * (int64_t)sizeof(double);
 }
 
@@ -1049,72 +1144,29 @@ int mpc_solve_batch(mpc_handle *h, int32_t B, const double *state, const int32_t
     const int N = h->cfg.horizon;
     const size_t N1 = (size_t)N + 1;
 
-    // ---- device views of the arguments
-    const double *d_state = state, *d_vref = vref, *d_weights = weights, *d_others = others;
-    const int32_t *d_ego = ego_index;
-    const uint8_t *d_coll = is_collide;
-    double *d_u0 = u0, *d_U = U, *d_X = X;
-    int32_t *d_status = status, *d_iters = iters;
-    const bool dev = (flags & MPC_FLAG_DEVICE_PTRS) != 0;
-    size_t off_u0 = 0, off_U = 0, off_X = 0, off_st = 0, off_it = 0;
-    if (!dev) {
-        // pack everything into one staging allocation (8-byte aligned segments)
-        size_t off = 0;
-        auto seg = [&](size_t bytes) { return carve(off, bytes); };
-        const size_t o_state = seg((size_t)B * 4 * 8), o_ego = seg((size_t)B * 4), o_w = seg((size_t)B * 3 * 8);
-        const size_t o_c = seg((size_t)B), o_vref = vref ? seg((size_t)B * N1 * 8) : 0;
-        const size_t o_oth = (cc && V > 0) ? seg((size_t)B * V * 4 * 8) : 0;
-        off_u0 = seg((size_t)B * 2 * 8);
-        off_U = U ? seg((size_t)B * N * 2 * 8) : 0;
-        off_X = X ? seg((size_t)B * N1 * 4 * 8) : 0;
-        off_st = seg((size_t)B * 4);
-        off_it = seg((size_t)B * 4);
-        if (int rc = ensure_stage(h, off)) return rc;
-        char *sb = static_cast<char *>(h->d_stage);
-        HIP_TRY(hipMemcpyAsync(sb + o_state, state, (size_t)B * 4 * 8, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(sb + o_ego, ego_index, (size_t)B * 4, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(sb + o_w, weights, (size_t)B * 3 * 8, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(sb + o_c, is_collide, (size_t)B, hipMemcpyHostToDevice, stream));
-        d_state = reinterpret_cast<double *>(sb + o_state);
-        d_ego = reinterpret_cast<int32_t *>(sb + o_ego);
-        d_weights = reinterpret_cast<double *>(sb + o_w);
-        d_coll = reinterpret_cast<uint8_t *>(sb + o_c);
-        if (vref) {
-            HIP_TRY(hipMemcpyAsync(sb + o_vref, vref, (size_t)B * N1 * 8, hipMemcpyHostToDevice, stream));
-            d_vref = reinterpret_cast<double *>(sb + o_vref);
-        }
-        if (cc && V > 0) {
-            HIP_TRY(hipMemcpyAsync(sb + o_oth, others, (size_t)B * V * 4 * 8, hipMemcpyHostToDevice, stream));
-            d_others = reinterpret_cast<double *>(sb + o_oth);
-        }
-        d_u0 = reinterpret_cast<double *>(sb + off_u0);
-        d_U = U ? reinterpret_cast<double *>(sb + off_U) : nullptr;
-        d_X = X ? reinterpret_cast<double *>(sb + off_X) : nullptr;
-        d_status = reinterpret_cast<int32_t *>(sb + off_st);
-        d_iters = reinterpret_cast<int32_t *>(sb + off_it);
-    }
-
-    const bool warm = (flags & MPC_FLAG_WARM_START) != 0;
+    const bool dev = (flags & MPC_FLAG_DEVICE_PTRS) != 0, warm = (flags & MPC_FLAG_WARM_START) != 0;
     if (warm && !U) return fail(MPC_ERR_INVALID_ARG, "mpc_solve_batch: MPC_FLAG_WARM_START needs U (initial controls in, solution out)");
-    if (warm && !dev)
-        HIP_TRY(hipMemcpyAsync(d_U, U, (size_t)B * N * 2 * 8, hipMemcpyHostToDevice, stream));
-    if (int rc = ensure_order(h, B, stream)) return rc;
-    if (int rc = dispatch_solve(h, B, cc, V, flags, stream, d_state, d_ego, d_vref, d_weights, d_coll, d_others, nullptr,
-                                warm ? d_U : nullptr, 0, nullptr, d_u0, d_U, d_X, d_status, d_iters))
-        return rc;
 
-    if (!dev) {
-        char *sb = static_cast<char *>(h->d_stage);
-        HIP_TRY(hipMemcpyAsync(u0, sb + off_u0, (size_t)B * 2 * 8, hipMemcpyDeviceToHost, stream));
-        if (U) HIP_TRY(hipMemcpyAsync(U, sb + off_U, (size_t)B * N * 2 * 8, hipMemcpyDeviceToHost, stream));
-        if (X) HIP_TRY(hipMemcpyAsync(X, sb + off_X, (size_t)B * N1 * 4 * 8, hipMemcpyDeviceToHost, stream));
-        if (status) HIP_TRY(hipMemcpyAsync(status, sb + off_st, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
-        if (iters) HIP_TRY(hipMemcpyAsync(iters, sb + off_it, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-    } else if (!(flags & MPC_FLAG_NO_SYNC)) {
-        HIP_TRY(hipStreamSynchronize(stream));
-    }
-    return MPC_OK;
+    Staging st(h, stream, dev);
+    const auto s_state = st.in(state, (size_t)B * 4 * 8);
+    const auto s_ego = st.in(ego_index, (size_t)B * 4);
+    const auto s_w = st.in(weights, (size_t)B * 3 * 8);
+    const auto s_c = st.in(is_collide, (size_t)B);
+    const auto s_vref = st.in(vref, (size_t)B * N1 * 8);                                     // optional
+    const auto s_oth = st.in(cc && V > 0 ? others : nullptr, (size_t)B * V * 4 * 8);
+    const auto s_u0 = st.out(u0, (size_t)B * 2 * 8);
+    const auto s_U = warm ? st.inout(U, (size_t)B * N * 2 * 8) : st.out(U, (size_t)B * N * 2 * 8);   // optional unless warm
+    const auto s_X = st.out(X, (size_t)B * N1 * 4 * 8);                                      // optional
+    const auto s_st = st.out(status, (size_t)B * 4, Staging::kReserve);
+    const auto s_it = st.out(iters, (size_t)B * 4, Staging::kReserve);
+    if (int rc = st.commit()) return rc;
+
+    double *d_U = st.ptr(s_U);
+    if (int rc = dispatch_solve(h, B, cc, V, flags, stream, st.ptr(s_state), st.ptr(s_ego), st.ptr(s_vref), st.ptr(s_w),
+                                st.ptr(s_c), st.ptr(s_oth), nullptr, warm ? d_U : nullptr, 0, nullptr, st.ptr(s_u0), d_U,
+                                st.ptr(s_X), st.ptr(s_st), st.ptr(s_it)))
+        return rc;
+    return st.finish(flags);
 }
 
 // grow the per-environment state array to at least B records (new records start as fresh episodes).  The old buffers
@@ -1122,17 +1174,16 @@ int mpc_solve_batch(mpc_handle *h, int32_t B, const double *state, const int32_t
 // graph has the addresses baked in - size the handle first with mpc_reserve_envs), and only after the device is idle.
 static int ensure_env(mpc_handle *h, int B, hipStream_t stream) {
     if (B <= h->env_cap) return MPC_OK;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (stream && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-        return fail(MPC_ERR_INVALID_ARG, "per-environment buffers must grow, which is not possible inside a stream capture: "
-                                         "call mpc_reserve_envs before capturing");
+    if (int rc = refuse_in_capture(stream, "per-environment buffers must grow, which is not possible inside a stream capture: "
+                                           "call mpc_reserve_envs before capturing"))
+        return rc;
     int cap = h->env_cap > 0 ? h->env_cap : 256;
     while (cap < B) cap *= 2;
     const size_t wrow = (size_t)h->cfg.horizon * 2 * sizeof(double);
     constexpr int NB = 4;
     void *nb[NB] = {nullptr, nullptr, nullptr, nullptr};
     const size_t bytes[NB] = {(size_t)cap * sizeof(mpc::pre::EnvState), (size_t)cap * wrow, (size_t)cap, (size_t)cap * wrow};
-    void *old[NB] = {h->d_env, h->d_warm, h->d_warm_valid, h->d_ltv_u};
+    void *old[NB] = {h->d_env.p, h->d_warm.p, h->d_warm_valid.p, h->d_ltv_u.p};
     const size_t old_bytes[NB] = {(size_t)h->env_cap * sizeof(mpc::pre::EnvState), (size_t)h->env_cap * wrow,
                                   (size_t)h->env_cap, (size_t)h->env_cap * wrow};
     hipError_t e = hipDeviceSynchronize();       // in-flight MPC_FLAG_NO_SYNC work on any stream still uses the old buffers
@@ -1148,10 +1199,10 @@ static int ensure_env(mpc_handle *h, int B, hipStream_t stream) {
     }
     for (int i = 0; i < NB; ++i)
         if (old[i]) (void)hipFree(old[i]);
-    h->d_env = static_cast<mpc::pre::EnvState *>(nb[0]);
-    h->d_warm = static_cast<double *>(nb[1]);
-    h->d_warm_valid = static_cast<uint8_t *>(nb[2]);
-    h->d_ltv_u = static_cast<double *>(nb[3]);
+    h->d_env.p = static_cast<mpc::pre::EnvState *>(nb[0]);
+    h->d_warm.p = static_cast<double *>(nb[1]);
+    h->d_warm_valid.p = static_cast<uint8_t *>(nb[2]);
+    h->d_ltv_u.p = static_cast<double *>(nb[3]);
     h->env_cap = cap;
     return MPC_OK;
 }
@@ -1159,7 +1210,6 @@ static int ensure_env(mpc_handle *h, int B, hipStream_t stream) {
 int mpc_reserve_envs(mpc_handle *h, int32_t B) {
     if (!h || B < 0) return fail(MPC_ERR_INVALID_ARG, "mpc_reserve_envs: bad argument");
     HIP_TRY(hipSetDevice(h->device));
-    if (int rc = ensure_order(h, B, nullptr)) return rc;
     return ensure_env(h, B, nullptr);
 }
 
@@ -1191,21 +1241,10 @@ int mpc_predict_batch(mpc_handle *h, int32_t B, const float *obs, int32_t vehicl
         const size_t o_state = seg((size_t)B * 4 * 8), o_vref = seg((size_t)B * N1 * 8);
         const size_t o_oth = seg((size_t)B * (V > 0 ? V : 1) * 4 * 8), o_ego = seg((size_t)B * 4);
         const size_t o_nv = seg((size_t)B * 4), o_c = seg((size_t)B);
-        if (h->pre_bytes < off) {
-            // the old buffer may still be in use by enqueued (MPC_FLAG_NO_SYNC) work, and a captured graph holds its
-            // address: never inside a capture, and only once the device is idle
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (stream && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-                return fail(MPC_ERR_INVALID_ARG, "mpc_predict_batch: the problem-data buffer must grow, which is not possible "
-                                                 "inside a stream capture: run one step of this size before capturing");
-            HIP_TRY(hipDeviceSynchronize());
-            if (h->d_pre) HIP_TRY(hipFree(h->d_pre));
-            h->d_pre = nullptr;
-            h->pre_bytes = 0;
-            HIP_TRY(hipMalloc(&h->d_pre, off));
-            h->pre_bytes = off;
-        }
-        char *pb = static_cast<char *>(h->d_pre);
+        if (int rc = grow(h->pre, off, stream, "mpc_predict_batch: the problem-data buffer must grow, which is not possible "
+                                               "inside a stream capture: run one step of this size before capturing"))
+            return rc;
+        char *pb = static_cast<char *>(h->pre.p);
         h->p_state = reinterpret_cast<double *>(pb + o_state);
         h->p_vref = reinterpret_cast<double *>(pb + o_vref);
         h->p_others = reinterpret_cast<double *>(pb + o_oth);
@@ -1216,86 +1255,46 @@ int mpc_predict_batch(mpc_handle *h, int32_t B, const float *obs, int32_t vehicl
         h->pre_V = V;
     }
 
-    const float *d_obs = obs;
-    const double *d_weights = weights, *d_rs = ref_speed;
-    double *d_act = act;
-    int32_t *d_status = status, *d_iters = iters;
-    size_t off_act = 0, off_st = 0, off_it = 0;
-    if (!dev) {
-        size_t off = 0;
-        auto seg = [&](size_t bytes) { return carve(off, bytes); };
-        const size_t o_obs = seg((size_t)B * rows * mpc::pre::kObsCols * 4), o_w = seg((size_t)B * 3 * 8);
-        const size_t o_rs = ref_speed ? seg((size_t)B * 8) : 0;
-        off_act = seg((size_t)B * 2 * 8);
-        off_st = seg((size_t)B * 4);
-        off_it = seg((size_t)B * 4);
-        if (int rc = ensure_stage(h, off)) return rc;
-        char *sb = static_cast<char *>(h->d_stage);
-        HIP_TRY(hipMemcpyAsync(sb + o_obs, obs, (size_t)B * rows * mpc::pre::kObsCols * 4, hipMemcpyHostToDevice,
-                               stream));
-        if (weights) HIP_TRY(hipMemcpyAsync(sb + o_w, weights, (size_t)B * 3 * 8, hipMemcpyHostToDevice, stream));
-        d_obs = reinterpret_cast<float *>(sb + o_obs);
-        d_weights = reinterpret_cast<double *>(sb + o_w);
-        if (ref_speed) {
-            HIP_TRY(hipMemcpyAsync(sb + o_rs, ref_speed, (size_t)B * 8, hipMemcpyHostToDevice, stream));
-            d_rs = reinterpret_cast<double *>(sb + o_rs);
-        }
-        d_act = reinterpret_cast<double *>(sb + off_act);
-        d_status = reinterpret_cast<int32_t *>(sb + off_st);
-        d_iters = reinterpret_cast<int32_t *>(sb + off_it);
-    }
+    Staging st(h, stream, dev);
+    const auto s_obs = st.in(obs, (size_t)B * rows * mpc::pre::kObsCols * 4);
+    const auto s_w = st.in(weights, (size_t)B * 3 * 8, Staging::kReserve);        // null with MPC_FLAG_DETECT_ONLY, like act
+    const auto s_rs = st.in(ref_speed, (size_t)B * 8);                            // optional
+    const auto s_act = st.out(act, (size_t)B * 2 * 8, Staging::kReserve);
+    const auto s_st = st.out(status, (size_t)B * 4, Staging::kReserve);
+    const auto s_it = st.out(iters, (size_t)B * 4, Staging::kReserve);
+    if (int rc = st.commit()) return rc;
 
     if (h->diag) {
         size_t off = 0;
         const size_t P = mpc::pre::kPredHorizon + 1, Vs = (size_t)(V > 0 ? V : 1);
         const size_t o_ego = carve(off, (size_t)B * P * 2 * 8), o_len = carve(off, (size_t)B * 4);
         const size_t o_ag = carve(off, (size_t)B * Vs * P * 2 * 4);
-        if (h->diag_bytes < off) {
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (stream && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-                return fail(MPC_ERR_INVALID_ARG, "mpc_predict_batch: diagnostics buffers cannot grow inside a stream capture");
-            HIP_TRY(hipDeviceSynchronize());
-            if (h->d_diag) HIP_TRY(hipFree(h->d_diag));
-            h->d_diag = nullptr;
-            h->diag_bytes = 0;
-            HIP_TRY(hipMalloc(&h->d_diag, off));
-            h->diag_bytes = off;
-        }
-        char *db = static_cast<char *>(h->d_diag);
+        if (int rc = grow(h->diag_buf, off, stream, "mpc_predict_batch: diagnostics buffers cannot grow inside a stream capture"))
+            return rc;
+        char *db = static_cast<char *>(h->diag_buf.p);
         h->g_ego = reinterpret_cast<double *>(db + o_ego);
         h->g_len = reinterpret_cast<int32_t *>(db + o_len);
         h->g_agents = reinterpret_cast<float *>(db + o_ag);
         h->diag_B = B;
         h->diag_V = (int)Vs;
-        HIP_TRY(hipMemsetAsync(h->d_diag, 0, off, stream));
+        HIP_TRY(hipMemsetAsync(h->diag_buf.p, 0, off, stream));
     }
     hipLaunchKernelGGL(mpc_preamble_kernel, dim3((unsigned)B), dim3(kBlock), 0, stream,
-                       (int)B, d_obs, rows, h->d_ref, h->M, N, h->cfg.dt, d_rs, h->d_env, h->p_state, h->p_ego,
-                       h->p_vref, h->p_coll, h->p_others, V > 0 ? V : 1, h->p_nveh, detected ? 0 : 1,
+                       (int)B, st.ptr(s_obs), rows, h->d_ref, h->M, N, h->cfg.dt, st.ptr(s_rs), h->d_env,
+                       h->p_state, h->p_ego, h->p_vref, h->p_coll, h->p_others, V > 0 ? V : 1, h->p_nveh, detected ? 0 : 1,
                        h->diag ? h->g_ego : nullptr, h->diag ? h->g_len : nullptr, h->diag ? h->g_agents : nullptr);
     HIP_TRY(hipGetLastError());
     const bool warm = (flags & MPC_FLAG_WARM_START) != 0;
     if (detect_only) {
-        // _check_collision on its own (agents/pure_mpc.py:552-676): the records are advanced, nothing is solved
-        if (!dev || !(flags & MPC_FLAG_NO_SYNC)) HIP_TRY(hipStreamSynchronize(stream));
-        return MPC_OK;
+        // _check_collision on its own (agents/pure_mpc.py:552-676): the records are advanced, nothing is solved and
+        // nothing is copied back
+        return st.sync(flags);
     }
-    if (int rc = ensure_order(h, B, stream)) return rc;
-    if (int rc = dispatch_solve(h, B, cc, V, flags, stream, h->p_state, h->p_ego, h->p_vref, d_weights, h->p_coll,
+    if (int rc = dispatch_solve(h, B, cc, V, flags, stream, h->p_state, h->p_ego, h->p_vref, st.ptr(s_w), h->p_coll,
                                 h->p_others, h->p_nveh, warm ? h->d_warm : nullptr, 1, warm ? h->d_warm_valid : nullptr,
-                                d_act, warm ? h->d_warm : nullptr, nullptr, d_status, d_iters))
+                                st.ptr(s_act), warm ? h->d_warm : nullptr, nullptr, st.ptr(s_st), st.ptr(s_it)))
         return rc;
-
-    if (!dev) {
-        char *sb = static_cast<char *>(h->d_stage);
-        HIP_TRY(hipMemcpyAsync(act, sb + off_act, (size_t)B * 2 * 8, hipMemcpyDeviceToHost, stream));
-        if (status) HIP_TRY(hipMemcpyAsync(status, sb + off_st, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
-        if (iters) HIP_TRY(hipMemcpyAsync(iters, sb + off_it, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-    } else if (!(flags & MPC_FLAG_NO_SYNC)) {
-        HIP_TRY(hipStreamSynchronize(stream));
-    }
-    return MPC_OK;
+    return st.finish(flags);
 }
 
 // ---- iterative-linear MPC (reference agents/pure_mpc_linear.py) ---------------------------------------------
@@ -1314,17 +1313,12 @@ static int launch_ltv(mpc_handle *h, int B, hipStream_t stream, const double *d_
     P.passes = h->cfg.ltv_passes;
     P.dt = h->cfg.dt;
     const size_t lds = (size_t)mpc::ltv::lds_doubles(P.N) * sizeof(double);
-    static std::atomic<size_t> lds_set[kMaxDevices];
-    if (h->device >= kMaxDevices || lds_set[h->device].load(std::memory_order_acquire) < lds) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(mpc_ltv_kernel<kLtvOcc, 0>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(mpc_ltv_kernel<kLtvOccLat, kLtvRelaxLat>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (h->device < kMaxDevices) {
-            size_t cur = lds_set[h->device].load(std::memory_order_relaxed);
-            while (cur < lds && !lds_set[h->device].compare_exchange_weak(cur, lds, std::memory_order_release)) {}
-        }
-    }
+    // both builds on first use, whichever is launched: a later capture may launch the other
+    static LdsLimits lds_set, lds_set_lat;
+    const void *thr = reinterpret_cast<const void *>(mpc_ltv_kernel<kLtvOcc, 0>);
+    const void *lat = reinterpret_cast<const void *>(mpc_ltv_kernel<kLtvOccLat, kLtvRelaxLat>);
+    if (int rc = raise_lds_limit(thr, h->device, lds, lds_set)) return rc;
+    if (int rc = raise_lds_limit(lat, h->device, lds, lds_set_lat)) return rc;
     // which build: by how deep the batch fills the SIMDs
     if (B <= kLtvLatDepth * 4 * h->num_cu)
         hipLaunchKernelGGL((mpc_ltv_kernel<kLtvOccLat, kLtvRelaxLat>), dim3((unsigned)B), dim3(kBlock), lds, stream, P, B,
@@ -1348,46 +1342,19 @@ int mpc_ltv_solve_batch(mpc_handle *h, int32_t B, const double *state, uint32_t 
     const int N = h->cfg.horizon;
     const size_t N1 = (size_t)N + 1;
     const bool dev = (flags & MPC_FLAG_DEVICE_PTRS) != 0;
-    const double *d_state = state;
-    double *d_u0 = u0, *d_U = U, *d_X = X;
-    int32_t *d_status = status, *d_iters = iters, *d_target = target_index;
-    size_t o_u0 = 0, o_U = 0, o_X = 0, o_st = 0, o_it = 0, o_tg = 0;
-    if (!dev) {
-        size_t off = 0;
-        auto seg = [&](size_t bytes) { return carve(off, bytes); };
-        const size_t o_state = seg((size_t)B * 4 * 8);
-        o_u0 = seg((size_t)B * 2 * 8);
-        o_U = seg((size_t)B * N * 2 * 8);
-        o_X = X ? seg((size_t)B * N1 * 4 * 8) : 0;
-        o_st = seg((size_t)B * 4);
-        o_it = seg((size_t)B * 4);
-        o_tg = seg((size_t)B * 4);
-        if (int rc = ensure_stage(h, off)) return rc;
-        char *sb = static_cast<char *>(h->d_stage);
-        HIP_TRY(hipMemcpyAsync(sb + o_state, state, (size_t)B * 4 * 8, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(sb + o_U, U, (size_t)B * N * 2 * 8, hipMemcpyHostToDevice, stream));
-        d_state = reinterpret_cast<double *>(sb + o_state);
-        d_u0 = reinterpret_cast<double *>(sb + o_u0);
-        d_U = reinterpret_cast<double *>(sb + o_U);
-        d_X = X ? reinterpret_cast<double *>(sb + o_X) : nullptr;
-        d_status = reinterpret_cast<int32_t *>(sb + o_st);
-        d_iters = reinterpret_cast<int32_t *>(sb + o_it);
-        d_target = reinterpret_cast<int32_t *>(sb + o_tg);
-    }
-    if (int rc = launch_ltv(h, B, stream, d_state, nullptr, 0, d_U, d_u0, d_X, d_status, d_iters, d_target)) return rc;
-    if (!dev) {
-        char *sb = static_cast<char *>(h->d_stage);
-        HIP_TRY(hipMemcpyAsync(u0, sb + o_u0, (size_t)B * 2 * 8, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipMemcpyAsync(U, sb + o_U, (size_t)B * N * 2 * 8, hipMemcpyDeviceToHost, stream));
-        if (X) HIP_TRY(hipMemcpyAsync(X, sb + o_X, (size_t)B * N1 * 4 * 8, hipMemcpyDeviceToHost, stream));
-        if (status) HIP_TRY(hipMemcpyAsync(status, sb + o_st, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
-        if (iters) HIP_TRY(hipMemcpyAsync(iters, sb + o_it, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
-        if (target_index) HIP_TRY(hipMemcpyAsync(target_index, sb + o_tg, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-    } else if (!(flags & MPC_FLAG_NO_SYNC)) {
-        HIP_TRY(hipStreamSynchronize(stream));
-    }
-    return MPC_OK;
+    Staging st(h, stream, dev);
+    const auto s_state = st.in(state, (size_t)B * 4 * 8);
+    const auto s_u0 = st.out(u0, (size_t)B * 2 * 8);
+    const auto s_U = st.inout(U, (size_t)B * N * 2 * 8);            // stored profile in, new profile out
+    const auto s_X = st.out(X, (size_t)B * N1 * 4 * 8);             // optional
+    const auto s_st = st.out(status, (size_t)B * 4, Staging::kReserve);
+    const auto s_it = st.out(iters, (size_t)B * 4, Staging::kReserve);
+    const auto s_tg = st.out(target_index, (size_t)B * 4, Staging::kReserve);
+    if (int rc = st.commit()) return rc;
+    if (int rc = launch_ltv(h, B, stream, st.ptr(s_state), nullptr, 0, st.ptr(s_U), st.ptr(s_u0), st.ptr(s_X), st.ptr(s_st),
+                            st.ptr(s_it), st.ptr(s_tg)))
+        return rc;
+    return st.finish(flags);
 }
 
 int mpc_ltv_predict_batch(mpc_handle *h, int32_t B, const float *obs, int32_t vehicles_count, uint32_t flags, double *act,
@@ -1404,37 +1371,16 @@ int mpc_ltv_predict_batch(mpc_handle *h, int32_t B, const float *obs, int32_t ve
     const int rows = vehicles_count;
     const bool dev = (flags & MPC_FLAG_DEVICE_PTRS) != 0;
     if (int rc = ensure_env(h, B, stream)) return rc;
-    const float *d_obs = obs;
-    double *d_act = act;
-    int32_t *d_status = status, *d_iters = iters;
-    size_t o_act = 0, o_st = 0, o_it = 0;
-    if (!dev) {
-        size_t off = 0;
-        auto seg = [&](size_t bytes) { return carve(off, bytes); };
-        const size_t o_obs = seg((size_t)B * rows * mpc::pre::kObsCols * 4);
-        o_act = seg((size_t)B * 2 * 8);
-        o_st = seg((size_t)B * 4);
-        o_it = seg((size_t)B * 4);
-        if (int rc = ensure_stage(h, off)) return rc;
-        char *sb = static_cast<char *>(h->d_stage);
-        HIP_TRY(hipMemcpyAsync(sb + o_obs, obs, (size_t)B * rows * mpc::pre::kObsCols * 4, hipMemcpyHostToDevice, stream));
-        d_obs = reinterpret_cast<float *>(sb + o_obs);
-        d_act = reinterpret_cast<double *>(sb + o_act);
-        d_status = reinterpret_cast<int32_t *>(sb + o_st);
-        d_iters = reinterpret_cast<int32_t *>(sb + o_it);
-    }
-    if (int rc = launch_ltv(h, B, stream, nullptr, d_obs, rows, h->d_ltv_u, d_act, nullptr, d_status, d_iters, nullptr))
+    Staging st(h, stream, dev);
+    const auto s_obs = st.in(obs, (size_t)B * rows * mpc::pre::kObsCols * 4);
+    const auto s_act = st.out(act, (size_t)B * 2 * 8);
+    const auto s_st = st.out(status, (size_t)B * 4, Staging::kReserve);
+    const auto s_it = st.out(iters, (size_t)B * 4, Staging::kReserve);
+    if (int rc = st.commit()) return rc;
+    if (int rc = launch_ltv(h, B, stream, nullptr, st.ptr(s_obs), rows, h->d_ltv_u, st.ptr(s_act), nullptr, st.ptr(s_st),
+                            st.ptr(s_it), nullptr))
         return rc;
-    if (!dev) {
-        char *sb = static_cast<char *>(h->d_stage);
-        HIP_TRY(hipMemcpyAsync(act, sb + o_act, (size_t)B * 2 * 8, hipMemcpyDeviceToHost, stream));
-        if (status) HIP_TRY(hipMemcpyAsync(status, sb + o_st, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
-        if (iters) HIP_TRY(hipMemcpyAsync(iters, sb + o_it, (size_t)B * 4, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-    } else if (!(flags & MPC_FLAG_NO_SYNC)) {
-        HIP_TRY(hipStreamSynchronize(stream));
-    }
-    return MPC_OK;
+    return st.finish(flags);
 }
 
 int mpc_reset_env_state(mpc_handle *h, const int32_t *env_ids, int32_t n, void *stream_) {
@@ -1450,17 +1396,10 @@ int mpc_reset_env_state(mpc_handle *h, const int32_t *env_ids, int32_t n, void *
         return MPC_OK;
     }
     if (n == 0) return MPC_OK;
-    if (n > h->ids_cap) {                       // handle-owned, grow-only (no allocation per call)
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (h->d_ids) HIP_TRY(hipFree(h->d_ids));
-        h->d_ids = nullptr;
-        h->ids_cap = 0;
-        int cap = 256;
-        while (cap < n) cap *= 2;
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&h->d_ids), (size_t)cap * 4));
-        h->ids_cap = cap;
-    }
-    int32_t *d_ids = h->d_ids;
+    size_t cap = 256;                           // handle-owned, grow-only (no allocation per call)
+    while (cap < (size_t)n) cap *= 2;
+    if (int rc = grow(h->ids, cap * 4, stream, nullptr)) return rc;      // (this call is synchronous: never captured)
+    int32_t *d_ids = static_cast<int32_t *>(h->ids.p);
     hipError_t e = hipMemcpyAsync(d_ids, env_ids, (size_t)n * 4, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(mpc_env_reset_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (int)n, d_ids,
@@ -1477,27 +1416,16 @@ int mpc_reset_env_mask(mpc_handle *h, int32_t B, const uint8_t *done, uint32_t f
     if (!h->d_env || B == 0) return MPC_OK;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const uint8_t *d_done = done;
-    uint8_t *tmp = nullptr;
-    if (!(flags & MPC_FLAG_DEVICE_PTRS)) {
-        HIP_TRY(hipMalloc(reinterpret_cast<void **>(&tmp), (size_t)B));
-        hipError_t e = hipMemcpyAsync(tmp, done, (size_t)B, hipMemcpyHostToDevice, stream);
-        if (e != hipSuccess) {
-            (void)hipFree(tmp);
-            return fail(MPC_ERR_HIP, std::string("mpc_reset_env_mask: ") + hipGetErrorString(e));
-        }
-        d_done = tmp;
-    }
+    Staging st(h, stream, (flags & MPC_FLAG_DEVICE_PTRS) != 0);
+    const auto s_done = st.in(done, (size_t)B);
+    if (int rc = st.commit()) return rc;
     const int n = B < h->env_cap ? B : h->env_cap;
     hipLaunchKernelGGL(mpc_env_reset_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n,
-                       (const int32_t *)nullptr, d_done, h->d_env, h->d_warm_valid, h->env_cap,
+                       (const int32_t *)nullptr, st.ptr(s_done), h->d_env, h->d_warm_valid, h->env_cap,
                        (flags & MPC_FLAG_WARM_START) ? 1 : 0, (flags & MPC_FLAG_WARM_START) ? nullptr : h->d_ltv_u,
                        h->cfg.horizon * 2);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && (tmp || !(flags & MPC_FLAG_NO_SYNC))) e = hipStreamSynchronize(stream);
-    if (tmp) (void)hipFree(tmp);
-    if (e != hipSuccess) return fail(MPC_ERR_HIP, std::string("mpc_reset_env_mask: ") + hipGetErrorString(e));
-    return MPC_OK;
+    HIP_TRY(hipGetLastError());
+    return st.finish(flags);
 }
 
 int mpc_get_env_state(mpc_handle *h, int32_t B, int32_t *is_collide, int32_t *ego_index, int32_t *collision_memory,
@@ -1752,39 +1680,26 @@ int mpc_eval_nlp(mpc_handle *h, int32_t B, const int32_t *ego_index, const doubl
     HIP_TRY(hipSetDevice(h->device));
     const int N = h->cfg.horizon;
     const size_t N1 = (size_t)N + 1;
-    size_t off = 0;
-    auto seg = [&](size_t bytes) { return carve(off, bytes); };
-    const size_t o_ego = seg((size_t)B * 4), o_w = seg((size_t)B * 3 * 8), o_c = seg((size_t)B);
-    const size_t o_vref = vref ? seg((size_t)B * N1 * 8) : 0, o_oth = (cc && V > 0) ? seg((size_t)B * V * 4 * 8) : 0;
-    const size_t o_X = seg((size_t)B * N1 * 4 * 8), o_U = seg((size_t)B * N * 2 * 8), o_f = seg((size_t)B * 8);
-    const size_t o_xn = seg((size_t)B * N * 4 * 8);
-    if (int rc = ensure_stage(h, off)) return rc;
-    char *sb = static_cast<char *>(h->d_stage);
     hipStream_t stream = nullptr;
-    HIP_TRY(hipMemcpyAsync(sb + o_ego, ego_index, (size_t)B * 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(sb + o_w, weights, (size_t)B * 3 * 8, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(sb + o_c, is_collide, (size_t)B, hipMemcpyHostToDevice, stream));
-    if (vref) HIP_TRY(hipMemcpyAsync(sb + o_vref, vref, (size_t)B * N1 * 8, hipMemcpyHostToDevice, stream));
-    if (cc && V > 0) HIP_TRY(hipMemcpyAsync(sb + o_oth, others, (size_t)B * V * 4 * 8, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(sb + o_X, X, (size_t)B * N1 * 4 * 8, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(sb + o_U, U, (size_t)B * N * 2 * 8, hipMemcpyHostToDevice, stream));
+    Staging st(h, stream, false);                  // host pointers only, on the null stream
+    const auto s_ego = st.in(ego_index, (size_t)B * 4);
+    const auto s_w = st.in(weights, (size_t)B * 3 * 8);
+    const auto s_c = st.in(is_collide, (size_t)B);
+    const auto s_vref = st.in(vref, (size_t)B * N1 * 8);                                     // optional
+    const auto s_oth = st.in(cc && V > 0 ? others : nullptr, (size_t)B * V * 4 * 8);
+    const auto s_X = st.in(X, (size_t)B * N1 * 4 * 8);
+    const auto s_U = st.in(U, (size_t)B * N * 2 * 8);
+    const auto s_f = st.out(f, (size_t)B * 8);
+    const auto s_xn = st.out(x_next, (size_t)B * N * 4 * 8);
+    if (int rc = st.commit()) return rc;
     mpc::SolveParams P = solve_params(h, cc ? V : 0);
     const size_t lds = (size_t)mpc::wave::lds_doubles(cc, N, P.V) * sizeof(double);
-    auto D = [&](size_t o) { return reinterpret_cast<double *>(sb + o); };
-    if (cc)
-        hipLaunchKernelGGL(mpc_eval_kernel<true>, dim3((unsigned)B), dim3(kBlock), lds, stream, P, (int)B, h->d_ref, h->M,
-                           reinterpret_cast<int32_t *>(sb + o_ego), vref ? D(o_vref) : nullptr, D(o_w),
-                           reinterpret_cast<uint8_t *>(sb + o_c), V > 0 ? D(o_oth) : nullptr, (int)V, h->cfg.w_collision, D(o_X),
-                           D(o_U), D(o_f), D(o_xn));
-    else
-        hipLaunchKernelGGL(mpc_eval_kernel<false>, dim3((unsigned)B), dim3(kBlock), lds, stream, P, (int)B, h->d_ref, h->M,
-                           reinterpret_cast<int32_t *>(sb + o_ego), vref ? D(o_vref) : nullptr, D(o_w),
-                           reinterpret_cast<uint8_t *>(sb + o_c), nullptr, 0, h->cfg.w_collision, D(o_X), D(o_U), D(o_f), D(o_xn));
+    auto kern = cc ? mpc_eval_kernel<true> : mpc_eval_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kBlock), lds, stream, P, (int)B, h->d_ref.p, h->M, st.ptr(s_ego),
+                       st.ptr(s_vref), st.ptr(s_w), st.ptr(s_c), st.ptr(s_oth), cc ? (int)V : 0, h->cfg.w_collision,
+                       st.ptr(s_X), st.ptr(s_U), st.ptr(s_f), st.ptr(s_xn));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(f, sb + o_f, (size_t)B * 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipMemcpyAsync(x_next, sb + o_xn, (size_t)B * N * 4 * 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return MPC_OK;
+    return st.finish(0);
 }
 
 int mpc_set_diagnostics(mpc_handle *h, int32_t on) {
@@ -1797,7 +1712,7 @@ int mpc_set_diagnostics(mpc_handle *h, int32_t on) {
 int mpc_get_last_paths(mpc_handle *h, int32_t B, double *ego_path, int32_t *ego_len, float *agent_paths) {
     if (!h || B < 0) return fail(MPC_ERR_INVALID_ARG, "mpc_get_last_paths: bad argument");
     if (B == 0) return MPC_OK;
-    if (!h->diag || !h->d_diag || B > h->diag_B)
+    if (!h->diag || !h->diag_buf || B > h->diag_B)
         return fail(MPC_ERR_INVALID_ARG, "mpc_get_last_paths: no diagnostics of that size (mpc_set_diagnostics, then mpc_predict_batch)");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipDeviceSynchronize());
@@ -1812,7 +1727,7 @@ int mpc_get_last_inputs(mpc_handle *h, int32_t B, double *state, int32_t *ego_in
                         uint8_t *is_collide, double *others, int32_t *nveh) {
     if (!h || B < 0) return fail(MPC_ERR_INVALID_ARG, "mpc_get_last_inputs: bad argument");
     if (B == 0) return MPC_OK;
-    if (!h->d_pre || B > h->pre_B) return fail(MPC_ERR_INVALID_ARG, "mpc_get_last_inputs: no preamble output of that size");
+    if (!h->pre || B > h->pre_B) return fail(MPC_ERR_INVALID_ARG, "mpc_get_last_inputs: no preamble output of that size");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipDeviceSynchronize());
     const size_t N1 = (size_t)h->cfg.horizon + 1, V = (size_t)(h->pre_V > 0 ? h->pre_V : 1);

@@ -190,7 +190,47 @@ def concurrent_streams(n: int, device=0, candidates: int = 32):
 
 
 def _ptr(a):
-    return None if a is None else ctypes.c_void_p(a.ctypes.data)
+    """Raw address of a numpy array (host) or a torch tensor (device); None stays None."""
+    if a is None:
+        return None
+    return ctypes.c_void_p(a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr())
+
+
+def _obs_array(obs):
+    obs = np.ascontiguousarray(obs, dtype=np.float32)
+    if obs.ndim != 3 or obs.shape[2] != 8:
+        raise ValueError(f"obs must be [B, vehicles_count, 8], got {obs.shape}")
+    return obs
+
+
+def _host_out(key, B):
+    """Host arrays an entry point fills: `key` (u0 or act) [B, 2], status [B], iters [B]."""
+    return {key: np.empty((B, 2)), "status": np.empty(B, dtype=np.int32), "iters": np.empty(B, dtype=np.int32)}
+
+
+def _stream(dev):
+    """torch's current stream on `dev`, which the *_torch methods enqueue on."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _check_tensors(dev, *specs):
+    """specs (name, tensor or None, dtype[, shape]): each tensor contiguous, of that dtype (and shape), on device `dev`."""
+    for name, t, dt_, *shape in specs:
+        if t is None:
+            continue
+        if t.dtype != dt_ or not t.is_contiguous() or not t.is_cuda or t.device != dev or \
+                (shape and tuple(t.shape) != shape[0]):
+            raise ValueError(f"{name}: expected contiguous {dt_} tensor{f' {shape[0]}' if shape else ''} on {dev}")
+
+
+def _torch_out(out, key, B, dev):
+    """The caller's `out`, or fresh device tensors: `key` (u0 or act) [B, 2] float64, status [B] and iters [B] int32."""
+    if out is not None:
+        return out
+    import torch
+    return {key: torch.empty((B, 2), dtype=torch.float64, device=dev),
+            "status": torch.empty(B, dtype=torch.int32, device=dev), "iters": torch.empty(B, dtype=torch.int32, device=dev)}
 
 
 class MPCEngine:
@@ -257,11 +297,9 @@ class MPCEngine:
             if others.ndim != 3 or others.shape[0] != B or others.shape[2] != 4:
                 raise ValueError(f"others must be [B, V, 4], got {others.shape}")
             V = others.shape[1]
-        u0 = np.empty((B, 2))
+        o = _host_out("u0", B)
         U = np.empty((B, N, 2)) if want_trajectories else None
         X = np.empty((B, N + 1, 4)) if want_trajectories else None
-        status = np.empty(B, dtype=np.int32)
-        iters = np.empty(B, dtype=np.int32)
         flags = (FLAG_COLLISION_COST if collision_cost else 0) | (FLAG_STRICT_DISCONTINUITY if strict_discontinuity else 0)
         if u_init is not None:
             U = np.array(u_init, dtype=np.float64, order="C")       # in: initial controls, out: solution
@@ -269,10 +307,10 @@ class MPCEngine:
                 raise ValueError(f"u_init must be [B, N, 2] = {(B, N, 2)}, got {U.shape}")
             flags |= FLAG_WARM_START
         rc = self._lib.mpc_solve_batch(self._h, B, _ptr(state), _ptr(ego_index), _ptr(vref), _ptr(weights),
-                                       _ptr(is_collide), _ptr(others), V, flags, _ptr(u0), _ptr(U), _ptr(X),
-                                       _ptr(status), _ptr(iters), None)
+                                       _ptr(is_collide), _ptr(others), V, flags, _ptr(o["u0"]), _ptr(U), _ptr(X),
+                                       _ptr(o["status"]), _ptr(o["iters"]), None)
         self._check(rc, "mpc_solve_batch")
-        return dict(u0=u0, U=U, X=X, status=status, iters=iters)
+        return dict(o, U=U, X=X)
 
     # ------------------------------------------------------------------ device (torch) path
     def solve_batch_torch(self, state, ego_index, weights, is_collide, vref=None, others=None,
@@ -284,26 +322,17 @@ class MPCEngine:
         import torch
         B = state.shape[0]
         dev = state.device
-        for name, t, dt_ in (("state", state, torch.float64), ("ego_index", ego_index, torch.int32),
-                             ("weights", weights, torch.float64), ("is_collide", is_collide, torch.uint8),
-                             ("vref", vref, torch.float64), ("others", others, torch.float64)):
-            if t is None:
-                continue
-            if t.dtype != dt_ or not t.is_contiguous() or t.device != dev or not t.is_cuda:
-                raise ValueError(f"{name}: expected contiguous {dt_} tensor on {dev}")
-        if out is None:
-            out = dict(u0=torch.empty((B, 2), dtype=torch.float64, device=dev),
-                       status=torch.empty(B, dtype=torch.int32, device=dev),
-                       iters=torch.empty(B, dtype=torch.int32, device=dev))
+        _check_tensors(dev, ("state", state, torch.float64), ("ego_index", ego_index, torch.int32),
+                       ("weights", weights, torch.float64), ("is_collide", is_collide, torch.uint8),
+                       ("vref", vref, torch.float64), ("others", others, torch.float64))
+        out = _torch_out(out, "u0", B, dev)
         V = 0 if others is None else int(others.shape[1])
         flags = FLAG_DEVICE_PTRS | (FLAG_COLLISION_COST if collision_cost else 0) | (0 if sync else FLAG_NO_SYNC) | \
             (FLAG_THROUGHPUT if throughput else 0) | \
             (FLAG_STRICT_DISCONTINUITY if strict_discontinuity else 0)     # throughput: several batches in flight (MPC_FLAG_THROUGHPUT)
-        p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        rc = self._lib.mpc_solve_batch(self._h, B, p(state), p(ego_index), p(vref), p(weights), p(is_collide),
-                                       p(others), V, flags, p(out["u0"]), p(out.get("U")), p(out.get("X")),
-                                       p(out["status"]), p(out["iters"]), stream)
+        rc = self._lib.mpc_solve_batch(self._h, B, _ptr(state), _ptr(ego_index), _ptr(vref), _ptr(weights), _ptr(is_collide),
+                                       _ptr(others), V, flags, _ptr(out["u0"]), _ptr(out.get("U")), _ptr(out.get("X")),
+                                       _ptr(out["status"]), _ptr(out["iters"]), _stream(dev))
         self._check(rc, "mpc_solve_batch")
         return out
 
@@ -311,9 +340,7 @@ class MPCEngine:
     def detect_batch(self, obs):
         """`_check_collision` alone (agents/pure_mpc.py:552-676) for obs[B, vehicles_count, 8]: advances the detector
         records; `env_state` serves the result.  Follow with `predict_batch(..., detected=True)` for the same obs."""
-        obs = np.ascontiguousarray(obs, dtype=np.float32)
-        if obs.ndim != 3 or obs.shape[2] != 8:
-            raise ValueError(f"obs must be [B, vehicles_count, 8], got {obs.shape}")
+        obs = _obs_array(obs)
         B, rows = obs.shape[:2]
         rc = self._lib.mpc_predict_batch(self._h, B, _ptr(obs), rows, None, None, FLAG_DETECT_ONLY, None, None, None, None)
         self._check(rc, "mpc_predict_batch")
@@ -324,21 +351,17 @@ class MPCEngine:
         per-environment memory kept inside the engine), speed-profile rewrite and solve, all on the device.
         warm_start (not in the reference): each environment starts from its previous solution advanced one stage.
         detected: `detect_batch` has already advanced the records for this observation."""
-        obs = np.ascontiguousarray(obs, dtype=np.float32)
-        if obs.ndim != 3 or obs.shape[2] != 8:
-            raise ValueError(f"obs must be [B, vehicles_count, 8], got {obs.shape}")
+        obs = _obs_array(obs)
         B, rows = obs.shape[:2]
         weights = np.ascontiguousarray(weights, dtype=np.float64).reshape(B, 3)
         rs = None if ref_speed is None else np.ascontiguousarray(ref_speed, dtype=np.float64).reshape(B)
-        act = np.empty((B, 2))
-        status = np.empty(B, dtype=np.int32)
-        iters = np.empty(B, dtype=np.int32)
+        o = _host_out("act", B)
         flags = (FLAG_COLLISION_COST if collision_cost else 0) | (FLAG_WARM_START if warm_start else 0) | \
             (FLAG_DETECTED if detected else 0) | (FLAG_STRICT_DISCONTINUITY if strict_discontinuity else 0)
-        rc = self._lib.mpc_predict_batch(self._h, B, _ptr(obs), rows, _ptr(weights), _ptr(rs), flags, _ptr(act),
-                                         _ptr(status), _ptr(iters), None)
+        rc = self._lib.mpc_predict_batch(self._h, B, _ptr(obs), rows, _ptr(weights), _ptr(rs), flags, _ptr(o["act"]),
+                                         _ptr(o["status"]), _ptr(o["iters"]), None)
         self._check(rc, "mpc_predict_batch")
-        return dict(act=act, status=status, iters=iters)
+        return o
 
     def predict_batch_torch(self, obs, weights, ref_speed=None, collision_cost=False, out=None, sync=False,
                             warm_start=False, throughput=False, strict_discontinuity=False):
@@ -347,25 +370,16 @@ class MPCEngine:
         import torch
         B, rows = int(obs.shape[0]), int(obs.shape[1])
         dev = obs.device
-        for name, t, dt_ in (("obs", obs, torch.float32), ("weights", weights, torch.float64),
-                             ("ref_speed", ref_speed, torch.float64)):
-            if t is None:
-                continue
-            if t.dtype != dt_ or not t.is_contiguous() or t.device != dev or not t.is_cuda:
-                raise ValueError(f"{name}: expected contiguous {dt_} tensor on {dev}")
+        _check_tensors(dev, ("obs", obs, torch.float32), ("weights", weights, torch.float64),
+                       ("ref_speed", ref_speed, torch.float64))
         if obs.dim() != 3 or obs.shape[2] != 8 or tuple(weights.shape) != (B, 3):
             raise ValueError("obs must be [B, vehicles_count, 8] and weights [B, 3]")
-        if out is None:
-            out = dict(act=torch.empty((B, 2), dtype=torch.float64, device=dev),
-                       status=torch.empty(B, dtype=torch.int32, device=dev),
-                       iters=torch.empty(B, dtype=torch.int32, device=dev))
+        out = _torch_out(out, "act", B, dev)
         flags = FLAG_DEVICE_PTRS | (FLAG_COLLISION_COST if collision_cost else 0) | (0 if sync else FLAG_NO_SYNC) | \
             (FLAG_WARM_START if warm_start else 0) | (FLAG_THROUGHPUT if throughput else 0) | \
             (FLAG_STRICT_DISCONTINUITY if strict_discontinuity else 0)   # throughput: several groups in flight
-        p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        rc = self._lib.mpc_predict_batch(self._h, B, p(obs), rows, p(weights), p(ref_speed), flags, p(out["act"]),
-                                         p(out["status"]), p(out["iters"]), stream)
+        rc = self._lib.mpc_predict_batch(self._h, B, _ptr(obs), rows, _ptr(weights), _ptr(ref_speed), flags,
+                                         _ptr(out["act"]), _ptr(out["status"]), _ptr(out["iters"]), _stream(dev))
         self._check(rc, "mpc_predict_batch")
         return out
 
@@ -406,15 +420,13 @@ class MPCEngine:
         U = np.array(U, dtype=np.float64, order="C", copy=True)
         if U.shape != (B, N, 2):
             raise ValueError(f"U must be [B, {N}, 2], got {U.shape}")
-        u0 = np.empty((B, 2))
+        o = _host_out("u0", B)
         X = np.empty((B, N + 1, 4)) if want_traj else None
-        status = np.empty(B, dtype=np.int32)
-        iters = np.empty(B, dtype=np.int32)
         target = np.empty(B, dtype=np.int32)
-        rc = self._lib.mpc_ltv_solve_batch(self._h, B, _ptr(state), 0, _ptr(u0), _ptr(U), _ptr(X), _ptr(status),
-                                           _ptr(iters), _ptr(target), None)
+        rc = self._lib.mpc_ltv_solve_batch(self._h, B, _ptr(state), 0, _ptr(o["u0"]), _ptr(U), _ptr(X), _ptr(o["status"]),
+                                           _ptr(o["iters"]), _ptr(target), None)
         self._check(rc, "mpc_ltv_solve_batch")
-        out = dict(u0=u0, U=U, status=status, iters=iters, target_index=target)
+        out = dict(o, U=U, target_index=target)
         if want_traj:
             out["X"] = X
         return out
@@ -424,34 +436,24 @@ class MPCEngine:
         Returns dict(u0, status, iters) of device tensors."""
         import torch
         B, N, dev = int(state.shape[0]), self.horizon, state.device
-        for name, t, shape in (("state", state, (B, 4)), ("U", U, (B, N, 2))):
-            if t.dtype != torch.float64 or not t.is_contiguous() or not t.is_cuda or t.device != dev or \
-                    tuple(t.shape) != shape:
-                raise ValueError(f"{name}: expected contiguous float64 tensor {shape} on {dev}")
-        if out is None:
-            out = dict(u0=torch.empty((B, 2), dtype=torch.float64, device=dev),
-                       status=torch.empty(B, dtype=torch.int32, device=dev),
-                       iters=torch.empty(B, dtype=torch.int32, device=dev))
-        p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        rc = self._lib.mpc_ltv_solve_batch(self._h, B, p(state), FLAG_DEVICE_PTRS | (0 if sync else FLAG_NO_SYNC),
-                                           p(out["u0"]), p(U), None, p(out["status"]), p(out["iters"]), None, stream)
+        _check_tensors(dev, ("state", state, torch.float64, (B, 4)), ("U", U, torch.float64, (B, N, 2)))
+        out = _torch_out(out, "u0", B, dev)
+        rc = self._lib.mpc_ltv_solve_batch(self._h, B, _ptr(state), FLAG_DEVICE_PTRS | (0 if sync else FLAG_NO_SYNC),
+                                           _ptr(out["u0"]), _ptr(U), None, _ptr(out["status"]), _ptr(out["iters"]), None,
+                                           _stream(dev))
         self._check(rc, "mpc_ltv_solve_batch")
         return out
 
     def ltv_predict_batch(self, obs):
         """obs[B, vehicles_count, 8] float32 -> dict(act, status, iters): Agent.predict of the iterative-linear agent
         with the per-environment stored profile kept inside the engine."""
-        obs = np.ascontiguousarray(obs, dtype=np.float32)
-        if obs.ndim != 3 or obs.shape[2] != 8:
-            raise ValueError(f"obs must be [B, vehicles_count, 8], got {obs.shape}")
+        obs = _obs_array(obs)
         B, rows = obs.shape[:2]
-        act = np.empty((B, 2))
-        status = np.empty(B, dtype=np.int32)
-        iters = np.empty(B, dtype=np.int32)
-        rc = self._lib.mpc_ltv_predict_batch(self._h, B, _ptr(obs), rows, 0, _ptr(act), _ptr(status), _ptr(iters), None)
+        o = _host_out("act", B)
+        rc = self._lib.mpc_ltv_predict_batch(self._h, B, _ptr(obs), rows, 0, _ptr(o["act"]), _ptr(o["status"]),
+                                             _ptr(o["iters"]), None)
         self._check(rc, "mpc_ltv_predict_batch")
-        return dict(act=act, status=status, iters=iters)
+        return o
 
     def ltv_predict_batch_torch(self, obs, out=None, sync=False):
         """Zero-copy variant on a float32 device tensor [B, R, 8], enqueued on torch's current stream."""
@@ -459,14 +461,9 @@ class MPCEngine:
         if obs.dtype != torch.float32 or not obs.is_contiguous() or not obs.is_cuda or obs.dim() != 3 or obs.shape[2] != 8:
             raise ValueError("obs: expected contiguous float32 device tensor [B, vehicles_count, 8]")
         B, rows, dev = int(obs.shape[0]), int(obs.shape[1]), obs.device
-        if out is None:
-            out = dict(act=torch.empty((B, 2), dtype=torch.float64, device=dev),
-                       status=torch.empty(B, dtype=torch.int32, device=dev),
-                       iters=torch.empty(B, dtype=torch.int32, device=dev))
-        p = lambda t: ctypes.c_void_p(t.data_ptr())
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        rc = self._lib.mpc_ltv_predict_batch(self._h, B, p(obs), rows, FLAG_DEVICE_PTRS | (0 if sync else FLAG_NO_SYNC),
-                                             p(out["act"]), p(out["status"]), p(out["iters"]), stream)
+        out = _torch_out(out, "act", B, dev)
+        rc = self._lib.mpc_ltv_predict_batch(self._h, B, _ptr(obs), rows, FLAG_DEVICE_PTRS | (0 if sync else FLAG_NO_SYNC),
+                                             _ptr(out["act"]), _ptr(out["status"]), _ptr(out["iters"]), _stream(dev))
         self._check(rc, "mpc_ltv_predict_batch")
         return out
 
@@ -485,9 +482,9 @@ class MPCEngine:
         import torch
         if done.dtype != torch.uint8 or not done.is_contiguous() or not done.is_cuda:
             raise ValueError("done: expected contiguous uint8 device tensor")
-        stream = ctypes.c_void_p(torch.cuda.current_stream(done.device).cuda_stream)
-        rc = self._lib.mpc_reset_env_mask(self._h, int(done.numel()), ctypes.c_void_p(done.data_ptr()),
-                                          FLAG_DEVICE_PTRS | FLAG_NO_SYNC | (FLAG_WARM_START if warm_only else 0), stream)
+        rc = self._lib.mpc_reset_env_mask(self._h, int(done.numel()), _ptr(done),
+                                          FLAG_DEVICE_PTRS | FLAG_NO_SYNC | (FLAG_WARM_START if warm_only else 0),
+                                          _stream(done.device))
         self._check(rc, "mpc_reset_env_mask")
 
     def env_state(self, B):

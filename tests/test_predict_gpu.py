@@ -99,6 +99,31 @@ def test_predict_batch_torch_zero_copy_and_mask_reset():
     e.close()
 
 
+def test_reset_env_mask_host_pointers():
+    """mpc_reset_env_mask with a host mask (no MPC_FLAG_DEVICE_PTRS; the binding only passes device masks): synchronous,
+    forgets exactly the masked environments, and with MPC_FLAG_WARM_START leaves the detector state alone."""
+    import ctypes
+    from mpc_rl_for_avs_amd import engine, synth
+    B = 128
+    e = engine.MPCEngine(horizon=20, max_iter=100)
+    e.predict_batch(synth.make_obs_batch(B, 5, seed=3), np.ones((B, 3)))
+    mem0 = e.env_state(B)["collision_memory"].copy()
+    assert mem0.max() == 10
+    mask = np.zeros(B, np.uint8)
+    mask[::3] = 1
+    host = ctypes.c_void_p(mask.ctypes.data)
+    lib = engine.load_library()
+    rc = lib.mpc_reset_env_mask(e._h, B, host, engine.FLAG_WARM_START, None)
+    assert rc == 0, lib.mpc_last_error()
+    assert np.array_equal(e.env_state(B)["collision_memory"], mem0)
+    rc = lib.mpc_reset_env_mask(e._h, B, host, 0, None)
+    assert rc == 0, lib.mpc_last_error()
+    mem1 = e.env_state(B)["collision_memory"]
+    assert np.all(mem1[::3] == 0) and np.array_equal(mem1[mask == 0], mem0[mask == 0])
+    assert mem0[::3].max() > 0
+    e.close()
+
+
 def test_predict_batch_argument_errors():
     from mpc_rl_for_avs_amd import engine
     e = engine.MPCEngine(horizon=20)
