@@ -283,6 +283,24 @@ int mpc_synth_env_step(int32_t device, int32_t B, int32_t K, double dt, double s
                        uint8_t *arrived, int32_t reset_all, void *stream);
 
 /*
+ * mpc_synth_env_step_idm (an addition within ABI 8: old clients never call it, nothing else changes) - the same step with
+ * reactive traffic (csrc/mpc_synth_traffic.hpp): every other vehicle follows one of twelve routes through the junction (its
+ * entry lane x straight / left / right), keeps its distance with the Intelligent Driver Model and brakes for whatever stands
+ * in the 40 m x 4 m corridor in front of it, the ego included; a respawned or reset vehicle is placed only where it is 10 m
+ * clear of the others.  The ego, the crash test, reward, termination and the observation are those of mpc_synth_env_step.
+ * Arguments of mpc_synth_env_step plus three state arrays, DEVICE memory, updated in place: oroute [B][K'] i32 = 3 * entry +
+ * turn (entry 0..3 the approach lane, turn 0 straight, 1 left, 2 right), oprog [B][K'] f64 arc length along the route, otarget
+ * [B][K'] f64 desired speed.  opos / ohead are written from (oroute, oprog) every step.  Same limits and error returns as
+ * mpc_synth_env_step (a NULL oroute / oprog / otarget is MPC_ERR_INVALID_ARG); enqueues on `stream` only and never
+ * synchronises (capturable in a hipGraph).  The draws mpc_synth_env_step makes keep their slots; the turn is one more draw.
+ */
+int mpc_synth_env_step_idm(int32_t device, int32_t B, int32_t K, double dt, double spawn_probability, uint64_t seed,
+                           int32_t env_offset, const double *ref_xy, int32_t M, const double *action, double *ego, double *opos,
+                           double *ospeed, double *ohead, uint8_t *oactive, int32_t *oroute, double *oprog, double *otarget,
+                           int32_t *t, int64_t *rng_counter, float *obs, float *terminal_obs, float *reward, uint8_t *done,
+                           uint8_t *truncated, uint8_t *crashed, uint8_t *arrived, int32_t reset_all, void *stream);
+
+/*
  * Rollout glue for the same configurations (csrc/mpc_rollout_glue.hpp): what a step of the reference's collect_rollouts does
  * besides the MPC call and env.step, as two launches per step instead of ~40 torch kernels, and one at the rollout's end.  Device pointers, enqueue only.
  *

@@ -28,6 +28,7 @@
 #include "mpc_preamble.hpp"
 #include "mpc_preamble_wave.hpp"
 #include "mpc_synth_env.hpp"
+#include "mpc_synth_traffic.hpp"
 #include "mpc_rollout_glue.hpp"
 #include "mpc_episode_stats.hpp"
 
@@ -621,6 +622,193 @@ __global__ __launch_bounds__(64) void mpc_synth_env_rows_kernel(
         truncated[b] = trunc;
         crashed[b] = crash;
         arrived[b] = arr;
+    }
+}
+
+// ---- the same step with reactive traffic (mpc_synth_traffic.hpp; traffic = "idm").  A kernel of its own, so that the
+// constant-velocity kernel above stays the code it was, with the same mapping: lane j of a 16-lane group owns vehicle j.  Its
+// corridor scan and the spawn rule are loops over k < K of group shuffles of what lane k holds, the shape of the rank count in
+// synth_observe_rows; every shuffle sits in control flow that is uniform over the wave (a lane without a vehicle, or a group
+// whose episode goes on, computes along and discards), and all four groups reach every barrier.
+//
+// spawn rule for lane q from what lane k offers (its position, whether it stays, whether it was drawn this step)
+__device__ inline bool synth_spawn_clear(int q, int K, double cx, double cy, double sx, double sy, bool stays, bool drew) {
+    namespace env = mpc::env;
+    bool clear = true;
+    for (int k = 0; k < K; ++k) {
+        const double kx = __shfl(sx, k, 16), ky = __shfl(sy, k, 16);
+        const int kst = __shfl((int)stays, k, 16), kdr = __shfl((int)drew, k, 16);
+        const bool blocks = k != q && (kst || (k < q && kdr)) && env::too_close(cx, cy, kx, ky);
+        clear = clear && !blocks;
+    }
+    return clear;
+}
+
+__global__ __launch_bounds__(64) void mpc_synth_env_idm_kernel(
+    int B, int K, double dt, double spawn_probability, uint64_t seed, int env_offset, const double *__restrict__ ref_xy,
+    int M, const double *__restrict__ action, double *__restrict__ ego, double *__restrict__ opos,
+    double *__restrict__ ospeed, double *__restrict__ ohead, uint8_t *__restrict__ oactive, int32_t *__restrict__ oroute,
+    double *__restrict__ oprog, double *__restrict__ otarget, int32_t *__restrict__ t, int64_t *__restrict__ ctr,
+    float *__restrict__ obs, float *__restrict__ terminal_obs, float *__restrict__ reward, uint8_t *__restrict__ done,
+    uint8_t *__restrict__ truncated, uint8_t *__restrict__ crashed, uint8_t *__restrict__ arrived, int reset_all) {
+    namespace env = mpc::env;
+    constexpr int kObs = env::kRows * env::kCols;
+    __shared__ double s_ref[2 * 128];
+    __shared__ float s_obs[4][kObs];
+    for (int i = threadIdx.x; i < 2 * M; i += blockDim.x) s_ref[i] = ref_xy[i];
+    __syncthreads();
+    const int q = threadIdx.x & 15, g = threadIdx.x >> 4;
+    const int b_ = blockIdx.x * 4 + g;
+    const bool live = b_ < B;              // a group past the end computes on the last environment and writes nothing
+    const int b = live ? b_ : B - 1;
+    const int Ks = K > 0 ? K : 1;
+    const bool mine = q < K;
+    const int j = mine ? q : 0;
+    double *eg = ego + (size_t)b * 4;
+    const size_t vo = (size_t)b * Ks + j;
+    float *o = obs + (size_t)b * kObs;
+    const int64_t c0 = ctr[b];
+    const env::Rng r(seed, env_offset + b, c0);
+    double px = 0.0, py = 0.0, ps = 0.0, ph = 0.0, prog = 0.0, target = 1.0;
+    int route = 0;
+    bool act = false;
+    double ex = 0.0, ey = 0.0, eth = 0.0, esp = 0.0;
+    float rew = 0.0f;
+    bool fin = true, trunc = false, crash = false, arr = false;
+    int tn = 0;
+    if (!reset_all) {
+        // ---- ego: the MPC's own vehicle model with the action limits of the environment
+        double a = action[(size_t)b * 2], delta = action[(size_t)b * 2 + 1];
+        a = a < -5.0 ? -5.0 : (a > 5.0 ? 5.0 : a);
+        delta = delta < -env::kPiE / 4 ? -env::kPiE / 4 : (delta > env::kPiE / 4 ? env::kPiE / 4 : delta);
+        const double x = eg[0], y = eg[1], th = eg[2], sp = eg[3];
+        const double beta = atan(0.5 * tan(delta));
+        ex = x + sp * cos(th + beta) * dt;
+        ey = y + sp * sin(th + beta) * dt;
+        eth = th + sp / env::kWheelbase * sin(beta) * dt;
+        const double nv = sp + a * dt;
+        esp = nv < 0.0 ? 0.0 : (nv > 30.0 ? 30.0 : nv);
+        // ---- vehicle j: its leader among the ego and the others as they were before the step
+        if (mine) {
+            px = opos[2 * vo]; py = opos[2 * vo + 1]; ps = ospeed[vo]; ph = ohead[vo];
+            act = oactive[vo] != 0;
+            route = oroute[vo]; prog = oprog[vo]; target = otarget[vo];
+        }
+        const double cj = cos(ph), sj = sin(ph);
+        env::Leader lead = env::no_leader();
+        env::offer_leader(lead, q, px, py, ph, cj, sj, -1, x, y, th, sp);
+        for (int k = 0; k < K; ++k) {
+            const double kx = __shfl(px, k, 16), ky = __shfl(py, k, 16), kh = __shfl(ph, k, 16), kv = __shfl(ps, k, 16);
+            const int ka = __shfl((int)act, k, 16);
+            if (k != q && ka) env::offer_leader(lead, q, px, py, ph, cj, sj, k, kx, ky, kh, kv);
+        }
+        // a circle of vehicles waiting for each other: its lowest index drives free (env::walk_leaders)
+        const int who = mine && act ? lead.who : -2;
+        int wp = who, lowest = q;
+        bool closed = false;
+        for (int n = 0; n < K; ++n) {
+            const int next = __shfl(who, wp >= 0 ? wp : 0, 16);
+            env::walk_leaders(q, wp >= 0 ? next : -2, wp, lowest, closed);
+        }
+        if (closed && lowest == q) lead = env::no_leader();
+        bool stays = false, drew = false;
+        env::Drawn cand = {};
+        if (mine) {
+            if (act) {
+                const double acc = env::idm_acceleration(ps, target, ph, lead);
+                env::advance(acc, dt, prog, ps);
+                env::pose(route, prog, px, py, ph);
+                const double ax = fabs(px), ay = fabs(py);
+                stays = !((ax > ay ? ax : ay) > 65.0);
+            }
+            drew = !stays && r.u01(env::kSlotRespawn + 5 * j) < spawn_probability;
+            if (drew) cand = env::draw_vehicle(r, env::kSlotRespawn + 5 * j + 1, env::kSlotTurnRespawn + j, 40.0, 60.0);
+        }
+        const bool clear = synth_spawn_clear(q, K, cand.x, cand.y, stays ? px : cand.x, stays ? py : cand.y, stays, drew);
+        bool hit = false;
+        if (mine) {
+            if (!stays) {
+                act = drew && clear;
+                if (act) {
+                    px = cand.x; py = cand.y; ps = cand.speed; ph = cand.h;
+                    route = cand.route; prog = cand.s; target = cand.target;
+                }
+            }
+            if (act) {
+                const double dx = px - ex, dy = py - ey;
+                hit = sqrt(dx * dx + dy * dy) < env::kCrashDistance;
+            }
+        }
+        const unsigned long long hits = __ballot(hit);
+        crash = ((hits >> (16 * g)) & 0xffffull) != 0;
+        // ---- nearest route point: the first of the nearest, as the serial scan
+        double lateral = INFINITY;
+        int idx = 0;
+        for (int i = q; i < M; i += 16) {
+            const double dx = s_ref[2 * i] - ex, dy = s_ref[2 * i + 1] - ey;
+            const double d = sqrt(dx * dx + dy * dy);
+            if (d < lateral) {
+                lateral = d;
+                idx = i;
+            }
+        }
+        for (int off = 8; off >= 1; off >>= 1) {
+            const double od = __shfl_xor(lateral, off, 16);
+            const int oi = __shfl_xor(idx, off, 16);
+            const bool take = od < lateral || (od == lateral && oi < idx);
+            lateral = take ? od : lateral;
+            idx = take ? oi : idx;
+        }
+        const bool on_road = lateral <= env::kLaneHalfWidth;
+        arr = idx >= M - 3 && on_road;
+        double cen = lateral / env::kLaneHalfWidth;
+        cen = 1.0 - (cen > 1.0 ? 1.0 : cen);
+        rew = (float)(env::kRewardCollision * (crash ? 1.0 : 0.0) + env::kRewardHighSpeed * (esp / 10.0) +
+                      env::kRewardArrived * (arr ? 1.0 : 0.0) + (on_road ? env::kRewardCenter * cen : env::kRewardOffRoad));
+        tn = t[b] + 1;
+        const bool terminated = crash || arr;
+        trunc = tn >= env::kEpisodeSteps && !terminated;
+        fin = terminated || trunc;
+        synth_observe_rows(q, K, ex, ey, eth, esp, px, py, ps, ph, act, s_obs[g], terminal_obs + (size_t)b * kObs, live);
+    }
+    // ---- fresh episode (every group of a reset launch, the groups whose episode ended otherwise; uniform over a group)
+    env::Drawn fresh = {};
+    if (fin && mine) fresh = env::draw_vehicle(r, env::kSlotReset + 4 * j, env::kSlotTurnReset + j, 5.0, 60.0);
+    const bool placed = synth_spawn_clear(q, K, fresh.x, fresh.y, fresh.x, fresh.y, false, fin && mine);
+    if (fin) {
+        ex = 2.0;
+        ey = 45.0 + (-5.0 + 10.0 * r.u01(env::kSlotEgo));
+        eth = -env::kPiE / 2;
+        esp = 10.0;
+        if (mine) {
+            px = fresh.x; py = fresh.y; ps = fresh.speed; ph = fresh.h;
+            route = fresh.route; prog = fresh.s; target = fresh.target;
+            act = placed;
+        }
+    }
+    // (a group that goes on rebuilds the same observation: the four groups of a wave stay in step for the barriers inside)
+    synth_observe_rows(q, K, ex, ey, eth, esp, px, py, ps, ph, act, s_obs[g], o, live);
+    if (live && mine) {
+        opos[2 * vo] = px;
+        opos[2 * vo + 1] = py;
+        ospeed[vo] = ps;
+        ohead[vo] = ph;
+        oactive[vo] = act ? 1 : 0;
+        oroute[vo] = route;
+        oprog[vo] = prog;
+        otarget[vo] = target;
+    }
+    if (live && q == 0) {
+        eg[0] = ex; eg[1] = ey; eg[2] = eth; eg[3] = esp;
+        t[b] = fin ? 0 : tn;
+        ctr[b] = c0 + 1;
+        if (!reset_all) {
+            reward[b] = rew;
+            done[b] = fin;
+            truncated[b] = trunc;
+            crashed[b] = crash;
+            arrived[b] = arr;
+        }
     }
 }
 
@@ -1548,6 +1736,29 @@ int mpc_synth_env_step(int32_t device, int32_t B, int32_t K, double dt, double s
                        (int)B, (int)K, dt, spawn_probability, seed, (int)env_offset, ref_xy, (int)M, action, ego, opos, ospeed,
                        ohead, oactive, t, rng_counter, obs, terminal_obs, reward, done, truncated, crashed, arrived,
                        (int)reset_all);
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_synth_env_step_idm(int32_t device, int32_t B, int32_t K, double dt, double spawn_probability, uint64_t seed,
+                           int32_t env_offset, const double *ref_xy, int32_t M, const double *action, double *ego, double *opos,
+                           double *ospeed, double *ohead, uint8_t *oactive, int32_t *oroute, double *oprog, double *otarget,
+                           int32_t *t, int64_t *rng_counter, float *obs, float *terminal_obs, float *reward, uint8_t *done,
+                           uint8_t *truncated, uint8_t *crashed, uint8_t *arrived, int32_t reset_all, void *stream_) {
+    if (B < 0 || K < 0 || K > mpc::env::kMaxOthers || !(dt > 0.0) || M < 1)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_synth_env_step_idm: bad size");
+    if (!ref_xy || !ego || !opos || !ospeed || !ohead || !oactive || !oroute || !oprog || !otarget || !t || !rng_counter || !obs)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_synth_env_step_idm: null state pointer");
+    if (!reset_all && (!action || !terminal_obs || !reward || !done || !truncated || !crashed || !arrived))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_synth_env_step_idm: null output pointer");
+    if (B == 0) return MPC_OK;
+    HIP_TRY(hipSetDevice(device));
+    if (K > 15 || M > 128)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_synth_env_step_idm: at most 15 other vehicles and 128 route points");
+    hipLaunchKernelGGL(mpc_synth_env_idm_kernel, dim3((unsigned)((B + 3) / 4)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream_),
+                       (int)B, (int)K, dt, spawn_probability, seed, (int)env_offset, ref_xy, (int)M, action, ego, opos, ospeed,
+                       ohead, oactive, oroute, oprog, otarget, t, rng_counter, obs, terminal_obs, reward, done, truncated,
+                       crashed, arrived, (int)reset_all);
     HIP_TRY(hipGetLastError());
     return MPC_OK;
 }

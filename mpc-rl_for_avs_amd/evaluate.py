@@ -154,7 +154,8 @@ def _engine_of(agent):
 
 
 def _env_state_names(env):
-    return [n for n in ("ego", "opos", "ospeed", "ohead", "oactive", "t", "rng_counter") if hasattr(env, n)]
+    return [n for n in ("ego", "opos", "ospeed", "ohead", "oactive", "oroute", "oprog", "otarget", "t", "rng_counter")
+            if hasattr(env, n)]
 
 
 @torch.no_grad()

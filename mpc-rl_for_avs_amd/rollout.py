@@ -53,11 +53,19 @@ class SyntheticIntersectionEnv:
     observation in ONE launch, counter-based random numbers) - `backend="hip"`, the default there; on the CPU, or with
     `backend="torch"`, the vectorised torch ops below (about a hundred small kernels per step on a GPU).  Same state
     tensors, same return values; the two draw different random streams (as torch's CPU and GPU generators do), the
-    deterministic part of the step is identical (tests/test_rollout_cpu.py, tests/test_predict_gpu.py)."""
+    deterministic part of the step is identical (tests/test_rollout_cpu.py, tests/test_predict_gpu.py).
+
+    traffic="constant" (default): the other vehicles drive straight on at constant velocity.  traffic="idm": they follow one of
+    twelve routes through the junction (straight, left, right), keep their distance with the Intelligent Driver Model and brake
+    for what is in the corridor in front of them, the ego included (csrc/mpc_synth_traffic.hpp, `mpc_synth_env_step_idm`); three
+    more state tensors: oroute (3 * entry + turn), oprog (arc length), otarget (desired speed)."""
 
     def __init__(self, num_envs: int, device="cpu", seed: int = 0, n_others: int = 4, dt: float = 0.1,
-                 spawn_probability: float = 0.3, backend: str = "auto", env_offset: int = 0):
+                 spawn_probability: float = 0.3, backend: str = "auto", env_offset: int = 0, traffic: str = "constant"):
         assert 0 <= n_others <= VEHICLES_COUNT - 1
+        if traffic not in ("constant", "idm"):
+            raise ValueError("traffic must be constant|idm")
+        self.traffic = traffic
         self.num_envs, self.K, self.dt = int(num_envs), int(n_others), float(dt)
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
@@ -84,6 +92,12 @@ class SyntheticIntersectionEnv:
         self.oactive = torch.zeros((B, K), dtype=torch.bool, device=self.device)
         self.t = torch.zeros(B, dtype=torch.int32, device=self.device)
         self._lane_h = torch.tensor([0.0, math.pi / 2, math.pi, -math.pi / 2], dtype=torch.float64, device=self.device)
+        if self.traffic == "idm":           # csrc/mpc_synth_traffic.hpp: route = 3 * entry + turn, arc length, desired speed
+            self.oroute = torch.zeros((B, K), dtype=torch.int32, device=self.device)
+            self.oprog = torch.zeros((B, K), dtype=torch.float64, device=self.device)
+            self.otarget = torch.ones((B, K), dtype=torch.float64, device=self.device)
+            self._lane_dx = torch.tensor([1.0, 0.0, -1.0, 0.0], dtype=torch.float64, device=self.device)
+            self._lane_dy = torch.tensor([0.0, 1.0, 0.0, -1.0], dtype=torch.float64, device=self.device)
         if self.backend == "hip":
             from . import engine as _engine
             self._lib = _engine.load_library()
@@ -101,6 +115,16 @@ class SyntheticIntersectionEnv:
         o = self._out
         p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
         stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        if self.traffic == "idm":
+            rc = self._lib.mpc_synth_env_step_idm(
+                self.device.index, self.num_envs, self.K, self.dt, self.spawn_probability, self.seed, self.env_offset,
+                p(self.ref_xy), self.M, p(action), p(self.ego), p(self.opos), p(self.ospeed), p(self.ohead), p(self.oactive),
+                p(self.oroute), p(self.oprog), p(self.otarget), p(self.t), p(self.rng_counter), p(o["obs"]),
+                p(o["terminal_obs"]), p(o["reward"]), p(o["done"]), p(o["truncated"]), p(o["crashed"]), p(o["arrived"]),
+                1 if reset_all else 0, stream)
+            if rc != 0:
+                raise RuntimeError(f"mpc_synth_env_step_idm failed ({rc}): {self._lib.mpc_last_error().decode()}")
+            return
         rc = self._lib.mpc_synth_env_step(
             self.device.index, self.num_envs, self.K, self.dt, self.spawn_probability, self.seed, self.env_offset,
             p(self.ref_xy), self.M, p(action), p(self.ego), p(self.opos), p(self.ospeed), p(self.ohead), p(self.oactive),
@@ -123,6 +147,114 @@ class SyntheticIntersectionEnv:
         sp = torch.clamp(8.0 + torch.randn(shape, generator=self.gen, device=self.device, dtype=torch.float64), min=0.0)
         return torch.stack([x, y], dim=-1), sp, h
 
+    # ---- reactive traffic (traffic="idm"; the torch statement of csrc/mpc_synth_traffic.hpp) -----------------------------
+    def pose(self, route, s):
+        """Position [..., 2] and heading of arc length s on route = 3 * entry + turn (0 straight, 1 left, 2 right): the approach
+        lane up to s = 50, then a quarter circle (radius 8 right, 12 left) onto the exit arm's lane, then straight on."""
+        entry = torch.div(route, 3, rounding_mode="floor").long()
+        turn = route.long() - 3 * entry
+        dx, dy, h0 = self._lane_dx[entry], self._lane_dy[entry], self._lane_h[entry]
+        nx, ny = -dy, dx
+        u = s - 50.0
+        sgn = torch.where(turn == 2, 1.0, -1.0).to(torch.float64)          # right: centre -10 d + 10 n, heading h + phi
+        R = torch.where(turn == 2, 8.0, 12.0).to(torch.float64)
+        length = R * (math.pi / 2)
+        straight = (turn == 0) | (u <= 0.0)
+        phi = torch.clamp(u, min=0.0) / R
+        on_arc = u <= length
+        phi = torch.where(on_arc, phi, torch.full_like(phi, math.pi / 2))
+        r = torch.where(on_arc, torch.zeros_like(u), u - length)           # beyond the arc: along sgn * n from its end
+        c, sn = torch.cos(phi), torch.sin(phi)
+        ax = (-10.0 * dx + sgn * 10.0 * nx) + R * (-sgn * nx * c + dx * sn) + r * sgn * nx
+        ay = (-10.0 * dy + sgn * 10.0 * ny) + R * (-sgn * ny * c + dy * sn) + r * sgn * ny
+        x = torch.where(straight, (s - 60.0) * dx + 2.0 * nx, ax)
+        y = torch.where(straight, (s - 60.0) * dy + 2.0 * ny, ay)
+        h = torch.where(straight, h0, h0 + sgn * phi)
+        h = torch.where(h > math.pi, h - 2 * math.pi, h)
+        h = torch.where(h <= -math.pi, h + 2 * math.pi, h)
+        return torch.stack([x, y], dim=-1), h
+
+    def _draw_vehicles(self, shape, dlo, dhi):
+        """Entry lane, distance from the centre, turn and speed of new vehicles; the desired speed is the drawn one, at least 1."""
+        lane = torch.randint(0, 4, shape, generator=self.gen, device=self.device)
+        turn = torch.randint(0, 3, shape, generator=self.gen, device=self.device)
+        route = (3 * lane + turn).to(torch.int32)
+        s = 60.0 - self._u(shape, dlo, dhi)
+        sp = torch.clamp(8.0 + torch.randn(shape, generator=self.gen, device=self.device, dtype=torch.float64), min=0.0)
+        pos, h = self.pose(route, s)
+        return route, s, sp, torch.clamp(sp, min=1.0), pos, h
+
+    @staticmethod
+    def _within(a, b, clearance=10.0):
+        """[B, K, K]: vehicle j of a closer than `clearance` to vehicle k of b"""
+        d = a[:, :, None, :] - b[:, None, :, :]
+        return (d * d).sum(dim=-1) < clearance * clearance
+
+    def _traffic_step(self, x, y, th, v):
+        """The other vehicles' part of a step: IDM behind the nearest counted candidate in the corridor (the ego at x, y, th,
+        v and the others, all as they were before the step), motion along the route, respawn under the spawn rule."""
+        dt, K = self.dt, self.K
+        act, hj, vj = self.oactive, self.ohead, self.ospeed
+        cx = torch.cat([x[:, None], self.opos[..., 0]], dim=1)              # candidates [B, K + 1]: the ego, then the others
+        cy = torch.cat([y[:, None], self.opos[..., 1]], dim=1)
+        ch = torch.cat([th[:, None], hj], dim=1)
+        cv = torch.cat([v[:, None], vj], dim=1)
+        cact = torch.cat([torch.ones_like(act[:, :1]), act], dim=1)
+        cj, sj = torch.cos(hj)[..., None], torch.sin(hj)[..., None]
+        ex, ey = cx[:, None, :] - self.opos[..., 0, None], cy[:, None, :] - self.opos[..., 1, None]
+        ell = ex * cj + ey * sj                                            # [B, K, K + 1] in vehicle j's body frame
+        w = ey * cj - ex * sj
+        inside = (ell > 0.0) & (ell <= 40.0) & (w.abs() <= 2.0)
+        ic = torch.arange(-1, K, device=self.device)[None, None, :]
+        ij = torch.arange(K, device=self.device)[None, :, None]
+        dh = ch[:, None, :] - hj[..., None]
+        dh = torch.where(dh > math.pi, dh - 2 * math.pi, dh)
+        dh = torch.where(dh <= -math.pi, dh + 2 * math.pi, dh)
+        # the ego always; another vehicle a full length ahead that drives j's way, or crosses and has the lower index
+        counts = (ic < 0) | ((ell > 5.0) & ((ic < ij) | (dh.abs() < math.pi / 4)))
+        valid = inside & counts & cact[:, None, :] & (ic != ij)
+        best, arg = torch.where(valid, ell, torch.full_like(ell, float("inf"))).min(dim=2)
+        has = torch.isfinite(best) & act
+        # a circle of vehicles waiting for each other (merging at a small angle, or following mixed with yielding): walk the
+        # map j -> leader(j) K steps; the lowest index of a circle drives free this step (env::walk_leaders)
+        who = torch.where(has, arg - 1, torch.full_like(arg, -2))
+        wp, lowest = who.clone(), ij[:, :, 0].expand_as(who).clone()
+        closed = torch.zeros_like(has)
+        for _ in range(K):
+            go = (wp >= 0) & ~closed
+            closed = closed | (go & (wp == ij[:, :, 0]))
+            go = go & ~closed
+            lowest = torch.where(go, torch.minimum(lowest, wp), lowest)
+            wp = torch.where(go, torch.gather(who, 1, wp.clamp(min=0)), wp)
+        has = has & ~(closed & (lowest == ij[:, :, 0]))
+        lh, lv = torch.gather(ch, 1, arg), torch.gather(cv, 1, arg)
+        gap = torch.clamp(torch.where(has, best, torch.ones_like(best)) - 5.0, min=0.1)
+        dv = vj - lv * torch.cos(lh - hj)
+        q = (5.0 + torch.clamp(vj * 1.5 + vj * dv / 7.745966692414834, min=0.0)) / gap
+        r2 = (vj / self.otarget) ** 2
+        acc = torch.clamp(3.0 * (1.0 - r2 * r2 - torch.where(has, q * q, torch.zeros_like(q))), -6.0, 3.0)
+        self.oprog.copy_(torch.where(act, self.oprog + vj * dt, self.oprog))
+        self.ospeed.copy_(torch.where(act, torch.clamp(vj + acc * dt, 0.0, 30.0), vj))
+        pos, h = self.pose(self.oroute, self.oprog)
+        self.opos.copy_(torch.where(act[..., None], pos, self.opos))
+        self.ohead.copy_(torch.where(act, h, self.ohead))
+        stays = act & ~(self.opos.abs().amax(dim=-1) > 65.0)
+        drew = ~stays & (torch.rand(stays.shape, generator=self.gen, device=self.device) < self.spawn_probability)
+        route, s, sp, v0, pos, h = self._draw_vehicles(stays.shape, 40.0, 60.0)
+        # not placed within 10 m of a lower-index vehicle that stays or was drawn, or of a higher-index one that stays
+        other = torch.where(stays[..., None], self.opos, pos)
+        lower = ij[0] > torch.arange(K, device=self.device)[None, :]       # [K(j), K(k)]: k < j
+        diff = ~torch.eye(K, dtype=torch.bool, device=self.device)
+        blocks = self._within(pos, other) & diff[None] & (stays[:, None, :] | (lower[None] & drew[:, None, :]))
+        placed = drew & ~blocks.any(dim=2)
+        self.opos.copy_(torch.where(placed[..., None], pos, self.opos))
+        self.ospeed.copy_(torch.where(placed, sp, self.ospeed))
+        self.ohead.copy_(torch.where(placed, h, self.ohead))
+        self.oroute.copy_(torch.where(placed, route, self.oroute))
+        self.oprog.copy_(torch.where(placed, s, self.oprog))
+        self.otarget.copy_(torch.where(placed, v0, self.otarget))
+        self.oactive.copy_(stays | placed)
+
     def _reset_where(self, mask):
         B, K = self.num_envs, max(self.K, 1)
         ego = torch.zeros((B, 4), dtype=torch.float64, device=self.device)
@@ -130,6 +262,20 @@ class SyntheticIntersectionEnv:
         ego[:, 1] = 45.0 + self._u((B,), -5.0, 5.0)          # envs/intersection_env_Feb2025_v1.py:397-410
         ego[:, 2] = -math.pi / 2
         ego[:, 3] = 10.0
+        if self.traffic == "idm":
+            route, s, sp, v0, pos, h = self._draw_vehicles((B, K), 5.0, 60.0)
+            lower = torch.arange(K, device=self.device)[:, None] > torch.arange(K, device=self.device)[None, :]
+            placed = ~(self._within(pos, pos) & lower[None]).any(dim=2)    # clear of every lower-index vehicle drawn
+            if self.K == 0:
+                placed = torch.zeros_like(placed)
+            m1 = mask[:, None]
+            self.ego.copy_(torch.where(m1, ego, self.ego))
+            self.opos.copy_(torch.where(mask[:, None, None], pos, self.opos))
+            for dst, src in ((self.ospeed, sp), (self.ohead, h), (self.oactive, placed), (self.oroute, route),
+                             (self.oprog, s), (self.otarget, v0)):
+                dst.copy_(torch.where(m1, src, dst))
+            self.t.copy_(torch.where(mask, torch.zeros_like(self.t), self.t))
+            return
         pos, sp, h = self._spawn_others((B, K), 5.0, 60.0)
         m1, m2 = mask[:, None], mask[:, None, None]
         # state tensors are updated in place: a captured hipGraph (BatchedCollector(use_graph=True)) replays against
@@ -197,8 +343,14 @@ class SyntheticIntersectionEnv:
         ny = y + v * torch.sin(th + beta) * dt
         nth = th + v / WHEELBASE * torch.sin(beta) * dt
         nv = torch.clamp(v + a * dt, 0.0, 30.0)
+        if self.traffic == "idm":           # the traffic reacts to the ego as it was before the step (x .. v are views)
+            x, y, th, v = x.clone(), y.clone(), th.clone(), v.clone()
         self.ego.copy_(torch.stack([nx, ny, nth, nv], dim=1))
-        if self.K > 0:
+        if self.K > 0 and self.traffic == "idm":
+            self._traffic_step(x, y, th, v)
+            dist = torch.linalg.norm(self.opos - self.ego[:, None, :2], dim=-1)
+            crashed = ((dist < CRASH_DISTANCE) & self.oactive).any(dim=1)
+        elif self.K > 0:
             step = (self.ospeed * dt)[..., None] * torch.stack([torch.cos(self.ohead), torch.sin(self.ohead)], dim=-1)
             self.opos.add_(step)
             gone = (self.opos.abs().amax(dim=-1) > 65.0) | ~self.oactive
@@ -760,7 +912,8 @@ class BatchedCollector:
         # detector records - including records a caller restored with mpc_set_env_state before building the collector
         # (resume).  A graph collector and an eager one with the same seeds therefore produce the same rollouts
         # (tests/test_predict_gpu.py::test_graph_and_eager_collectors_produce_the_same_rollout).
-        names = [n for n in ("ego", "opos", "ospeed", "ohead", "oactive", "t", "rng_counter") if hasattr(env, n)]
+        names = [n for n in ("ego", "opos", "ospeed", "ohead", "oactive", "oroute", "oprog", "otarget", "t", "rng_counter")
+                 if hasattr(env, n)]
         snap = {n: getattr(env, n).clone() for n in names}
         snap_obs, snap_starts = self._last_obs.clone(), self._last_episode_starts.clone()
         gen_states = [self.gen.get_state(), env.gen.get_state()]

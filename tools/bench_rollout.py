@@ -29,6 +29,11 @@ def main():
                          "captured hipGraph, which is the collector's default on a GPU")
     ap.add_argument("--env-backend", default="auto", choices=("auto", "hip", "torch"),
                     help="fused HIP environment step (default on a GPU) or the vectorised torch ops")
+    ap.add_argument("--traffic", default="constant", choices=("constant", "idm"),
+                    help="the other vehicles: constant velocity on the approach lanes, or IDM on turning routes")
+    ap.add_argument("--env-only", action="store_true",
+                    help="time the environment step alone: --steps steps captured as one hipGraph, replayed --repeats times")
+    ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--max-iter", type=int, default=100, help="solver iteration cap (the reference: 1000)")
     ap.add_argument("--tol", type=float, default=1e-8, help="solver tolerance (the reference: 1e-6)")
     ap.add_argument("--sde", action="store_true",
@@ -49,7 +54,34 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29541")
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
-    for total in a.envs:
+    for total in a.envs if a.env_only else ():
+        env = rollout.SyntheticIntersectionEnv(total, device=dev, seed=0, n_others=a.others, backend=a.env_backend,
+                                               traffic=a.traffic)
+        env.reset()
+        act = torch.zeros((total, 2), dtype=torch.float64, device=dev)
+        act[:, 0] = 1.0
+        side = torch.cuda.Stream(dev)
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                env.step(act)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            for _ in range(a.steps):
+                env.step(act)
+        us = []
+        for _ in range(a.repeats + 2):                           # the first two replays are warm-up
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            graph.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) * 1e3 / a.steps)
+        us = sorted(us[2:])
+        print(json.dumps(dict(config=f"environment step alone, {total} envs, {a.others} other vehicles, {a.traffic} traffic, "
+                                     f"{env.backend} environment, {a.steps} steps per replay", envs=total, traffic=a.traffic,
+                              us_per_step_median=us[len(us) // 2], us_per_step_min=us[0], us_per_step_max=us[-1])), flush=True)
+    for total in () if a.env_only else a.envs:
         lo, hi = sharding.shard_range(total, rank, world)
         B = hi - lo
         G = max(1, min(a.groups, B))
@@ -60,7 +92,7 @@ def main():
             glo, ghi = sharding.shard_range(B, g, G)
             e_g = engine.MPCEngine(horizon=20, max_iter=a.max_iter, tol=a.tol, device=local)
             env = rollout.SyntheticIntersectionEnv(ghi - glo, device=dev, seed=rank * 97 + g, n_others=a.others,
-                                                   backend=a.env_backend, env_offset=lo + glo)
+                                                   backend=a.env_backend, env_offset=lo + glo, traffic=a.traffic)
             engs.append(e_g)
             cols.append(rollout.BatchedCollector(env, pol, e_g, version=a.version, algorithm=a.algorithm, n_steps=a.steps,
                                                  collision_cost=False, gather_actions=use_dist and G == 1,
@@ -109,8 +141,8 @@ def main():
         st = torch.cat([c.last_mpc["status"] for c in cols]).cpu().numpy()
         if rank == 0:
             print(json.dumps(dict(config=f"{total} envs on {world} GPU(s), {a.others} other vehicles, {a.version}/{a.algorithm}, "
-                                         f"horizon 20, max_iter {a.max_iter}, tol {a.tol:g}" + (f", {G} groups on {G} streams" if G > 1 else "") + (", hipGraph step" if graph else ", eager step") + f", {cols[0].env.backend} environment" + (f", gSDE (sample freq {a.sde_sample_freq})" if a.sde else ""),
-                              envs=total, n_gpus=world, distributed=dist_info, graph_fallback_reason=cols[0].graph_fallback_reason, fused_glue=cols[0].fused_glue, groups=G, graph=bool(graph), env_backend=cols[0].env.backend,
+                                         f"horizon 20, max_iter {a.max_iter}, tol {a.tol:g}" + (f", {G} groups on {G} streams" if G > 1 else "") + (", hipGraph step" if graph else ", eager step") + f", {cols[0].env.backend} environment, {a.traffic} traffic" + (f", gSDE (sample freq {a.sde_sample_freq})" if a.sde else ""),
+                              envs=total, n_gpus=world, distributed=dist_info, graph_fallback_reason=cols[0].graph_fallback_reason, fused_glue=cols[0].fused_glue, groups=G, graph=bool(graph), env_backend=cols[0].env.backend, traffic=a.traffic,
                               steps_per_env=a.steps, env_steps_per_s=total * a.steps / dt, ms_per_step=dt / a.steps * 1e3,
                               mpc_ms_per_step=(dm / a.steps * 1e3) if events else None, episodes=stats["episodes"], crashed=stats["crashed"],
                               arrived=stats["arrived"], converged_frac=float(((st == 0) | ((st >= 5) & (st <= 7))).mean()),

@@ -24,6 +24,8 @@ def main():
     ap.add_argument("--episodes-per-env", type=int, default=1)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--deterministic", action="store_true", help="MPC-RL acts with the policy's mean")
+    ap.add_argument("--traffic", default="constant", choices=("constant", "idm"),
+                    help="the other vehicles: constant velocity on the approach lanes, or IDM on turning routes")
     src = ap.add_mutually_exclusive_group()
     src.add_argument("--mpcrl", help="an SB3 checkpoint (.zip) of the reference's MPC-RL agent")
     src.add_argument("--fixture", action="store_true", help="MPC-RL: the v0 PPO policy of tests/golden/sb3_policies.npz")
@@ -52,11 +54,12 @@ def main():
         path = sde_host.sb3_zip(tmp.name, "ppo_v0")
     if path:
         agents["mpcrl"], _ = rollout.MPCRLAgent.from_sb3(path, MPCEngine(horizon=20, device=0), device=dev)
-    make_env = lambda: rollout.SyntheticIntersectionEnv(args.envs, device=dev, seed=args.seed, n_others=4)
+    make_env = lambda: rollout.SyntheticIntersectionEnv(args.envs, device=dev, seed=args.seed, n_others=4,
+                                                         traffic=args.traffic)
     for name, agent in agents.items():
         s = evaluate.compare({name: agent}, make_env, args.episodes_per_env, deterministic=args.deterministic,
                              seed=args.seed)[name]
-        print(json.dumps(dict(agent=name, envs=args.envs, episodes_per_env=args.episodes_per_env, **s)), flush=True)
+        print(json.dumps(dict(agent=name, traffic=args.traffic, envs=args.envs, episodes_per_env=args.episodes_per_env, **s)), flush=True)
     if tmp is not None:
         tmp.cleanup()
 
