@@ -393,6 +393,41 @@ int mpc_episode_stats(int32_t device, int32_t B, int32_t Q, int32_t reset, const
                       double *rec_f64, int64_t *recorded, int64_t *step_counter, void *stream);
 
 /*
+ * mpc_drive_metrics (an addition within ABI 8: old clients never call it, nothing else changes) - safety and comfort metrics
+ * of a closed-loop evaluation of B environments, per episode, beside mpc_episode_stats: how close the ego got, how long it
+ * was on a collision course, how hard it braked and jerked, how well it kept its route (formulas, in evaluation order, and
+ * the per-environment update in csrc/mpc_drive_metrics.hpp; the thresholds there are this project's).  Device pointers,
+ * enqueue only on `stream`, never synchronises (capturable in a hipGraph); sixteen lanes per environment, no LDS, no scratch.
+ * One launch per policy step, after mpc_synth_env_step (or any environment with the reference's observation layout: the
+ * update reads observations and the action only).
+ *
+ * Inputs of a step: terminal_obs [B][R][8] f32 (the scene after the step, before the auto-reset: presence, x, y, vx, vy,
+ * heading, sin_h, cos_h; row 0 the ego, rows 1 .. R-1 the other vehicles, counted when presence != 0), obs [B][R][8] f32 (what
+ * the next step starts from), action [B][2] f64 (acceleration, steering as commanded), done [B] u8, ref_xy [M][2] f64 (the
+ * ego's route), dt (step length, s).
+ * Running state: state_i32 [5][B] = steps, ttc_steps (time to collision < 2 s), close_steps (box gap < 1 m),
+ * hard_brake_steps (longitudinal acceleration < -3 m/s^2), episode ordinal j; state_f64 [17][B] = min centre gap, min box
+ * gap, min ttc, max |a_lon|, max |a_lat|, sum of squared jerk, max jerk, max steering rate, sum of the cross-track error,
+ * max cross-track error, then the carries vx, vy, cos_h, sin_h, ax, ay, steer.
+ * Records, one slot per (environment b, ordinal j < Q), the slot mpc_episode_stats writes for the same episode:
+ * rec_i32 [4][B][Q] = steps, ttc_steps, close_steps, hard_brake_steps; rec_f64 [10][B][Q] = min_centre_gap, min_box_gap,
+ * min_ttc (+inf when no other vehicle was ever present / on a collision course), max_abs_alon, max_abs_alat, rms_jerk
+ * (sqrt(sum / (steps - 1)), 0 when steps < 2), max_jerk, max_steer_rate, mean_xte, max_xte.
+ *
+ * reset != 0 (issue it after the environments' reset; terminal_obs, action and done may be NULL): initialise the running
+ * state, and the carries from obs.  Otherwise update the running state; when done[b]: if j < Q write slot [b][j]; then clear
+ * the running state and j += 1 (up to Q).  Every launch ends by storing the carries from obs row 0 and the step's ax, ay,
+ * steer.  All arithmetic is f64 without contraction on + - * / sqrt fabs: the kernel, a host build of the header and the
+ * evaluator's torch path agree bit for bit.
+ * Errors: B < 0, Q < 1, R outside 1 .. MPC_MAX_OTHERS + 1, M outside 1 .. 128, dt <= 0, a NULL state / record / obs / ref_xy
+ * pointer, or a NULL terminal_obs / action / done of a non-reset launch.
+ */
+int mpc_drive_metrics(int32_t device, int32_t B, int32_t R, int32_t Q, int32_t M, int32_t reset, double dt,
+                      const float *terminal_obs, const float *obs, const double *action, const uint8_t *done,
+                      const double *ref_xy, int32_t *state_i32, double *state_f64, int32_t *rec_i32, double *rec_f64,
+                      void *stream);
+
+/*
  * Diagnostics: the NLP's functions at GIVEN points, evaluated by the solve kernel's own code (csrc/mpc_wave.hpp:
  * Solver::evaluate - stage_terms / track / dist, which judge every line-search trial, and the model step of the rollouts),
  * so that f(z) and g(z) computed by the reference's statements (agents/pure_mpc.py:128-283; tests/golden/

@@ -30,6 +30,7 @@
 #include "mpc_synth_env.hpp"
 #include "mpc_synth_traffic.hpp"
 #include "mpc_rollout_glue.hpp"
+#include "mpc_drive_metrics.hpp"
 #include "mpc_episode_stats.hpp"
 
 namespace {
@@ -924,6 +925,33 @@ __global__ __launch_bounds__(256) void mpc_episode_stats_kernel(mpc::stats::Acco
         if (reset) *recorded = 0ull;                      // a reset launch writes no record: no add races with this
         else if (step_counter) *step_counter += 1;        // policy steps taken so far: keys mpc_policy_act's next noise
     }
+}
+
+// safety and comfort metrics of a closed-loop evaluation (mpc_drive_metrics.hpp): sixteen lanes per environment, four
+// environments per wave, the mapping of the two environment kernels.  Lane l of a group owns observation row l + 1 (R <= 17)
+// and the route segments l, l + 16, ...; four group minima by shuffles, then lane 0 does the sequential update and the one
+// record write.  Every shuffle sits in wave-uniform control flow: a lane without a row, and a group past the end (it reads
+// the last environment), carry +inf and write nothing.  No LDS, no atomics.
+__global__ __launch_bounds__(64) void mpc_drive_metrics_kernel(mpc::drive::Accounts acc, mpc::drive::StepInputs in, int reset) {
+    namespace drive = mpc::drive;
+    const int l = threadIdx.x & 15, g = threadIdx.x >> 4;
+    const int b_ = blockIdx.x * 4 + g;
+    const bool live = b_ < acc.B;
+    const int b = live ? b_ : acc.B - 1;
+    drive::Gaps m{drive::kInf, drive::kInf, drive::kInf, drive::kInf};
+    if (!reset) {
+        const float *ego = in.terminal_obs + (size_t)b * in.R * drive::kCols;
+        if (l < in.R - 1) drive::fold_row(ego, ego + (l + 1) * drive::kCols, m);
+        const int nseg = in.M > 1 ? in.M - 1 : 1;
+        for (int i = l; i < nseg; i += 16) drive::fold_segment(ego, in.ref_xy, in.M, i, m);
+    }
+    for (int off = 8; off >= 1; off >>= 1) {
+        m.centre = drive::min2(m.centre, __shfl_xor(m.centre, off, 16));
+        m.box = drive::min2(m.box, __shfl_xor(m.box, off, 16));
+        m.ttc = drive::min2(m.ttc, __shfl_xor(m.ttc, off, 16));
+        m.xte2 = drive::min2(m.xte2, __shfl_xor(m.xte2, off, 16));
+    }
+    if (live && l == 0) drive::episode_update(acc, in, b, reset != 0, m);
 }
 
 // end of a rollout (mpc_rollout_glue.hpp: truncation bootstrap + GAE): one workgroup per environment; thread t computes the
@@ -1872,6 +1900,26 @@ int mpc_episode_stats(int32_t device, int32_t B, int32_t Q, int32_t reset, const
     hipLaunchKernelGGL(mpc_episode_stats_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream_), acc, in, (int)reset,
                        reinterpret_cast<unsigned long long *>(recorded), reinterpret_cast<long long *>(step_counter));
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_drive_metrics(int32_t device, int32_t B, int32_t R, int32_t Q, int32_t M, int32_t reset, double dt,
+                      const float *terminal_obs, const float *obs, const double *action, const uint8_t *done,
+                      const double *ref_xy, int32_t *state_i32, double *state_f64, int32_t *rec_i32, double *rec_f64,
+                      void *stream_) {
+    if (B < 0 || Q < 1 || R < 1 || R > MPC_MAX_OTHERS + 1 || M < 1 || M > mpc::drive::kMaxRoute || !(dt > 0.0))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_drive_metrics: bad size (B >= 0, Q >= 1, 1 <= R <= 17, 1 <= M <= 128, dt > 0)");
+    if (!obs || !ref_xy || !state_i32 || !state_f64 || !rec_i32 || !rec_f64)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_drive_metrics: null obs / ref_xy / state / record pointer");
+    if (!reset && (!terminal_obs || !action || !done))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_drive_metrics: null step-input pointer");
+    if (B == 0) return MPC_OK;
+    HIP_TRY(hipSetDevice(device));
+    const mpc::drive::Accounts acc{(int)B, (int)Q, state_i32, state_f64, rec_i32, rec_f64};
+    const mpc::drive::StepInputs in{(int)R, (int)M, dt, terminal_obs, obs, action, done, ref_xy};
+    hipLaunchKernelGGL(mpc_drive_metrics_kernel, dim3((unsigned)((B + 3) / 4)), dim3(64), 0,
+                       reinterpret_cast<hipStream_t>(stream_), acc, in, (int)reset);
     HIP_TRY(hipGetLastError());
     return MPC_OK;
 }

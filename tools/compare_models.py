@@ -1,11 +1,14 @@
 """The reference's model comparison (main/model_comparison.py) on the synthetic intersection: every agent evaluated in closed
 loop on the same episodes (evaluate.compare), one JSON line per agent with model_comparison's five numbers (success and
-collision rate in %, average steps, average speed, average travel time) and the throughput.
+collision rate in %, average steps, average speed, average travel time) and the throughput.  --metrics adds the safety and
+comfort metrics of every agent's episodes (evaluate.DriveMetrics: near misses, time on a collision course, braking, jerk,
+route keeping; a value that does not exist, such as the closest gap when no vehicle was met, prints as null).
 
 Agents: pure MPC with the collision cost off and on, the iterative-linear (LTV) agent, and MPC-RL - an SB3 `.zip` given with
 --mpcrl, or with --fixture the v0 PPO (gSDE) policy rebuilt from tests/golden/sb3_policies.npz.
 
   python tools/compare_models.py --envs 256 --episodes-per-env 1 --fixture
+  python tools/compare_models.py --metrics --traffic idm --envs 256 --fixture
 """
 import argparse
 import json
@@ -26,10 +29,13 @@ def main():
     ap.add_argument("--deterministic", action="store_true", help="MPC-RL acts with the policy's mean")
     ap.add_argument("--traffic", default="constant", choices=("constant", "idm"),
                     help="the other vehicles: constant velocity on the approach lanes, or IDM on turning routes")
+    ap.add_argument("--metrics", action="store_true", help="also the safety and comfort metrics (evaluate.DriveMetrics)")
     src = ap.add_mutually_exclusive_group()
     src.add_argument("--mpcrl", help="an SB3 checkpoint (.zip) of the reference's MPC-RL agent")
     src.add_argument("--fixture", action="store_true", help="MPC-RL: the v0 PPO policy of tests/golden/sb3_policies.npz")
     args = ap.parse_args()
+
+    import math
 
     import torch
     from mpc_rl_for_avs_amd import evaluate, rollout
@@ -58,7 +64,8 @@ def main():
                                                          traffic=args.traffic)
     for name, agent in agents.items():
         s = evaluate.compare({name: agent}, make_env, args.episodes_per_env, deterministic=args.deterministic,
-                             seed=args.seed)[name]
+                             seed=args.seed, metrics=args.metrics)[name]
+        s = {k: (None if isinstance(v, float) and not math.isfinite(v) else v) for k, v in s.items()}
         print(json.dumps(dict(agent=name, traffic=args.traffic, envs=args.envs, episodes_per_env=args.episodes_per_env, **s)), flush=True)
     if tmp is not None:
         tmp.cleanup()
