@@ -428,6 +428,42 @@ int mpc_drive_metrics(int32_t device, int32_t B, int32_t R, int32_t Q, int32_t M
                       void *stream);
 
 /*
+ * mpc_perceive (an addition within ABI 8: old clients never call it, nothing else changes) - a perception model between the
+ * environment and the agent of a closed-loop evaluation: obs_seen is what the ego sees of the true scene obs_true under a
+ * limited range, occlusion by the other vehicles' 5 m x 2 m rectangles and by static convex quadrilaterals, random dropout
+ * and bounded measurement noise (every formula, in evaluation order, in csrc/mpc_perception.hpp).  Device pointers, enqueue
+ * only on `stream`, never synchronises (capturable in a hipGraph); sixteen lanes per environment, no LDS, no scratch.  One
+ * launch per policy step, after the environment's step, and one with reset != 0 after the environments' reset.
+ *
+ * obs_true, obs_seen [B][R][8] f32 (presence, x, y, vx, vy, heading, sin_h, cos_h; row 0 the ego, copied); occluders
+ * [S][4][2] f64, corners in order (NULL when S == 0); row_class [B][R] u8 or NULL: per INPUT row 0 absent, 1 seen, 2 out of
+ * range, 3 occluded, 4 dropped; counts [5][B] i64 += rows >= 1 present, seen, out of range, occluded, dropped; ctr [B] i64:
+ * the launch counter that keys the draws with (seed, env_offset + b), += 1.  The seen rows are compacted to rows 1, 2, ...
+ * in input order, the rest is +0.0f.  reset != 0: ctr and the counts of every b start from 0, then the launch perceives
+ * obs_true like any other.  With every parameter off (range +inf, occlusion 0, min_points 1, p_drop and the sigmas 0) obs_seen is obs_true bit for bit when the
+ * input's present rows are contiguous.
+ * Errors (MPC_ERR_INVALID_ARG): B < 0, R outside 1 .. MPC_MAX_OTHERS + 1, S outside 0 .. 8 or S > 0 with NULL occluders, a
+ * NULL params / obs_true / obs_seen / counts / ctr, obs_seen == obs_true, a wrong struct_size, min_points outside 1 .. 5,
+ * p_drop outside [0, 1], a negative or NaN sigma, range NaN or <= 0.  B == 0 is a no-op.
+ */
+typedef struct mpc_perception {
+    int32_t struct_size; /* sizeof(mpc_perception), checked like mpc_config.struct_size */
+    int32_t occlusion;   /* 0 off, 1: vehicles and static occluders hide what is behind them */
+    int32_t min_points;  /* 1..5: a row is seen when at least this many of centre + four corners are visible */
+    int32_t env_offset;  /* global id of environment 0 of this batch (sharding) */
+    double range;        /* m; +inf = off */
+    double p_drop;       /* probability that a visible row is dropped, [0, 1] */
+    double sigma_pos;    /* m */
+    double sigma_vel;    /* m/s */
+    double sigma_head;   /* rad */
+    uint64_t seed;
+} mpc_perception;
+
+int mpc_perceive(int32_t device, int32_t B, int32_t R, int32_t S, int32_t reset, const mpc_perception *params,
+                 const float *obs_true, const double *occluders, float *obs_seen, uint8_t *row_class, int64_t *counts,
+                 int64_t *ctr, void *stream);
+
+/*
  * Diagnostics: the NLP's functions at GIVEN points, evaluated by the solve kernel's own code (csrc/mpc_wave.hpp:
  * Solver::evaluate - stage_terms / track / dist, which judge every line-search trial, and the model step of the rollouts),
  * so that f(z) and g(z) computed by the reference's statements (agents/pure_mpc.py:128-283; tests/golden/

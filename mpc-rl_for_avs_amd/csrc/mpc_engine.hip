@@ -31,6 +31,7 @@
 #include "mpc_synth_traffic.hpp"
 #include "mpc_rollout_glue.hpp"
 #include "mpc_drive_metrics.hpp"
+#include "mpc_perception.hpp"
 #include "mpc_episode_stats.hpp"
 
 namespace {
@@ -952,6 +953,84 @@ __global__ __launch_bounds__(64) void mpc_drive_metrics_kernel(mpc::drive::Accou
         m.xte2 = drive::min2(m.xte2, __shfl_xor(m.xte2, off, 16));
     }
     if (live && l == 0) drive::episode_update(acc, in, b, reset != 0, m);
+}
+
+// perception model of a closed-loop evaluation (mpc_perception.hpp): sixteen lanes per environment, four environments per
+// wave, the mapping of mpc_drive_metrics_kernel.  Lane l of a group owns observation row l + 1 (R <= 17): it forms the row's
+// rectangle once, the lanes hand their rectangles round inside the group by shuffles (no second read of global memory), the
+// static occluders are read at wave-uniform addresses, and the compaction rank of a seen row is a popcount of the group's
+// slice of the ballot below the lane: no LDS, no atomics, no serial scan.  Every shuffle and ballot sits in wave-uniform
+// control flow: a lane without a row counts as absent, a group past the end reads the last environment; only stores are
+// predicated.  ctr[b] is read by every lane of the group before lane 0 of the same wave writes it.
+__global__ __launch_bounds__(64) void mpc_perceive_kernel(mpc::sense::Params P, mpc::sense::Buffers buf, int reset) {
+    namespace sense = mpc::sense;
+    const int l = threadIdx.x & 15, g = threadIdx.x >> 4;
+    const int b_ = blockIdx.x * 4 + g;
+    const bool live = b_ < buf.B;
+    const int b = live ? b_ : buf.B - 1;
+    const int R = buf.R, i = l + 1;
+    const bool has = i < R;
+    const float *in = buf.obs_true + (size_t)b * R * sense::kCols;
+    float row[sense::kCols], ego[sense::kCols];
+#pragma unroll
+    for (int c = 0; c < sense::kCols; ++c) {
+        ego[c] = in[c];
+        row[c] = in[(has ? i : 0) * sense::kCols + c];
+    }
+    if (!has) row[0] = 0.0f;                                  // no row: absent
+    const bool present = row[0] != 0.0f;
+    const double px = ego[1], py = ego[2];
+    double sx[sense::kPoints], sy[sense::kPoints];            // the centre, then the rectangle this lane also lends out
+    sense::sample_points(row, sx, sy);
+    unsigned hidden = 0;
+    if (P.occlusion != 0) {
+        for (int j = 0; j < R - 1; ++j) {
+            double qx[4], qy[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                qx[k] = __shfl(sx[k + 1], j, 16);
+                qy[k] = __shfl(sy[k + 1], j, 16);
+            }
+            const int blocks = __shfl((int)present, j, 16);
+            const unsigned h = sense::hidden_points(px, py, sx, sy, qx, qy);
+            hidden |= (blocks && j != l) ? h : 0u;
+        }
+        hidden |= sense::hidden_by_static(px, py, sx, sy, buf.occluders, buf.S);
+    }
+    const int64_t c = reset ? 0 : buf.ctr[b];
+    const mpc::env::Rng r(P.seed ^ sense::kSalt, P.env_offset + b, c);
+    const int cls = sense::classify(P, r, i, ego, row, hidden);
+    const int shift = g * 16;
+    const unsigned seen_mask = (unsigned)(__ballot(cls == sense::kSeen) >> shift) & 0xFFFFu;
+    const unsigned present_mask = (unsigned)(__ballot(cls != sense::kAbsent) >> shift) & 0xFFFFu;
+    const unsigned range_mask = (unsigned)(__ballot(cls == sense::kOutOfRange) >> shift) & 0xFFFFu;
+    const unsigned occluded_mask = (unsigned)(__ballot(cls == sense::kOccluded) >> shift) & 0xFFFFu;
+    const unsigned dropped_mask = (unsigned)(__ballot(cls == sense::kDropped) >> shift) & 0xFFFFu;
+    const int rank = (int)__popc(seen_mask & ((1u << l) - 1u)), n_seen = (int)__popc(seen_mask);
+    if (!live) return;                                        // nothing but stores below
+    float *out = buf.obs_seen + (size_t)b * R * sense::kCols;
+    if (cls == sense::kSeen) {
+        float o[sense::kCols];
+        sense::noisy_row(P, r, i, row, o);
+#pragma unroll
+        for (int k = 0; k < sense::kCols; ++k) out[(1 + rank) * sense::kCols + k] = o[k];
+    }
+    if (has && l >= n_seen) {
+#pragma unroll
+        for (int k = 0; k < sense::kCols; ++k) out[i * sense::kCols + k] = 0.0f;
+    }
+    if (has && buf.row_class) buf.row_class[(size_t)b * R + i] = (uint8_t)cls;
+    if (l == 0) {
+#pragma unroll
+        for (int k = 0; k < sense::kCols; ++k) out[k] = ego[k];
+        if (buf.row_class) buf.row_class[(size_t)b * R] = (uint8_t)sense::kSeen;
+        const size_t B = (size_t)buf.B;
+        const int n[sense::kCounts] = {(int)__popc(present_mask), n_seen, (int)__popc(range_mask),
+                                       (int)__popc(occluded_mask), (int)__popc(dropped_mask)};
+#pragma unroll
+        for (int f = 0; f < sense::kCounts; ++f) buf.counts[f * B + b] = (reset ? 0 : buf.counts[f * B + b]) + n[f];
+        buf.ctr[b] = c + 1;
+    }
 }
 
 // end of a rollout (mpc_rollout_glue.hpp: truncation bootstrap + GAE): one workgroup per environment; thread t computes the
@@ -1920,6 +1999,32 @@ int mpc_drive_metrics(int32_t device, int32_t B, int32_t R, int32_t Q, int32_t M
     const mpc::drive::StepInputs in{(int)R, (int)M, dt, terminal_obs, obs, action, done, ref_xy};
     hipLaunchKernelGGL(mpc_drive_metrics_kernel, dim3((unsigned)((B + 3) / 4)), dim3(64), 0,
                        reinterpret_cast<hipStream_t>(stream_), acc, in, (int)reset);
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_perceive(int32_t device, int32_t B, int32_t R, int32_t S, int32_t reset, const mpc_perception *params,
+                 const float *obs_true, const double *occluders, float *obs_seen, uint8_t *row_class, int64_t *counts,
+                 int64_t *ctr, void *stream_) {
+    if (B < 0 || R < 1 || R > MPC_MAX_OTHERS + 1 || S < 0 || S > mpc::sense::kMaxOccluders)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_perceive: bad size (B >= 0, 1 <= R <= 17, 0 <= S <= 8)");
+    if (!params || !obs_true || !obs_seen || !counts || !ctr || (S > 0 && !occluders))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_perceive: null params / obs_true / obs_seen / counts / ctr / occluders pointer");
+    if (obs_seen == obs_true) return fail(MPC_ERR_INVALID_ARG, "mpc_perceive: obs_seen must not be obs_true");
+    if (params->struct_size != (int32_t)sizeof(mpc_perception))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_perceive: mpc_perception.struct_size mismatch");
+    const mpc_perception &p = *params;
+    if (p.min_points < 1 || p.min_points > mpc::sense::kPoints || !(p.p_drop >= 0.0 && p.p_drop <= 1.0) ||
+        !(p.sigma_pos >= 0.0) || !(p.sigma_vel >= 0.0) || !(p.sigma_head >= 0.0) || !(p.range > 0.0))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_perceive: bad parameter (1 <= min_points <= 5, 0 <= p_drop <= 1, sigma >= 0, "
+                                         "range > 0; none NaN)");
+    if (B == 0) return MPC_OK;
+    HIP_TRY(hipSetDevice(device));
+    const mpc::sense::Params P{p.range, p.p_drop, p.sigma_pos, p.sigma_vel, p.sigma_head, p.seed, p.occlusion, p.min_points,
+                               p.env_offset};
+    const mpc::sense::Buffers buf{(int)B, (int)R, (int)S, obs_true, occluders, obs_seen, row_class, counts, ctr};
+    hipLaunchKernelGGL(mpc_perceive_kernel, dim3((unsigned)((B + 3) / 4)), dim3(64), 0,
+                       reinterpret_cast<hipStream_t>(stream_), P, buf, (int)reset);
     HIP_TRY(hipGetLastError());
     return MPC_OK;
 }

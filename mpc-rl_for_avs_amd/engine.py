@@ -50,11 +50,19 @@ class _Config(ctypes.Structure):
                 ("ltv_passes", ctypes.c_int32), ("stall_window", ctypes.c_int32)]
 
 
+class PerceptionParams(ctypes.Structure):
+    """mpc_perception of include/mpc_mi355x.h (csrc/mpc_perception.hpp has the model)."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("occlusion", ctypes.c_int32), ("min_points", ctypes.c_int32),
+                ("env_offset", ctypes.c_int32), ("range", ctypes.c_double), ("p_drop", ctypes.c_double),
+                ("sigma_pos", ctypes.c_double), ("sigma_vel", ctypes.c_double), ("sigma_head", ctypes.c_double),
+                ("seed", ctypes.c_uint64)]
+
+
 _EXPORTS = ["mpc_version", "mpc_last_error", "mpc_default_config", "mpc_default_config_sized", "mpc_create", "mpc_destroy",
             "mpc_set_reference", "mpc_solve_batch", "mpc_workspace_bytes", "mpc_predict_batch",
             "mpc_reset_env_state", "mpc_reset_env_mask", "mpc_get_env_state", "mpc_get_last_inputs",
             "mpc_ltv_solve_batch", "mpc_ltv_predict_batch", "mpc_env_state_bytes", "mpc_save_env_state",
-            "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_eval_nlp", "mpc_streams_overlap"]
+            "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_perceive", "mpc_eval_nlp", "mpc_streams_overlap"]
 ABI_VERSION = 8          # MPC_ABI_VERSION of include/mpc_mi355x.h this binding is written for
 MAX_OTHERS = 16
 _lib = None
@@ -152,12 +160,27 @@ def load_library(path: str | None = None):
     lib.mpc_episode_stats.restype = ctypes.c_int
     lib.mpc_drive_metrics.argtypes = [ctypes.c_int32] * 6 + [ctypes.c_double] + [vp] * 9 + [vp]
     lib.mpc_drive_metrics.restype = ctypes.c_int
+    lib.mpc_perceive.argtypes = [ctypes.c_int32] * 5 + [ctypes.POINTER(PerceptionParams)] + [vp] * 6 + [vp]
+    lib.mpc_perceive.restype = ctypes.c_int
     lib.mpc_eval_nlp.argtypes = [vp, ctypes.c_int32] + [vp] * 5 + [ctypes.c_int32, ctypes.c_uint32] + [vp] * 4
     lib.mpc_eval_nlp.restype = ctypes.c_int
     lib.mpc_streams_overlap.argtypes = [ctypes.c_int32, vp, vp, vp]
     lib.mpc_streams_overlap.restype = ctypes.c_int
     _lib = lib
     return lib
+
+
+def perceive(device: int, B: int, R: int, S: int, reset: bool, params: dict, obs_true, occluders, obs_seen, row_class,
+             counts, ctr, stream) -> None:
+    """mpc_perceive on device pointers (ints or None): `params` holds the fields of mpc_perception but struct_size.
+    Enqueue only; EngineError with the library's text when it refuses the arguments."""
+    lib = load_library()
+    p = PerceptionParams(struct_size=ctypes.sizeof(PerceptionParams), **params)
+    vp = lambda a: None if a is None else ctypes.c_void_p(a)
+    rc = lib.mpc_perceive(device, B, R, S, 1 if reset else 0, ctypes.byref(p), vp(obs_true), vp(occluders), vp(obs_seen),
+                          vp(row_class), vp(counts), vp(ctr), vp(stream))
+    if rc != 0:
+        raise EngineError(f"mpc_perceive failed ({rc}): {lib.mpc_last_error().decode()}")
 
 
 def streams_overlap(a, b, device: int = 0) -> bool:

@@ -19,6 +19,10 @@ path) it is `EpisodeStats._torch_update`, the same update as a few torch ops.
 `metrics=True` adds the safety and comfort metrics of csrc/mpc_drive_metrics.hpp to every episode (`DriveMetrics`: how close
 the ego got, time on a collision course, braking, jerk, route keeping), computed per step from the observations inside the
 same captured step (mpc_drive_metrics), or by the same update in elementwise torch ops on the CPU path.
+
+`perception=` puts a perception model (csrc/mpc_perception.hpp, `Perception`) between the environment and the agent: limited
+range, occlusion by vehicles and by buildings (`corner_buildings`), dropout and bounded noise.  The agent acts on what is
+seen; the accounting and the drive metrics keep reading the true scene.
 """
 from __future__ import annotations
 
@@ -42,6 +46,10 @@ DRIVE_F64 = ("min_centre_gap", "min_box_gap", "min_ttc", "max_abs_alon", "max_ab
 HALF_LENGTH, HALF_WIDTH, CRASH_DISTANCE = 2.5, 1.0, 2.5
 TTC_THRESHOLD, CLOSE_GAP, HARD_BRAKE = 2.0, 1.0, 3.0
 MAX_ROWS, MAX_ROUTE = 17, 128                                                       # MPC_MAX_OTHERS + 1, route points
+# csrc/mpc_perception.hpp: the classes of a row, the planes of `counts`, the salt of the draws, sqrt(3), slots per row
+ROW_ABSENT, ROW_SEEN, ROW_OUT_OF_RANGE, ROW_OCCLUDED, ROW_DROPPED = 0, 1, 2, 3, 4
+PERCEPTION_COUNTS = ("present", "seen", "out_of_range", "occluded", "dropped")      # mpc_perceive counts [5][B]
+PERCEPTION_SALT, UNIT_SCALE, ROW_SLOTS, MAX_OCCLUDERS = 0xC2B2AE3D27D4EB4F, 1.7320508075688772, 32, 8
 
 
 def records_from_planes(rec_i32, rec_f64) -> dict:
@@ -330,18 +338,209 @@ class DriveMetrics:
         return drive_records_from_planes(self.rec_i32.cpu().numpy(), self.rec_f64.cpu().numpy())
 
 
+def corner_buildings(setback: float = 6.0, size: float = 30.0, road_half_width: float = 4.0) -> np.ndarray:
+    """The four buildings on the corners of the junction of csrc/mpc_synth_env.hpp (lane centres at +-2 m, lane half width
+    2 m, so the carriageway ends at +-4 m) as static occluders [4][4][2]: axis-aligned squares, one per quadrant in the order
+    (+, +), (-, +), (-, -), (+, -), the inner corner at (+-(road_half_width + setback), +-(road_half_width + setback)),
+    extending `size` outwards."""
+    a = float(road_half_width) + float(setback)
+    b = a + float(size)
+    out = np.zeros((4, 4, 2))
+    for q, (sx, sy) in enumerate(((1, 1), (-1, 1), (-1, -1), (1, -1))):
+        x0, x1 = sorted((sx * a, sx * b))
+        y0, y1 = sorted((sy * a, sy * b))
+        out[q] = [[x0, y0], [x1, y0], [x1, y1], [x0, y1]]
+    return out
+
+
+def _mix64(z):
+    """mpc::env::mix64 on numpy uint64 arrays (wrapping arithmetic)."""
+    z = z + np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def _u01(seed: int, env, ctr, slots):
+    """mpc::env::Rng(seed, env, ctr).u01(slot) for env, ctr [B] (int64) and slots [...] -> f64 [B, ...]."""
+    with np.errstate(over="ignore"):
+        s = np.asarray([(int(seed) ^ 0xA5A5A5A5) & (2 ** 64 - 1)], dtype=np.uint64)
+        key = _mix64(_mix64(s) + np.asarray(env, np.int64).astype(np.uint64) * np.uint64(0x100000001B3)) ^ \
+            _mix64(np.asarray(ctr, np.int64).astype(np.uint64))
+        slots = np.asarray(slots, np.int64).astype(np.uint64)
+        bits = _mix64(key.reshape((-1,) + (1,) * slots.ndim) + slots[None] * np.uint64(0xD1342543DE82EF95))
+    return (bits >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+
+
+class Perception:
+    """What the ego sees of the true observation (csrc/mpc_perception.hpp states the model formula by formula): rows beyond
+    `range` metres, rows hidden behind other vehicles or behind the static `occluders` [S, 4, 2] (`occlusion`; a row counts
+    as visible while at least `min_points` of its centre and four corners are), rows dropped with probability `p_drop`, and
+    bounded noise of standard deviation sigma_pos [m], sigma_vel [m/s], sigma_head [rad] on the rest.  The default of every
+    parameter switches it off.  The draws are keyed by (seed, env_offset + b, launches since the reset), so they do not
+    depend on the batch size or on how the environments are sharded.
+
+    `apply(obs_true, out, reset=False)` fills `out` [B, R, 8] f32 (the seen rows compacted behind the ego's, the rest zero)
+    and returns it; `row_class` [B, R] u8 holds the class of every input row of the last launch (ROW_*), `counts` [5, B] i64
+    the rows of each of PERCEPTION_COUNTS since the reset, `ctr` [B] i64 the launches.  Backend "hip" is the kernel
+    (mpc_perceive, enqueue only, capturable); backend "torch" is the reference path for machines without a GPU: the same
+    update in numpy, draws in uint64, the same bits.  The parameters are plain attributes and may be changed between
+    launches."""
+
+    def __init__(self, B: int, device, backend: str = "torch", R: int = VEHICLES_COUNT, range: float = float("inf"),
+                 occlusion: bool = False, min_points: int = 1, p_drop: float = 0.0, sigma_pos: float = 0.0,
+                 sigma_vel: float = 0.0, sigma_head: float = 0.0, occluders=None, seed: int = 0, env_offset: int = 0):
+        if backend not in ("hip", "torch"):
+            raise ValueError("backend must be 'hip' or 'torch'")
+        if int(B) < 0 or not 1 <= int(R) <= MAX_ROWS:
+            raise ValueError(f"B must be >= 0 and R 1..{MAX_ROWS}")
+        if not 1 <= int(min_points) <= 5:
+            raise ValueError("min_points must be 1..5")
+        if not 0.0 <= float(p_drop) <= 1.0:
+            raise ValueError("p_drop must be in [0, 1]")
+        for name, v in (("sigma_pos", sigma_pos), ("sigma_vel", sigma_vel), ("sigma_head", sigma_head)):
+            if not float(v) >= 0.0:
+                raise ValueError(f"{name} must be >= 0")
+        if not float(range) > 0.0:
+            raise ValueError("range must be > 0")
+        if not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("seed must fit 64 unsigned bits")
+        self.B, self.R, self.device, self.backend = int(B), int(R), torch.device(device), backend
+        self.range, self.occlusion, self.min_points, self.p_drop = float(range), bool(occlusion), int(min_points), float(p_drop)
+        self.sigma_pos, self.sigma_vel, self.sigma_head = float(sigma_pos), float(sigma_vel), float(sigma_head)
+        self.seed, self.env_offset = int(seed), int(env_offset)
+        occ = np.zeros((0, 4, 2)) if occluders is None else np.ascontiguousarray(occluders, dtype=np.float64)
+        if occ.ndim != 3 or occ.shape[1:] != (4, 2) or occ.shape[0] > MAX_OCCLUDERS or not np.isfinite(occ).all():
+            raise ValueError(f"occluders must be [S, 4, 2] finite corners with S <= {MAX_OCCLUDERS}")
+        self.S = int(occ.shape[0])
+        self.occluders = torch.from_numpy(occ).to(self.device)
+        z = lambda *s, dt: torch.zeros(s, dtype=dt, device=self.device)
+        self.row_class = z(self.B, self.R, dt=torch.uint8)
+        self.counts = z(5, self.B, dt=torch.int64)
+        self.ctr = z(self.B, dt=torch.int64)
+
+    @property
+    def config(self) -> dict:
+        """The keyword arguments that make a Perception with the same model and the same draws."""
+        return dict(R=self.R, range=self.range, occlusion=self.occlusion, min_points=self.min_points, p_drop=self.p_drop,
+                    sigma_pos=self.sigma_pos, sigma_vel=self.sigma_vel, sigma_head=self.sigma_head,
+                    occluders=self.occluders.cpu().numpy().copy(), seed=self.seed, env_offset=self.env_offset)
+
+    def apply(self, obs_true, out, reset: bool = False):
+        shape = (self.B, self.R, 8)
+        for name, t in (("obs_true", obs_true), ("out", out)):
+            if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape} on {self.device}")
+        if out.data_ptr() == obs_true.data_ptr() and self.B > 0:
+            raise ValueError("out must not be obs_true")
+        if self.backend == "torch":
+            seen = self._numpy_apply(obs_true.cpu().numpy(), bool(reset))
+            out.copy_(torch.from_numpy(seen))
+            return out
+        from . import engine as _engine
+        params = dict(occlusion=int(self.occlusion), min_points=self.min_points, env_offset=self.env_offset, range=self.range,
+                      p_drop=self.p_drop, sigma_pos=self.sigma_pos, sigma_vel=self.sigma_vel, sigma_head=self.sigma_head,
+                      seed=self.seed)
+        _engine.perceive(self.device.index, self.B, self.R, self.S, bool(reset), params, obs_true.data_ptr(),
+                         self.occluders.data_ptr() if self.S else None, out.data_ptr(), self.row_class.data_ptr(),
+                         self.counts.data_ptr(), self.ctr.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        return out
+
+    def _hidden(self, t, present):
+        """[B, K, 5] bool: the sight line from the ego to sample point k of row i strictly crosses an occluding edge."""
+        B, K, S = self.B, self.R - 1, self.S
+        e = lambda a: a[:, None, None, None, None]                       # the ego [B] against [B, i, point, quad, edge]
+        px, py = e(t[:, 0, 1]), e(t[:, 0, 2])
+        rect = np.stack([np.stack(c, axis=-1) for c in _corners(t[:, 1:, 1], t[:, 1:, 2], t[:, 1:, 7], t[:, 1:, 6])], axis=2)
+        pts = np.concatenate([t[:, 1:, None, 1:3], rect], axis=2)        # [B, K, 5, 2]: the centre, then the corners
+        quads = np.concatenate([rect, np.broadcast_to(self.occluders.cpu().numpy()[None], (B, S, 4, 2))], axis=1)
+        blocks = np.concatenate([present, np.ones((B, S), bool)], axis=1)[:, None, :] & \
+            (np.arange(K)[:, None] != np.arange(K + S)[None, :])[None]   # [B, i, quad]: present, and not row i itself
+        e0, e1 = quads, np.roll(quads, -1, axis=2)
+        q = lambda a: a[:, None, None, :, :]
+        e0x, e0y, e1x, e1y = q(e0[..., 0]), q(e0[..., 1]), q(e1[..., 0]), q(e1[..., 1])
+        sx, sy = pts[:, :, :, None, None, 0], pts[:, :, :, None, None, 1]
+        cross = lambda ax, ay, bx, by: ax * by - ay * bx
+        ex, ey, rx, ry = e1x - e0x, e1y - e0y, sx - px, sy - py
+        d1, d2 = cross(ex, ey, px - e0x, py - e0y), cross(ex, ey, sx - e0x, sy - e0y)
+        d3, d4 = cross(rx, ry, e0x - px, e0y - py), cross(rx, ry, e1x - px, e1y - py)
+        crossing = (((d1 > 0) & (d2 < 0)) | ((d1 < 0) & (d2 > 0))) & (((d3 > 0) & (d4 < 0)) | ((d3 < 0) & (d4 > 0)))
+        return (crossing & blocks[:, :, None, :, None]).any(axis=(3, 4))
+
+    def _numpy_apply(self, obs, reset):
+        B, R, K = self.B, self.R, self.R - 1
+        counts, ctr = self.counts.cpu().numpy(), self.ctr.cpu().numpy()
+        if reset:
+            counts[:], ctr[:] = 0, 0
+        t = obs.astype(np.float64)
+        present = obs[:, 1:, 0] != 0
+        rx, ry = t[:, 1:, 1] - t[:, :1, 1], t[:, 1:, 2] - t[:, :1, 2]
+        far = rx * rx + ry * ry > self.range * self.range
+        if self.occlusion and K > 0:
+            occluded = (5 - self._hidden(t, present).sum(axis=2)) < self.min_points
+        else:
+            occluded = np.zeros((B, K), bool)
+        rows = np.arange(1, R)
+        u = _u01(self.seed ^ PERCEPTION_SALT, self.env_offset + np.arange(B), ctr,
+                 ROW_SLOTS * rows[:, None] + np.arange(21)[None, :])                    # [B, K, 21]
+        dropped = u[:, :, 0] < self.p_drop
+        cls = np.select([~present, far, occluded, dropped], [ROW_ABSENT, ROW_OUT_OF_RANGE, ROW_OCCLUDED, ROW_DROPPED],
+                        ROW_SEEN).astype(np.uint8)
+        n = lambda k: ((u[:, :, k] + u[:, :, k + 1]) + (u[:, :, k + 2] + u[:, :, k + 3]) - 2.0) * UNIT_SCALE
+        noisy = obs[:, 1:].copy()
+        if self.sigma_pos != 0.0:
+            noisy[:, :, 1] = (t[:, 1:, 1] + self.sigma_pos * n(1)).astype(np.float32)
+            noisy[:, :, 2] = (t[:, 1:, 2] + self.sigma_pos * n(5)).astype(np.float32)
+        if self.sigma_vel != 0.0:
+            noisy[:, :, 3] = (t[:, 1:, 3] + self.sigma_vel * n(9)).astype(np.float32)
+            noisy[:, :, 4] = (t[:, 1:, 4] + self.sigma_vel * n(13)).astype(np.float32)
+        if self.sigma_head != 0.0:
+            eps = self.sigma_head * n(17)
+            sh, ch = t[:, 1:, 6], t[:, 1:, 7]
+            c1, s1 = ch - eps * sh, sh + eps * ch
+            nrm = np.sqrt(c1 * c1 + s1 * s1)
+            ok = nrm != 0
+            safe = np.where(ok, nrm, 1.0)
+            noisy[:, :, 5] = (t[:, 1:, 5] + eps).astype(np.float32)
+            noisy[:, :, 6] = np.where(ok, (s1 / safe).astype(np.float32), obs[:, 1:, 6])
+            noisy[:, :, 7] = np.where(ok, (c1 / safe).astype(np.float32), obs[:, 1:, 7])
+        seen = cls == ROW_SEEN
+        out = np.zeros((B, R, 8), np.float32)
+        out[:, 0] = obs[:, 0]
+        if K > 0:
+            order = np.argsort(~seen, axis=1, kind="stable")                           # the seen rows first, in input order
+            packed = np.take_along_axis(noisy, order[:, :, None], axis=1)
+            keep = np.arange(K)[None, :] < seen.sum(axis=1)[:, None]
+            out[:, 1:][keep] = packed[keep]
+        for f, c in enumerate((ROW_ABSENT, ROW_SEEN, ROW_OUT_OF_RANGE, ROW_OCCLUDED, ROW_DROPPED)):
+            counts[f] += (cls != ROW_ABSENT).sum(axis=1) if f == 0 else (cls == c).sum(axis=1)
+        ctr += 1
+        row_class = np.concatenate([np.full((B, 1), ROW_SEEN, np.uint8), cls], axis=1)
+        for dst, src in ((self.counts, counts), (self.ctr, ctr), (self.row_class, row_class)):
+            dst.copy_(torch.from_numpy(np.ascontiguousarray(src)))
+        return out
+
+    def totals(self) -> dict:
+        """Rows >= 1 since the reset, summed over the environments: present, seen, out_of_range, occluded, dropped."""
+        c = self.counts.sum(dim=1).cpu().numpy()
+        return {k: int(c[i]) for i, k in enumerate(PERCEPTION_COUNTS)}
+
+
 @dataclass
 class EvalResult:
     """records: dict of numpy arrays [B, Q] (steps, success, collision, truncated, avg_speed, return, unsolved, max_iters);
     steps: policy steps the batch took; env_steps = steps * B; seconds: host clock around the stepping loop (it ends in a
     synchronise); drive: the drive metrics' records (dict of numpy arrays [B, Q], keys DRIVE_I32 + DRIVE_F64; slot [b, j]
-    is the episode of records' slot [b, j]) when the evaluation ran with metrics=True, else None."""
+    is the episode of records' slot [b, j]) when the evaluation ran with metrics=True, else None; perception: the totals of
+    the perception model (`Perception.totals()`: rows present, seen, out_of_range, occluded, dropped over the whole
+    evaluation, idle steps included) when the evaluation ran with one, else None."""
     records: dict
     dt: float
     steps: int
     env_steps: int
     seconds: float
     drive: dict | None = None
+    perception: dict | None = None
 
     @property
     def travel_time(self):
@@ -355,10 +554,14 @@ class EvalResult:
         is finite (inf when there is none), episodes_with_traffic (episodes with a finite min_box_gap), ttc_exposure and
         hard_brake_rate (steps below TTC_THRESHOLD / braking harder than HARD_BRAKE, over all steps), the means over
         episodes max_abs_alon_mean, max_abs_alat_mean, rms_jerk_mean, max_steer_rate_mean, mean_xte, and max_xte (the
-        largest of any episode)."""
+        largest of any episode).  With a perception model also seen_frac, occluded_frac, out_of_range_frac and dropped_frac:
+        each class as a share of the present rows (0 when no row was ever present)."""
         out = self._base_summary()
         if self.drive is not None:
             out.update(self._drive_summary())
+        if self.perception is not None:
+            present = max(self.perception["present"], 1)
+            out.update({f"{k}_frac": self.perception[k] / present for k in ("seen", "occluded", "out_of_range", "dropped")})
         return out
 
     def _drive_summary(self) -> dict:
@@ -403,7 +606,7 @@ def _env_state_names(env):
 @torch.no_grad()
 def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = False, reset_mpc_on_done: bool = False,
                    use_graph: bool | None = None, poll_every: int = 16, seed: int = 0, on_step=None,
-                   metrics: bool = False) -> EvalResult:
+                   metrics: bool = False, perception=None) -> EvalResult:
     """Run `agent` in closed loop on the B environments of `env` (a SyntheticIntersectionEnv) until each environment has
     finished `episodes_per_env` episodes; returns their records.
 
@@ -418,6 +621,11 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     after the reset and after every step (eager path only; tensors, valid until the next step).
     metrics=True: also the safety and comfort metrics of every episode (`DriveMetrics`, EvalResult.drive), updated after the
     accounting inside the step (so inside the captured graph); on_step's dict then also holds terminal_obs, obs and act.
+    perception: a `Perception` for this environment's batch, or a dict of its keyword arguments (env_offset defaults to the
+    environment's).  The agent then acts on `perception.apply(true observation)`, after the reset (reset=True) and after every
+    step inside the step (so inside the captured graph); the accounting and the drive metrics keep reading the true scene
+    and the environment's own flags.  on_step's dict then also holds obs (the true observation), seen (what the agent gets;
+    the buffer is overwritten by the next step) and row_class; EvalResult.perception holds the totals.  None: nothing changes.
     Every episode ends by EPISODE_STEPS (200) steps, so Q * 200 steps bound the loop; RuntimeError if the episodes are not
     all recorded by then."""
     Q = int(episodes_per_env)
@@ -441,6 +649,12 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     stats = EpisodeStats(B, Q, dev, "hip" if hip else "torch")
     obs = torch.zeros((B, VEHICLES_COUNT, 8), dtype=torch.float32, device=dev)     # the observation the agent acts on
     drive = DriveMetrics(B, Q, dev, "hip" if hip else "torch", env.ref_xy, env.dt, VEHICLES_COUNT) if metrics else None
+    if isinstance(perception, dict):
+        pkw = dict(env_offset=int(getattr(env, "env_offset", 0)))
+        pkw.update(perception)
+        perception = Perception(B, dev, "hip" if hip else "torch", **pkw)
+    if perception is not None and (perception.B != B or perception.R != VEHICLES_COUNT or perception.device != dev):
+        raise ValueError(f"perception must be built for {B} environments of {VEHICLES_COUNT} rows on {dev}")
     kw = dict(deterministic=bool(deterministic), seed=int(seed), env_offset=int(getattr(env, "env_offset", 0)))
 
     def step():
@@ -456,8 +670,20 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
         if drive is not None:
             drive.update(info["terminal_obs"], new_obs, out["act"], done)
             inputs.update(terminal_obs=info["terminal_obs"], obs=new_obs, act=out["act"])
-        obs.copy_(new_obs)
+        if perception is None:
+            obs.copy_(new_obs)
+        else:
+            perception.apply(new_obs, obs)
+            inputs.update(obs=new_obs, seen=obs, row_class=perception.row_class)
         return out, inputs
+
+    def first_obs(reset):
+        true = env.reset()
+        if perception is None:
+            obs.copy_(true)
+            return obs
+        perception.apply(true, obs, reset=reset)
+        return true
 
     graph = None
     if use_graph:
@@ -467,7 +693,7 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
         names = _env_state_names(env)
         snap = {n: getattr(env, n).clone() for n in names}
         gen_state = env.gen.get_state()
-        obs.copy_(env.reset())
+        first_obs(False)
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -485,7 +711,7 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
             getattr(env, n).copy_(snap[n])
         env.gen.set_state(gen_state)
 
-    obs.copy_(env.reset())
+    true0 = first_obs(True)                  # `obs` itself without a perception model
     if hasattr(agent, "reset_env_state"):
         agent.reset_env_state()
     elif hasattr(eng, "reset_env_state"):
@@ -494,9 +720,12 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
         agent.restart_actions()
     stats.update(env.ego, reset=True)
     if drive is not None:
-        drive.update(None, obs, None, None, reset=True)
+        drive.update(None, true0, None, None, reset=True)
     if on_step is not None:
-        on_step(dict(reset=True, ego=env.ego, obs=obs) if drive is not None else dict(reset=True, ego=env.ego))
+        first = dict(reset=True, ego=env.ego, obs=true0) if drive is not None else dict(reset=True, ego=env.ego)
+        if perception is not None:
+            first.update(obs=true0, seen=obs, row_class=perception.row_class)
+        on_step(first)
     target, max_steps = B * Q, Q * EPISODE_STEPS
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
@@ -520,12 +749,17 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     if recorded < target:
         raise RuntimeError(f"only {recorded} of {target} episodes recorded after {n} steps (bound {max_steps})")
     return EvalResult(records=stats.records(), dt=float(env.dt), steps=n, env_steps=n * B, seconds=seconds,
-                      drive=None if drive is None else drive.records())
+                      drive=None if drive is None else drive.records(),
+                      perception=None if perception is None else perception.totals())
 
 
-def compare(agents: dict, make_env, episodes_per_env: int = 1, metrics: bool = False, **kw) -> dict:
+def compare(agents: dict, make_env, episodes_per_env: int = 1, metrics: bool = False, perception=None, **kw) -> dict:
     """Evaluate every agent on a fresh environment from make_env() (same seed: the HIP environment keys its draws by seed and
     environment id, so every agent meets the same initial episodes) -> {name: summary}; metrics=True adds the drive metrics'
-    keys to every summary."""
-    return {name: evaluate_agent(agent, make_env(), episodes_per_env, metrics=metrics, **kw).summary()
+    keys to every summary.  perception (a dict of `Perception`'s keyword arguments, or a Perception whose configuration is
+    copied): every agent gets a fresh Perception with the same seed, hence the same draws on the same steps."""
+    if isinstance(perception, Perception):
+        perception = perception.config
+    return {name: evaluate_agent(agent, make_env(), episodes_per_env, metrics=metrics,
+                                 perception=None if perception is None else dict(perception), **kw).summary()
             for name, agent in agents.items()}

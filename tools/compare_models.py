@@ -3,12 +3,16 @@ loop on the same episodes (evaluate.compare), one JSON line per agent with model
 collision rate in %, average steps, average speed, average travel time) and the throughput.  --metrics adds the safety and
 comfort metrics of every agent's episodes (evaluate.DriveMetrics: near misses, time on a collision course, braking, jerk,
 route keeping; a value that does not exist, such as the closest gap when no vehicle was met, prints as null).
+--range, --occlusion, --dropout and the three --sigma-* flags put a perception model between the environment and every agent
+(evaluate.Perception: the agents act on what the ego sees, the numbers keep describing the true scene); the flags are echoed
+in the JSON line, which then also holds the share of present rows that were seen, occluded, out of range and dropped.
 
 Agents: pure MPC with the collision cost off and on, the iterative-linear (LTV) agent, and MPC-RL - an SB3 `.zip` given with
 --mpcrl, or with --fixture the v0 PPO (gSDE) policy rebuilt from tests/golden/sb3_policies.npz.
 
   python tools/compare_models.py --envs 256 --episodes-per-env 1 --fixture
   python tools/compare_models.py --metrics --traffic idm --envs 256 --fixture
+  python tools/compare_models.py --metrics --traffic idm --occlusion buildings --range 60 --sigma-pos 0.2
 """
 import argparse
 import json
@@ -30,6 +34,14 @@ def main():
     ap.add_argument("--traffic", default="constant", choices=("constant", "idm"),
                     help="the other vehicles: constant velocity on the approach lanes, or IDM on turning routes")
     ap.add_argument("--metrics", action="store_true", help="also the safety and comfort metrics (evaluate.DriveMetrics)")
+    ap.add_argument("--range", type=float, default=float("inf"), help="perception: sensing range [m] (default: unlimited)")
+    ap.add_argument("--occlusion", default="off", choices=("off", "vehicles", "buildings"),
+                    help="perception: vehicles hide what is behind them; buildings: also the four corner buildings "
+                         "(evaluate.corner_buildings)")
+    ap.add_argument("--dropout", type=float, default=0.0, help="perception: probability that a visible vehicle is dropped")
+    ap.add_argument("--sigma-pos", type=float, default=0.0, help="perception: position noise [m]")
+    ap.add_argument("--sigma-vel", type=float, default=0.0, help="perception: velocity noise [m/s]")
+    ap.add_argument("--sigma-head", type=float, default=0.0, help="perception: heading noise [rad]")
     src = ap.add_mutually_exclusive_group()
     src.add_argument("--mpcrl", help="an SB3 checkpoint (.zip) of the reference's MPC-RL agent")
     src.add_argument("--fixture", action="store_true", help="MPC-RL: the v0 PPO policy of tests/golden/sb3_policies.npz")
@@ -62,11 +74,21 @@ def main():
         agents["mpcrl"], _ = rollout.MPCRLAgent.from_sb3(path, MPCEngine(horizon=20, device=0), device=dev)
     make_env = lambda: rollout.SyntheticIntersectionEnv(args.envs, device=dev, seed=args.seed, n_others=4,
                                                          traffic=args.traffic)
+    flags = dict(range=args.range, occlusion=args.occlusion, dropout=args.dropout,
+                 sigma_pos=args.sigma_pos, sigma_vel=args.sigma_vel, sigma_head=args.sigma_head)
+    perception = None                    # no flag given: no perception model, the launches of before
+    if flags != dict(range=float("inf"), occlusion="off", dropout=0.0, sigma_pos=0.0, sigma_vel=0.0, sigma_head=0.0):
+        perception = dict(range=args.range, occlusion=args.occlusion != "off", p_drop=args.dropout,
+                          sigma_pos=args.sigma_pos, sigma_vel=args.sigma_vel, sigma_head=args.sigma_head, seed=args.seed,
+                          occluders=evaluate.corner_buildings() if args.occlusion == "buildings" else None)
+    finite = lambda v: None if isinstance(v, float) and not math.isfinite(v) else v
+    echo = {} if perception is None else dict(perception={k: finite(v) for k, v in flags.items()})
     for name, agent in agents.items():
         s = evaluate.compare({name: agent}, make_env, args.episodes_per_env, deterministic=args.deterministic,
-                             seed=args.seed, metrics=args.metrics)[name]
-        s = {k: (None if isinstance(v, float) and not math.isfinite(v) else v) for k, v in s.items()}
-        print(json.dumps(dict(agent=name, traffic=args.traffic, envs=args.envs, episodes_per_env=args.episodes_per_env, **s)), flush=True)
+                             seed=args.seed, metrics=args.metrics, perception=perception)[name]
+        s = {k: finite(v) for k, v in s.items()}
+        print(json.dumps(dict(agent=name, traffic=args.traffic, envs=args.envs, episodes_per_env=args.episodes_per_env,
+                              **echo, **s)), flush=True)
     if tmp is not None:
         tmp.cleanup()
 
