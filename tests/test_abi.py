@@ -54,6 +54,23 @@ def test_default_config_and_argument_checks():
     assert lib.mpc_rollout_finish(0, 9000, 4, 1, 85, 0, p, p, p, None, 0.99, 0.95, p, p, None) == -1   # T > 8192
     assert lib.mpc_rollout_finish(0, 8, 4, 1, 84, 0, p, p, p, None, 0.99, 0.95, p, p, None) == -1      # row layout
     assert lib.mpc_rollout_finish(0, 8, 4, 1, 85, 0, None, p, p, None, 0.99, 0.95, p, p, None) == -1   # null row
+    # mpc_rollout_record(device, T, B, A, cols, keep_terminal, 21 pointers, stream): 85 = 80 + A + 4, 166 = 85 + 80 + 1 columns
+    def record(T=8, B=4, A=1, cols=85, keep=0, null=()):
+        names = ("row", "mpc_actions_buf", "pos_dev", "ticket", "last_obs", "last_starts", "actions", "values", "log_probs",
+                 "mpc_act", "mpc_status", "new_obs", "reward", "done", "terminal_obs", "truncated", "crashed", "arrived", "counts",
+                 "dones_out", "step_counter")
+        assert set(null) <= set(names)
+        return lib.mpc_rollout_record(0, T, B, A, cols, keep, *[None if n in null else p for n in names], None)
+    assert record(T=0) == -1 and b"mpc_rollout_record: bad size" in lib.mpc_last_error()
+    assert record(A=0, cols=84) == -1 and record(A=9, cols=93) == -1                                   # action_dim 1..8
+    assert record(cols=84) == -1 and record(cols=86) == -1                                             # row layout, keep_terminal 0
+    assert record(keep=1, cols=165) == -1 and record(keep=1, cols=167) == -1 and record(keep=1, cols=85) == -1   # ... and 1
+    for name in ("row", "pos_dev", "ticket", "counts"):
+        assert record(null=(name,)) == -1 and b"mpc_rollout_record: null pointer" in lib.mpc_last_error(), name
+    assert record(keep=1, cols=166, null=("terminal_obs",)) == -1 and record(keep=1, cols=166, null=("truncated",)) == -1
+    assert b"null pointer" in lib.mpc_last_error()
+    assert record(B=0) == 0 and record(B=0, keep=1, cols=166) == 0                                     # nothing to do: no device call
+    assert record(B=0, null=("terminal_obs", "truncated", "step_counter")) == 0                        # optional without keep_terminal
     assert lib.mpc_policy_act(0, 4, 0, 128, *([p] * 10), 0, 0, None, 0, 1, p, p, p, None, p, None) == -1   # action_dim 0
     assert lib.mpc_policy_act(0, 4, 3, 128, *([p] * 10), 0, 0, None, 1, 1, p, p, p, None, None, None) == -1  # v1 without weights out
     assert lib.mpc_streams_overlap(0, None, None, None) == -1                 # nowhere to put the answer
