@@ -69,7 +69,8 @@ MPC_HD double warm_clamp(double u, int i) {
 // |delta| <= pi/3(1+1e-8), slacks and determinants are positive normal numbers.
 MPC_HD double frcp(double x) {  // 1/x for positive normal x
 #if defined(__HIP_DEVICE_COMPILE__)
-    // v_rcp_f64 is good to 2^-24 (measured, tools/ubench/fp64_latency.hip): one third-order step gives 2^-72
+    // v_rcp_f64 is good to 2^-24 (measured, tools/ubench/fp64_latency.hip): one third-order step leaves 2^-72 before the final
+    // rounding: a bound of 0.5 + 2^-18 ulp on the error against 1/x, which tests/test_device_math_gpu.py holds the device to
     const double y = __builtin_amdgcn_rcp(x);
     const double e = fma(-x, y, 1.0);
     return fma(y, fma(e, e, e), y);
@@ -79,7 +80,10 @@ MPC_HD double frcp(double x) {  // 1/x for positive normal x
 }
 MPC_HD double frsqrt(double x) {  // 1/sqrt(x) for positive normal x
 #if defined(__HIP_DEVICE_COMPILE__)
-    // v_rsq_f64 is good to 2^-24 (measured): one third-order step gives 2^-72
+    // v_rsq_f64 is good to 2^-24 (measured): the third-order step's own remainder is 2^-72, but the product -x y is rounded
+    // before it enters e (2^-53 relative, half of which reaches the result), so the result is within 1 ulp of x^-1/2, not
+    // correctly rounded (up to 0.96 ulp in an exactly rounded restatement of these steps; tests/test_device_math_gpu.py holds the
+    // device to 1 + 2^-17 ulp)
     const double y = __builtin_amdgcn_rsq(x);
     const double e = fma(-x * y, y, 1.0);     // 1 - x y^2
     return fma(y * e, fma(0.375, e, 0.5), y);
@@ -87,30 +91,6 @@ MPC_HD double frsqrt(double x) {  // 1/sqrt(x) for positive normal x
     return 1.0 / sqrt(x);
 #endif
 }
-// sin and cos of |x| <= ~2 pi: two-constant Cody-Waite reduction to |r| <= pi/4, fdlibm kernel polynomials
-MPC_HD void sincos_b(double x, double &s, double &c) {
-    const double n = rint(x * 6.36619772367581382433e-01);  // x * 2/pi
-    double r = fma(-n, 1.57079632679489655800e+00, x);
-    r = fma(-n, 6.12323399573676603587e-17, r);
-    const double z = r * r;
-    const double ps = fma(z, fma(z, fma(z, fma(z, fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08),
-                                              2.75573137070700676789e-06),
-                                       -1.98412698298579493134e-04),
-                                8.33333333332248946124e-03),
-                         -1.66666666666666324348e-01);
-    const double sr = fma(z * r, ps, r);
-    const double pc = fma(z, fma(z, fma(z, fma(z, fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09),
-                                              -2.75573143513906633035e-07),
-                                       2.48015872894767294178e-05),
-                                -1.38888888888741095749e-03),
-                         4.16666666666666019037e-02);
-    const double cr = fma(z * z, pc, fma(-0.5, z, 1.0));
-    const int q = ((int)n) & 3;
-    const double sa = (q & 1) ? cr : sr, ca = (q & 1) ? sr : cr;
-    s = (q & 2) ? -sa : sa;
-    c = ((q + 1) & 2) ? -ca : ca;
-}
-
 // The twelve coefficients of the fdlibm sine / cosine kernels (valid on |x| <= pi/4).  The solver keeps them in a table
 // in LDS and loads them at the start of every phase that evaluates the dynamics: as 64-bit literals the compiler hoists
 // them out of the iteration loop into 24 vector registers for the whole solve - a seventh of the 128 registers a wave
@@ -132,7 +112,9 @@ MPC_HD double trig_coef(int i) {
 // |theta| <= pi (1 + 1e-8) (the bounds of the NLP), without range reduction or quadrant logic: the fdlibm kernel
 // polynomials (valid on |x| <= pi/4) are evaluated at delta/2 and theta/4 - four independent Horner chains that share
 // every coefficient, so a lone wave overlaps their latencies - followed by one resp. two angle doublings
-// (sin 2a = 2 sin a cos a, cos 2a = 1 - 2 sin^2 a; absolute error < 1e-15).
+// (sin 2a = 2 sin a cos a, cos 2a = 1 - 2 sin^2 a; each doubling roughly doubles the absolute error.  The host build measures
+// 2.0e-16 for delta and 1.1e-15 for theta, the worst near +-pi (tests/test_device_math_cpu.py); host and device builds are held
+// to 7e-16 resp. 3e-15 there and in tests/test_device_math_gpu.py).
 // Measured on MI355X: the generic two-argument version (reduction, quadrant selects on 64-bit values) was ~190
 // instructions of the ~330 of a rollout stage, this one is ~50.
 MPC_HD void sincos_delta_theta(const TrigCoef &K, double delta, double theta, double &sd, double &cd, double &st, double &ct) {

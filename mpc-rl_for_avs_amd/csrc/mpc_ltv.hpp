@@ -531,7 +531,8 @@ struct Solver {
         c.phase([&](int) {});
     }
 
-    // sincos_b of mpc_core.hpp with every 64-bit literal behind CTX::fresh: used twice per linearisation pass only, but as plain
+    // sin and cos of |x| <= ~2 pi (two-constant Cody-Waite reduction to |r| <= pi/4, fdlibm kernel polynomials) with every 64-bit
+    // literal behind CTX::fresh: used twice per linearisation pass only, but as plain
     // literals the fifteen constants are hoisted out of the pass loop and sit in thirty vector registers through every
     // iteration (the throughput build then spills)
     MPC_HD void sincos_f(double x, double &sn, double &cs) const {

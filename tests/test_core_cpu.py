@@ -1,7 +1,8 @@
 """The kernel's solver (mpc_wave.hpp: one wave per instance), compiled for the host, against the oracle (CPU only).  The
 64 lanes are emulated by loops over the phases, the matrix core, lane permutations and reductions by host models
-(tests/cpu_wave_harness.cpp).  Same arithmetic as the HIP kernel minus the lean device math (frcp/frsqrt use 1/x,
-1/sqrt)."""
+(tests/cpu_wave_harness.cpp; held to the device bit for bit, primitive by primitive, by tests/test_wave_ops_gpu.py).  Same
+arithmetic as the HIP kernel minus the four device-only branches of the lean math in mpc_core.hpp: on the host frcp is 1/x,
+frsqrt 1/sqrt, atan_b libm's atan and log_pos libm's log (the device branches: tests/test_device_math_gpu.py)."""
 import numpy as np
 import pytest
 
