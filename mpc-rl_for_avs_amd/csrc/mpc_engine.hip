@@ -27,8 +27,7 @@
 #include "mpc_wave_dev.hpp"
 #include "mpc_preamble.hpp"
 #include "mpc_preamble_wave.hpp"
-#include "mpc_synth_env.hpp"
-#include "mpc_synth_traffic.hpp"
+#include "mpc_synth_lanes.hpp"
 #include "mpc_rollout_glue.hpp"
 #include "mpc_drive_metrics.hpp"
 #include "mpc_perception.hpp"
@@ -444,54 +443,8 @@ __global__ void mpc_env_reset_kernel(int n, const int32_t *__restrict__ ids, con
 // synthetic intersection environment (mpc_synth_env.hpp): step + terminal observation + auto-reset + next observation in ONE
 // launch (the torch implementation of the same step is ~100 small kernels)
 // ---------------------------------------------------------------------------------------------------
-// SIXTEEN lanes per environment (round 5; four environments per wave): lane j of a group owns vehicle j
-// (model step, respawn draws, crash test, its row of the observation - its place among the rows by counting the vehicles that
-// are nearer, which is the stable insertion sort of env::observe), the 85 route points of the lane-centring term are scanned
-// 16 at a time with a min-reduction over the group (lowest index among equal distances, as the serial scan keeps the first),
-// what concerns the ego alone is computed by every lane of the group.  Statement by statement the arithmetic of
-// env::step_env (the host build of that function stays the reference of the tests); one thread per environment spent 30 us
-// per step on 256 environments - a chain of ~2000 dependent operations in 4 of the GPU's 1024 SIMDs.
-__device__ inline void synth_observe_rows(int q, int K, double x, double y, double th, double sp, double px, double py,
-                                          double ps, double ph, bool active, float *s_obs, float *out, bool live) {
-    namespace env = mpc::env;
-    for (int i = q; i < env::kRows * env::kCols; i += 16) s_obs[i] = 0.0f;
-    const double dx = px - x, dy = py - y;
-    const double d = active ? sqrt(dx * dx + dy * dy) : INFINITY;
-    int rank = 0;
-    for (int k = 0; k < K; ++k) {
-        const double dk = __shfl(d, k, 16);
-        const int ak = __shfl((int)active, k, 16);
-        rank += (ak && (dk < d || (dk == d && k < q))) ? 1 : 0;
-    }
-    __syncthreads();
-    if (q == 15) {
-        const double s = sin(th), c = cos(th);
-        s_obs[0] = 1.0f;
-        s_obs[1] = (float)x;
-        s_obs[2] = (float)y;
-        s_obs[3] = (float)(sp * c);
-        s_obs[4] = (float)(sp * s);
-        s_obs[5] = (float)th;
-        s_obs[6] = (float)s;
-        s_obs[7] = (float)c;
-    }
-    if (active) {
-        float *row = s_obs + (1 + rank) * env::kCols;
-        const double sh = sin(ph), ch = cos(ph);
-        row[0] = 1.0f;
-        row[1] = (float)px;
-        row[2] = (float)py;
-        row[3] = (float)(ps * ch);
-        row[4] = (float)(ps * sh);
-        row[5] = (float)ph;
-        row[6] = (float)sh;
-        row[7] = (float)ch;
-    }
-    __syncthreads();
-    if (live)
-        for (int i = q; i < env::kRows * env::kCols; i += 16) out[i] = s_obs[i];
-}
-
+// The lane-group pieces the two kernels share (who a lane is, route staging, nearest route point, observation, write-back)
+// are in mpc_synth_lanes.hpp; each kernel below reads top to bottom as the steps of its traffic model.
 __global__ __launch_bounds__(64) void mpc_synth_env_rows_kernel(
     int B, int K, double dt, double spawn_probability, uint64_t seed, int env_offset, const double *__restrict__ ref_xy,
     int M, const double *__restrict__ action, double *__restrict__ ego, double *__restrict__ opos,
@@ -501,151 +454,50 @@ __global__ __launch_bounds__(64) void mpc_synth_env_rows_kernel(
     uint8_t *__restrict__ arrived, int reset_all) {
     namespace env = mpc::env;
     constexpr int kObs = env::kRows * env::kCols;
-    __shared__ double s_ref[2 * 128];      // M <= 128 (the launch falls back to one thread per environment otherwise)
+    __shared__ double s_ref[2 * env::kMaxRoutePoints];
     __shared__ float s_obs[4][kObs];
-    for (int i = threadIdx.x; i < 2 * M; i += blockDim.x) s_ref[i] = ref_xy[i];
-    __syncthreads();
-    const int q = threadIdx.x & 15, g = threadIdx.x >> 4;
-    const int b_ = blockIdx.x * 4 + g;
-    const bool live = b_ < B;              // a group past the end computes on the last environment and writes nothing
-    const int b = live ? b_ : B - 1;
-    const int Ks = K > 0 ? K : 1;
-    const bool mine = q < K;
-    const int j = mine ? q : 0;
-    double *eg = ego + (size_t)b * 4;
-    const size_t vo = (size_t)b * Ks + j;
-    float *o = obs + (size_t)b * kObs;
-    const int64_t c0 = ctr[b];
-    const env::Rng r(seed, env_offset + b, c0);
+    env::stage_route(s_ref, ref_xy, M);
+    const env::LaneGroup G = env::lane_group(B, K, seed, env_offset, ctr);
+    const int q = G.q, j = G.j;
+    float *o = obs + (size_t)G.b * kObs;
+    double px = 0.0, py = 0.0, ps = 0.0, ph = 0.0;
     if (reset_all) {
-        double px = 0.0, py = 0.0, ps = 0.0, ph = 0.0;
-        if (mine) env::spawn_other(r, env::kSlotReset + 4 * j, 5.0, 60.0, px, py, ps, ph);
-        const double ex = 2.0, ey = 45.0 + (-5.0 + 10.0 * r.u01(env::kSlotEgo)), eth = -env::kPiE / 2, esp = 10.0;
-        synth_observe_rows(q, K, ex, ey, eth, esp, px, py, ps, ph, mine, s_obs[g], o, live);
-        if (live && mine) {
-            opos[2 * vo] = px;
-            opos[2 * vo + 1] = py;
-            ospeed[vo] = ps;
-            ohead[vo] = ph;
-            oactive[vo] = 1;
-        }
-        if (live && q == 0) {
-            eg[0] = ex; eg[1] = ey; eg[2] = eth; eg[3] = esp;
-            t[b] = 0;
-            ctr[b] = c0 + 1;
-        }
+        if (G.mine) env::spawn_other(G.r, env::kSlotReset + 4 * j, 5.0, 60.0, px, py, ps, ph);
+        const env::Ego e = env::fresh_ego(G.r);
+        env::synth_observe_rows(q, K, e, px, py, ps, ph, G.mine, s_obs[G.g], o, G.live);
+        env::store_state(G, e, px, py, ps, ph, G.mine, 0, ego, opos, ospeed, ohead, oactive, t, ctr);
         return;
     }
-    // ---- ego: the MPC's own vehicle model with the action limits of the environment
-    double a = action[(size_t)b * 2], delta = action[(size_t)b * 2 + 1];
-    a = a < -5.0 ? -5.0 : (a > 5.0 ? 5.0 : a);
-    delta = delta < -env::kPiE / 4 ? -env::kPiE / 4 : (delta > env::kPiE / 4 ? env::kPiE / 4 : delta);
-    const double x = eg[0], y = eg[1], th = eg[2], sp = eg[3];
-    const double beta = atan(0.5 * tan(delta));
-    double ex = x + sp * cos(th + beta) * dt;
-    double ey = y + sp * sin(th + beta) * dt;
-    double eth = th + sp / env::kWheelbase * sin(beta) * dt;
-    const double nv = sp + a * dt;
-    double esp = nv < 0.0 ? 0.0 : (nv > 30.0 ? 30.0 : nv);
+    // ---- ego
+    env::Ego e = env::step_ego(env::load_ego(ego + (size_t)G.b * 4), action + (size_t)G.b * 2, dt);
     // ---- vehicle j
-    double px = 0.0, py = 0.0, ps = 0.0, ph = 0.0;
     bool act = false, hit = false;
-    if (mine) {
-        px = opos[2 * vo]; py = opos[2 * vo + 1]; ps = ospeed[vo]; ph = ohead[vo];
-        act = oactive[vo] != 0;
-        px += ps * dt * cos(ph);
-        py += ps * dt * sin(ph);
-        const double ax = fabs(px), ay = fabs(py);
-        const bool gone = (ax > ay ? ax : ay) > 65.0 || !act;
-        if (gone) {
-            const bool respawn = r.u01(env::kSlotRespawn + 5 * j) < spawn_probability;
-            if (respawn) env::spawn_other(r, env::kSlotRespawn + 5 * j + 1, 40.0, 60.0, px, py, ps, ph);
-            act = respawn;
-        }
-        if (act) {
-            const double dx = px - ex, dy = py - ey;
-            hit = sqrt(dx * dx + dy * dy) < env::kCrashDistance;
-        }
+    if (G.mine) {
+        px = opos[2 * G.vo]; py = opos[2 * G.vo + 1]; ps = ospeed[G.vo]; ph = ohead[G.vo];
+        act = oactive[G.vo] != 0;
+        hit = env::step_other(G.r, j, dt, spawn_probability, e.x, e.y, px, py, ps, ph, act);
     }
-    const unsigned long long hits = __ballot(hit);
-    const bool crash = ((hits >> (16 * g)) & 0xffffull) != 0;
-    // ---- nearest route point: the first of the nearest, as the serial scan
-    double lateral = INFINITY;
-    int idx = 0;
-    for (int i = q; i < M; i += 16) {
-        const double dx = s_ref[2 * i] - ex, dy = s_ref[2 * i + 1] - ey;
-        const double d = sqrt(dx * dx + dy * dy);
-        if (d < lateral) {
-            lateral = d;
-            idx = i;
-        }
-    }
-    for (int off = 8; off >= 1; off >>= 1) {
-        const double od = __shfl_xor(lateral, off, 16);
-        const int oi = __shfl_xor(idx, off, 16);
-        const bool take = od < lateral || (od == lateral && oi < idx);
-        lateral = take ? od : lateral;
-        idx = take ? oi : idx;
-    }
-    const bool on_road = lateral <= env::kLaneHalfWidth;
-    const bool arr = idx >= M - 3 && on_road;
-    double cen = lateral / env::kLaneHalfWidth;
-    cen = 1.0 - (cen > 1.0 ? 1.0 : cen);
-    const double rew = env::kRewardCollision * (crash ? 1.0 : 0.0) + env::kRewardHighSpeed * (esp / 10.0) +
-                       env::kRewardArrived * (arr ? 1.0 : 0.0) + (on_road ? env::kRewardCenter * cen : env::kRewardOffRoad);
-    const int tn = t[b] + 1;
-    const bool terminated = crash || arr;
-    const bool trunc = tn >= env::kEpisodeSteps && !terminated;
-    const bool fin = terminated || trunc;
-    synth_observe_rows(q, K, ex, ey, eth, esp, px, py, ps, ph, act, s_obs[g], terminal_obs + (size_t)b * kObs, live);
-    if (fin) {      // uniform over the group
-        ex = 2.0;
-        ey = 45.0 + (-5.0 + 10.0 * r.u01(env::kSlotEgo));
-        eth = -env::kPiE / 2;
-        esp = 10.0;
-        if (mine) env::spawn_other(r, env::kSlotReset + 4 * j, 5.0, 60.0, px, py, ps, ph);
-        act = mine;
+    const bool crash = env::group_any(hit, G.g);
+    // ---- reward and termination
+    const env::Nearest n = env::group_nearest_route_point(s_ref, M, q, e.x, e.y);
+    const int tn = t[G.b] + 1;
+    const env::StepOut so = env::score_step(n.d, n.idx, M, crash, e.sp, tn);
+    env::synth_observe_rows(q, K, e, px, py, ps, ph, act, s_obs[G.g], terminal_obs + (size_t)G.b * kObs, G.live);
+    if (so.done) {      // uniform over the group
+        e = env::fresh_ego(G.r);
+        if (G.mine) env::spawn_other(G.r, env::kSlotReset + 4 * j, 5.0, 60.0, px, py, ps, ph);
+        act = G.mine;
     }
     // (a group that goes on rebuilds the same observation: the four groups of a wave stay in step for the barriers inside)
-    synth_observe_rows(q, K, ex, ey, eth, esp, px, py, ps, ph, act, s_obs[g], o, live);
-    if (live && mine) {
-        opos[2 * vo] = px;
-        opos[2 * vo + 1] = py;
-        ospeed[vo] = ps;
-        ohead[vo] = ph;
-        oactive[vo] = act ? 1 : 0;
-    }
-    if (live && q == 0) {
-        eg[0] = ex; eg[1] = ey; eg[2] = eth; eg[3] = esp;
-        t[b] = fin ? 0 : tn;
-        ctr[b] = c0 + 1;
-        reward[b] = (float)rew;
-        done[b] = fin;
-        truncated[b] = trunc;
-        crashed[b] = crash;
-        arrived[b] = arr;
-    }
+    env::synth_observe_rows(q, K, e, px, py, ps, ph, act, s_obs[G.g], o, G.live);
+    env::store_state(G, e, px, py, ps, ph, act, so.done ? 0 : tn, ego, opos, ospeed, ohead, oactive, t, ctr);
+    env::store_outputs(G, so, reward, done, truncated, crashed, arrived);
 }
 
-// ---- the same step with reactive traffic (mpc_synth_traffic.hpp; traffic = "idm").  A kernel of its own, so that the
-// constant-velocity kernel above stays the code it was, with the same mapping: lane j of a 16-lane group owns vehicle j.  Its
-// corridor scan and the spawn rule are loops over k < K of group shuffles of what lane k holds, the shape of the rank count in
-// synth_observe_rows; every shuffle sits in control flow that is uniform over the wave (a lane without a vehicle, or a group
-// whose episode goes on, computes along and discards), and all four groups reach every barrier.
-//
-// spawn rule for lane q from what lane k offers (its position, whether it stays, whether it was drawn this step)
-__device__ inline bool synth_spawn_clear(int q, int K, double cx, double cy, double sx, double sy, bool stays, bool drew) {
-    namespace env = mpc::env;
-    bool clear = true;
-    for (int k = 0; k < K; ++k) {
-        const double kx = __shfl(sx, k, 16), ky = __shfl(sy, k, 16);
-        const int kst = __shfl((int)stays, k, 16), kdr = __shfl((int)drew, k, 16);
-        const bool blocks = k != q && (kst || (k < q && kdr)) && env::too_close(cx, cy, kx, ky);
-        clear = clear && !blocks;
-    }
-    return clear;
-}
-
+// ---- the same step with reactive traffic (mpc_synth_traffic.hpp; traffic = "idm"), with the same mapping: lane j of a 16-lane
+// group owns vehicle j.  Its corridor scan and the spawn rule are loops over k < K of group shuffles of what lane k holds, the
+// shape of the rank count in synth_observe_rows; every shuffle sits in control flow that is uniform over the wave (a lane
+// without a vehicle, or a group whose episode goes on, computes along and discards), and all four groups reach every barrier.
 __global__ __launch_bounds__(64) void mpc_synth_env_idm_kernel(
     int B, int K, double dt, double spawn_probability, uint64_t seed, int env_offset, const double *__restrict__ ref_xy,
     int M, const double *__restrict__ action, double *__restrict__ ego, double *__restrict__ opos,
@@ -655,57 +507,39 @@ __global__ __launch_bounds__(64) void mpc_synth_env_idm_kernel(
     uint8_t *__restrict__ truncated, uint8_t *__restrict__ crashed, uint8_t *__restrict__ arrived, int reset_all) {
     namespace env = mpc::env;
     constexpr int kObs = env::kRows * env::kCols;
-    __shared__ double s_ref[2 * 128];
+    __shared__ double s_ref[2 * env::kMaxRoutePoints];
     __shared__ float s_obs[4][kObs];
-    for (int i = threadIdx.x; i < 2 * M; i += blockDim.x) s_ref[i] = ref_xy[i];
-    __syncthreads();
-    const int q = threadIdx.x & 15, g = threadIdx.x >> 4;
-    const int b_ = blockIdx.x * 4 + g;
-    const bool live = b_ < B;              // a group past the end computes on the last environment and writes nothing
-    const int b = live ? b_ : B - 1;
-    const int Ks = K > 0 ? K : 1;
-    const bool mine = q < K;
-    const int j = mine ? q : 0;
-    double *eg = ego + (size_t)b * 4;
-    const size_t vo = (size_t)b * Ks + j;
-    float *o = obs + (size_t)b * kObs;
-    const int64_t c0 = ctr[b];
-    const env::Rng r(seed, env_offset + b, c0);
+    env::stage_route(s_ref, ref_xy, M);
+    const env::LaneGroup G = env::lane_group(B, K, seed, env_offset, ctr);
+    const int q = G.q, j = G.j;
+    const size_t vo = G.vo;
     double px = 0.0, py = 0.0, ps = 0.0, ph = 0.0, prog = 0.0, target = 1.0;
     int route = 0;
     bool act = false;
-    double ex = 0.0, ey = 0.0, eth = 0.0, esp = 0.0;
-    float rew = 0.0f;
-    bool fin = true, trunc = false, crash = false, arr = false;
+    env::Ego e = {};
+    env::StepOut so = {};
+    so.done = 1;        // a reset launch: every episode starts afresh
     int tn = 0;
     if (!reset_all) {
-        // ---- ego: the MPC's own vehicle model with the action limits of the environment
-        double a = action[(size_t)b * 2], delta = action[(size_t)b * 2 + 1];
-        a = a < -5.0 ? -5.0 : (a > 5.0 ? 5.0 : a);
-        delta = delta < -env::kPiE / 4 ? -env::kPiE / 4 : (delta > env::kPiE / 4 ? env::kPiE / 4 : delta);
-        const double x = eg[0], y = eg[1], th = eg[2], sp = eg[3];
-        const double beta = atan(0.5 * tan(delta));
-        ex = x + sp * cos(th + beta) * dt;
-        ey = y + sp * sin(th + beta) * dt;
-        eth = th + sp / env::kWheelbase * sin(beta) * dt;
-        const double nv = sp + a * dt;
-        esp = nv < 0.0 ? 0.0 : (nv > 30.0 ? 30.0 : nv);
+        // ---- ego
+        const env::Ego e0 = env::load_ego(ego + (size_t)G.b * 4);
+        e = env::step_ego(e0, action + (size_t)G.b * 2, dt);
         // ---- vehicle j: its leader among the ego and the others as they were before the step
-        if (mine) {
+        if (G.mine) {
             px = opos[2 * vo]; py = opos[2 * vo + 1]; ps = ospeed[vo]; ph = ohead[vo];
             act = oactive[vo] != 0;
             route = oroute[vo]; prog = oprog[vo]; target = otarget[vo];
         }
         const double cj = cos(ph), sj = sin(ph);
         env::Leader lead = env::no_leader();
-        env::offer_leader(lead, q, px, py, ph, cj, sj, -1, x, y, th, sp);
+        env::offer_leader(lead, q, px, py, ph, cj, sj, -1, e0.x, e0.y, e0.th, e0.sp);
         for (int k = 0; k < K; ++k) {
             const double kx = __shfl(px, k, 16), ky = __shfl(py, k, 16), kh = __shfl(ph, k, 16), kv = __shfl(ps, k, 16);
             const int ka = __shfl((int)act, k, 16);
             if (k != q && ka) env::offer_leader(lead, q, px, py, ph, cj, sj, k, kx, ky, kh, kv);
         }
         // a circle of vehicles waiting for each other: its lowest index drives free (env::walk_leaders)
-        const int who = mine && act ? lead.who : -2;
+        const int who = G.mine && act ? lead.who : -2;
         int wp = who, lowest = q;
         bool closed = false;
         for (int n = 0; n < K; ++n) {
@@ -713,22 +547,22 @@ __global__ __launch_bounds__(64) void mpc_synth_env_idm_kernel(
             env::walk_leaders(q, wp >= 0 ? next : -2, wp, lowest, closed);
         }
         if (closed && lowest == q) lead = env::no_leader();
+        // ---- it moves; one that left (or was away) draws its respawn and is placed where the spawn rule allows
         bool stays = false, drew = false;
         env::Drawn cand = {};
-        if (mine) {
+        if (G.mine) {
             if (act) {
                 const double acc = env::idm_acceleration(ps, target, ph, lead);
                 env::advance(acc, dt, prog, ps);
                 env::pose(route, prog, px, py, ph);
-                const double ax = fabs(px), ay = fabs(py);
-                stays = !((ax > ay ? ax : ay) > 65.0);
+                stays = !env::left_the_map(px, py);
             }
-            drew = !stays && r.u01(env::kSlotRespawn + 5 * j) < spawn_probability;
-            if (drew) cand = env::draw_vehicle(r, env::kSlotRespawn + 5 * j + 1, env::kSlotTurnRespawn + j, 40.0, 60.0);
+            drew = !stays && G.r.u01(env::kSlotRespawn + 5 * j) < spawn_probability;
+            if (drew) cand = env::draw_vehicle(G.r, env::kSlotRespawn + 5 * j + 1, env::kSlotTurnRespawn + j, 40.0, 60.0);
         }
-        const bool clear = synth_spawn_clear(q, K, cand.x, cand.y, stays ? px : cand.x, stays ? py : cand.y, stays, drew);
+        const bool clear = env::synth_spawn_clear(q, K, cand.x, cand.y, stays ? px : cand.x, stays ? py : cand.y, stays, drew);
         bool hit = false;
-        if (mine) {
+        if (G.mine) {
             if (!stays) {
                 act = drew && clear;
                 if (act) {
@@ -736,82 +570,37 @@ __global__ __launch_bounds__(64) void mpc_synth_env_idm_kernel(
                     route = cand.route; prog = cand.s; target = cand.target;
                 }
             }
-            if (act) {
-                const double dx = px - ex, dy = py - ey;
-                hit = sqrt(dx * dx + dy * dy) < env::kCrashDistance;
-            }
+            hit = act && env::hits_ego(px, py, e.x, e.y);
         }
-        const unsigned long long hits = __ballot(hit);
-        crash = ((hits >> (16 * g)) & 0xffffull) != 0;
-        // ---- nearest route point: the first of the nearest, as the serial scan
-        double lateral = INFINITY;
-        int idx = 0;
-        for (int i = q; i < M; i += 16) {
-            const double dx = s_ref[2 * i] - ex, dy = s_ref[2 * i + 1] - ey;
-            const double d = sqrt(dx * dx + dy * dy);
-            if (d < lateral) {
-                lateral = d;
-                idx = i;
-            }
-        }
-        for (int off = 8; off >= 1; off >>= 1) {
-            const double od = __shfl_xor(lateral, off, 16);
-            const int oi = __shfl_xor(idx, off, 16);
-            const bool take = od < lateral || (od == lateral && oi < idx);
-            lateral = take ? od : lateral;
-            idx = take ? oi : idx;
-        }
-        const bool on_road = lateral <= env::kLaneHalfWidth;
-        arr = idx >= M - 3 && on_road;
-        double cen = lateral / env::kLaneHalfWidth;
-        cen = 1.0 - (cen > 1.0 ? 1.0 : cen);
-        rew = (float)(env::kRewardCollision * (crash ? 1.0 : 0.0) + env::kRewardHighSpeed * (esp / 10.0) +
-                      env::kRewardArrived * (arr ? 1.0 : 0.0) + (on_road ? env::kRewardCenter * cen : env::kRewardOffRoad));
-        tn = t[b] + 1;
-        const bool terminated = crash || arr;
-        trunc = tn >= env::kEpisodeSteps && !terminated;
-        fin = terminated || trunc;
-        synth_observe_rows(q, K, ex, ey, eth, esp, px, py, ps, ph, act, s_obs[g], terminal_obs + (size_t)b * kObs, live);
+        const bool crash = env::group_any(hit, G.g);
+        // ---- reward and termination
+        const env::Nearest n = env::group_nearest_route_point(s_ref, M, q, e.x, e.y);
+        tn = t[G.b] + 1;
+        so = env::score_step(n.d, n.idx, M, crash, e.sp, tn);
+        env::synth_observe_rows(q, K, e, px, py, ps, ph, act, s_obs[G.g], terminal_obs + (size_t)G.b * kObs, G.live);
     }
     // ---- fresh episode (every group of a reset launch, the groups whose episode ended otherwise; uniform over a group)
+    const bool fin = so.done;
     env::Drawn fresh = {};
-    if (fin && mine) fresh = env::draw_vehicle(r, env::kSlotReset + 4 * j, env::kSlotTurnReset + j, 5.0, 60.0);
-    const bool placed = synth_spawn_clear(q, K, fresh.x, fresh.y, fresh.x, fresh.y, false, fin && mine);
+    if (fin && G.mine) fresh = env::draw_vehicle(G.r, env::kSlotReset + 4 * j, env::kSlotTurnReset + j, 5.0, 60.0);
+    const bool placed = env::synth_spawn_clear(q, K, fresh.x, fresh.y, fresh.x, fresh.y, false, fin && G.mine);
     if (fin) {
-        ex = 2.0;
-        ey = 45.0 + (-5.0 + 10.0 * r.u01(env::kSlotEgo));
-        eth = -env::kPiE / 2;
-        esp = 10.0;
-        if (mine) {
+        e = env::fresh_ego(G.r);
+        if (G.mine) {
             px = fresh.x; py = fresh.y; ps = fresh.speed; ph = fresh.h;
             route = fresh.route; prog = fresh.s; target = fresh.target;
             act = placed;
         }
     }
     // (a group that goes on rebuilds the same observation: the four groups of a wave stay in step for the barriers inside)
-    synth_observe_rows(q, K, ex, ey, eth, esp, px, py, ps, ph, act, s_obs[g], o, live);
-    if (live && mine) {
-        opos[2 * vo] = px;
-        opos[2 * vo + 1] = py;
-        ospeed[vo] = ps;
-        ohead[vo] = ph;
-        oactive[vo] = act ? 1 : 0;
+    env::synth_observe_rows(q, K, e, px, py, ps, ph, act, s_obs[G.g], obs + (size_t)G.b * kObs, G.live);
+    env::store_state(G, e, px, py, ps, ph, act, fin ? 0 : tn, ego, opos, ospeed, ohead, oactive, t, ctr);
+    if (G.live && G.mine) {
         oroute[vo] = route;
         oprog[vo] = prog;
         otarget[vo] = target;
     }
-    if (live && q == 0) {
-        eg[0] = ex; eg[1] = ey; eg[2] = eth; eg[3] = esp;
-        t[b] = fin ? 0 : tn;
-        ctr[b] = c0 + 1;
-        if (!reset_all) {
-            reward[b] = rew;
-            done[b] = fin;
-            truncated[b] = trunc;
-            crashed[b] = crash;
-            arrived[b] = arr;
-        }
-    }
+    if (!reset_all) env::store_outputs(G, so, reward, done, truncated, crashed, arrived);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1822,24 +1611,32 @@ int mpc_streams_overlap(int32_t device, void *stream_a, void *stream_b, int32_t 
     return MPC_OK;
 }
 
+// argument checks and launch geometry of the two entry points of the synthetic environment: sixteen lanes per environment,
+// four environments per block; *blocks = 0 where there is nothing to launch
+static int synth_env_launch_shape(const std::string &who, int32_t device, int32_t B, int32_t K, double dt, int32_t M,
+                                  bool state_ok, bool outputs_ok, unsigned *blocks) {
+    *blocks = 0;
+    if (B < 0 || K < 0 || K > mpc::env::kMaxOthers || !(dt > 0.0) || M < 1) return fail(MPC_ERR_INVALID_ARG, who + ": bad size");
+    if (!state_ok) return fail(MPC_ERR_INVALID_ARG, who + ": null state pointer");
+    if (!outputs_ok) return fail(MPC_ERR_INVALID_ARG, who + ": null output pointer");
+    if (B == 0) return MPC_OK;
+    HIP_TRY(hipSetDevice(device));
+    if (M > mpc::env::kMaxRoutePoints) return fail(MPC_ERR_INVALID_ARG, who + ": at most 15 other vehicles and 128 route points");
+    *blocks = (unsigned)((B + 3) / 4);
+    return MPC_OK;
+}
+
 int mpc_synth_env_step(int32_t device, int32_t B, int32_t K, double dt, double spawn_probability, uint64_t seed,
                        int32_t env_offset, const double *ref_xy, int32_t M, const double *action, double *ego, double *opos,
                        double *ospeed, double *ohead, uint8_t *oactive, int32_t *t, int64_t *rng_counter, float *obs,
                        float *terminal_obs, float *reward, uint8_t *done, uint8_t *truncated, uint8_t *crashed,
                        uint8_t *arrived, int32_t reset_all, void *stream_) {
-    if (B < 0 || K < 0 || K > mpc::env::kMaxOthers || !(dt > 0.0) || M < 1)
-        return fail(MPC_ERR_INVALID_ARG, "mpc_synth_env_step: bad size");
-    if (!ref_xy || !ego || !opos || !ospeed || !ohead || !oactive || !t || !rng_counter || !obs)
-        return fail(MPC_ERR_INVALID_ARG, "mpc_synth_env_step: null state pointer");
-    if (!reset_all && (!action || !terminal_obs || !reward || !done || !truncated || !crashed || !arrived))
-        return fail(MPC_ERR_INVALID_ARG, "mpc_synth_env_step: null output pointer");
-    if (B == 0) return MPC_OK;
-    HIP_TRY(hipSetDevice(device));
-    // sixteen lanes per environment (mpc_synth_env_rows_kernel); the one-thread-per-environment kernel it replaced in round 5 is
-    // gone (round 6) - its statement env::step_env stays as the host-side reference of the tests
-    if (K > 15 || M > 128)
-        return fail(MPC_ERR_INVALID_ARG, "mpc_synth_env_step: at most 15 other vehicles and 128 route points");
-    hipLaunchKernelGGL(mpc_synth_env_rows_kernel, dim3((unsigned)((B + 3) / 4)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream_),
+    unsigned blocks;
+    const int rc = synth_env_launch_shape(
+        "mpc_synth_env_step", device, B, K, dt, M, ref_xy && ego && opos && ospeed && ohead && oactive && t && rng_counter && obs,
+        reset_all || (action && terminal_obs && reward && done && truncated && crashed && arrived), &blocks);
+    if (rc || !blocks) return rc;
+    hipLaunchKernelGGL(mpc_synth_env_rows_kernel, dim3(blocks), dim3(64), 0, reinterpret_cast<hipStream_t>(stream_),
                        (int)B, (int)K, dt, spawn_probability, seed, (int)env_offset, ref_xy, (int)M, action, ego, opos, ospeed,
                        ohead, oactive, t, rng_counter, obs, terminal_obs, reward, done, truncated, crashed, arrived,
                        (int)reset_all);
@@ -1852,17 +1649,13 @@ int mpc_synth_env_step_idm(int32_t device, int32_t B, int32_t K, double dt, doub
                            double *ospeed, double *ohead, uint8_t *oactive, int32_t *oroute, double *oprog, double *otarget,
                            int32_t *t, int64_t *rng_counter, float *obs, float *terminal_obs, float *reward, uint8_t *done,
                            uint8_t *truncated, uint8_t *crashed, uint8_t *arrived, int32_t reset_all, void *stream_) {
-    if (B < 0 || K < 0 || K > mpc::env::kMaxOthers || !(dt > 0.0) || M < 1)
-        return fail(MPC_ERR_INVALID_ARG, "mpc_synth_env_step_idm: bad size");
-    if (!ref_xy || !ego || !opos || !ospeed || !ohead || !oactive || !oroute || !oprog || !otarget || !t || !rng_counter || !obs)
-        return fail(MPC_ERR_INVALID_ARG, "mpc_synth_env_step_idm: null state pointer");
-    if (!reset_all && (!action || !terminal_obs || !reward || !done || !truncated || !crashed || !arrived))
-        return fail(MPC_ERR_INVALID_ARG, "mpc_synth_env_step_idm: null output pointer");
-    if (B == 0) return MPC_OK;
-    HIP_TRY(hipSetDevice(device));
-    if (K > 15 || M > 128)
-        return fail(MPC_ERR_INVALID_ARG, "mpc_synth_env_step_idm: at most 15 other vehicles and 128 route points");
-    hipLaunchKernelGGL(mpc_synth_env_idm_kernel, dim3((unsigned)((B + 3) / 4)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream_),
+    unsigned blocks;
+    const int rc = synth_env_launch_shape(
+        "mpc_synth_env_step_idm", device, B, K, dt, M,
+        ref_xy && ego && opos && ospeed && ohead && oactive && oroute && oprog && otarget && t && rng_counter && obs,
+        reset_all || (action && terminal_obs && reward && done && truncated && crashed && arrived), &blocks);
+    if (rc || !blocks) return rc;
+    hipLaunchKernelGGL(mpc_synth_env_idm_kernel, dim3(blocks), dim3(64), 0, reinterpret_cast<hipStream_t>(stream_),
                        (int)B, (int)K, dt, spawn_probability, seed, (int)env_offset, ref_xy, (int)M, action, ego, opos, ospeed,
                        ohead, oactive, oroute, oprog, otarget, t, rng_counter, obs, terminal_obs, reward, done, truncated,
                        crashed, arrived, (int)reset_all);

@@ -1,6 +1,7 @@
 // mpc_synth_env.hpp - one step of the synthetic intersection environment for ONE environment (SURVEY section 8 f-1:
-// "env step as a HIP/torch kernel"), written once for device and host (MPC_HD): the kernel in mpc_engine.hip runs one
-// thread per environment, tests/cpu_synth_env_harness.cpp loops over environments.
+// "env step as a HIP/torch kernel"), written once for device and host (MPC_HD).  step_env at the end is the step as a serial
+// statement, which tests/cpu_synth_env_harness.cpp loops over environments; the kernel in mpc_engine.hip runs lane j of a
+// 16-lane group as vehicle j (mpc_synth_lanes.hpp) and calls the same pieces: step_ego, step_other, score_step, fresh_ego.
 //
 // It is the fused counterpart of rollout.SyntheticIntersectionEnv's torch implementation (step + observe + auto-reset +
 // observe, ~100 small torch kernels per step) and follows it statement by statement:
@@ -77,11 +78,36 @@ MPC_HD void spawn_other(const Rng &r, int s, double dlo, double dhi, double &x, 
 // draw slots of one step: 5 j .. 5 j + 4 respawn decision and vehicle j (j < 9), 64 ego spawn, 80 + 4 j .. reset vehicle j
 constexpr int kSlotRespawn = 0, kSlotEgo = 64, kSlotReset = 80;
 
+struct Ego {
+    double x, y, th, sp;
+};
+MPC_HD Ego load_ego(const double *p) {
+    Ego e;
+    e.x = p[0];
+    e.y = p[1];
+    e.th = p[2];
+    e.sp = p[3];
+    return e;
+}
+MPC_HD void store_ego(double *p, const Ego &e) {
+    p[0] = e.x;
+    p[1] = e.y;
+    p[2] = e.th;
+    p[3] = e.sp;
+}
+
+// the ego of a fresh episode
+MPC_HD Ego fresh_ego(const Rng &r) {
+    Ego e;
+    e.x = 2.0;
+    e.y = 45.0 + (-5.0 + 10.0 * r.u01(kSlotEgo));   // envs/intersection_env_Feb2025_v1.py:397-410
+    e.th = -kPiE / 2;
+    e.sp = 10.0;
+    return e;
+}
+
 MPC_HD void reset_env(const View &v, int K, const Rng &r) {
-    v.ego[0] = 2.0;
-    v.ego[1] = 45.0 + (-5.0 + 10.0 * r.u01(kSlotEgo));   // envs/intersection_env_Feb2025_v1.py:397-410
-    v.ego[2] = -kPiE / 2;
-    v.ego[3] = 10.0;
+    store_ego(v.ego, fresh_ego(r));
     for (int j = 0; j < K; ++j) {
         double x, y, sp, h;
         spawn_other(r, kSlotReset + 4 * j, 5.0, 60.0, x, y, sp, h);
@@ -138,84 +164,121 @@ MPC_HD void observe(const View &v, int K, float *obs) {
     }
 }
 
+// the ego's step: the MPC's own vehicle model with the action limits of the environment; action = (acceleration m/s^2,
+// steering angle rad) as the RL wrappers hand it to env.step (agents/ppo_mpc.py:430-432)
+MPC_HD Ego step_ego(const Ego &e, const double *action, double dt) {
+    double a = action[0], delta = action[1];
+    a = a < -5.0 ? -5.0 : (a > 5.0 ? 5.0 : a);                                              // config/config.py:31
+    delta = delta < -kPiE / 4 ? -kPiE / 4 : (delta > kPiE / 4 ? kPiE / 4 : delta);          // config/config.py:30
+    const double x = e.x, y = e.y, th = e.th, sp = e.sp;
+    const double beta = atan(0.5 * tan(delta));
+    Ego n;
+    n.x = x + sp * cos(th + beta) * dt;
+    n.y = y + sp * sin(th + beta) * dt;
+    n.th = th + sp / kWheelbase * sin(beta) * dt;
+    const double nv = sp + a * dt;
+    n.sp = nv < 0.0 ? 0.0 : (nv > 30.0 ? 30.0 : nv);
+    return n;
+}
+
+// a vehicle past the end of its lane
+MPC_HD bool left_the_map(double px, double py) {
+    const double ax = fabs(px), ay = fabs(py);
+    return (ax > ay ? ax : ay) > 65.0;
+}
+
+// the crash test of an active vehicle at (px, py) against the ego at (ex, ey)
+MPC_HD bool hits_ego(double px, double py, double ex, double ey) {
+    const double dx = px - ex, dy = py - ey;
+    return sqrt(dx * dx + dy * dy) < kCrashDistance;
+}
+
+// constant-velocity vehicle j: it moves, draws its respawn where it left or was away, and is tested against the ego after
+// the ego's step; returns whether it hit
+MPC_HD bool step_other(const Rng &r, int j, double dt, double spawn_probability, double ex, double ey, double &px, double &py,
+                       double &ps, double &ph, bool &act) {
+    px += ps * dt * cos(ph);
+    py += ps * dt * sin(ph);
+    const bool gone = left_the_map(px, py) || !act;
+    if (gone) {
+        const bool respawn = r.u01(kSlotRespawn + 5 * j) < spawn_probability;
+        if (respawn) spawn_other(r, kSlotRespawn + 5 * j + 1, 40.0, 60.0, px, py, ps, ph);
+        act = respawn;
+    }
+    return act && hits_ego(px, py, ex, ey);
+}
+
+// nearest of the route points first, first + stride, ..: the first of the nearest
+struct Nearest {
+    double d;
+    int idx;
+};
+MPC_HD Nearest nearest_route_point(const double *ref_xy, int M, int first, int stride, double ex, double ey) {
+    Nearest n;
+    n.d = INFINITY;
+    n.idx = 0;
+    for (int i = first; i < M; i += stride) {
+        const double dx = ref_xy[2 * i] - ex, dy = ref_xy[2 * i + 1] - ey;
+        const double d = sqrt(dx * dx + dy * dy);
+        if (d < n.d) {
+            n.d = d;
+            n.idx = i;
+        }
+    }
+    return n;
+}
+
 struct StepOut {
     float reward;
     uint8_t done, truncated, crashed, arrived;
 };
 
-// one policy step: action = (acceleration m/s^2, steering angle rad) as the RL wrappers hand it to env.step
-// (agents/ppo_mpc.py:430-432).  Writes the terminal observation, auto-resets a finished episode and writes the observation
-// the policy sees next.
-MPC_HD StepOut step_env(const View &v, int K, double dt, double spawn_probability, uint64_t seed, int env_id,
-                        const double *ref_xy, int M, const double *action, float *terminal_obs, float *obs) {
-    const Rng r(seed, env_id, *v.ctr);
-    *v.ctr += 1;
-    double a = action[0], delta = action[1];
-    a = a < -5.0 ? -5.0 : (a > 5.0 ? 5.0 : a);                                              // config/config.py:31
-    delta = delta < -kPiE / 4 ? -kPiE / 4 : (delta > kPiE / 4 ? kPiE / 4 : delta);          // config/config.py:30
-    const double x = v.ego[0], y = v.ego[1], th = v.ego[2], sp = v.ego[3];
-    const double beta = atan(0.5 * tan(delta));
-    v.ego[0] = x + sp * cos(th + beta) * dt;
-    v.ego[1] = y + sp * sin(th + beta) * dt;
-    v.ego[2] = th + sp / kWheelbase * sin(beta) * dt;
-    double nv = sp + a * dt;
-    v.ego[3] = nv < 0.0 ? 0.0 : (nv > 30.0 ? 30.0 : nv);
-    bool crashed = false;
-    for (int j = 0; j < K; ++j) {
-        v.opos[2 * j] += v.ospeed[j] * dt * cos(v.ohead[j]);
-        v.opos[2 * j + 1] += v.ospeed[j] * dt * sin(v.ohead[j]);
-        const double ax = fabs(v.opos[2 * j]), ay = fabs(v.opos[2 * j + 1]);
-        const bool gone = (ax > ay ? ax : ay) > 65.0 || !v.oactive[j];
-        if (gone) {
-            const bool respawn = r.u01(kSlotRespawn + 5 * j) < spawn_probability;
-            if (respawn) {
-                double px, py, ps, ph;
-                spawn_other(r, kSlotRespawn + 5 * j + 1, 40.0, 60.0, px, py, ps, ph);
-                v.opos[2 * j] = px;
-                v.opos[2 * j + 1] = py;
-                v.ospeed[j] = ps;
-                v.ohead[j] = ph;
-            }
-            v.oactive[j] = respawn ? 1 : 0;
-        }
-        if (v.oactive[j]) {
-            const double dx = v.opos[2 * j] - v.ego[0], dy = v.opos[2 * j + 1] - v.ego[1];
-            crashed = crashed || sqrt(dx * dx + dy * dy) < kCrashDistance;
-        }
-    }
-    double lateral = INFINITY;
-    int idx = 0;
-    for (int i = 0; i < M; ++i) {
-        const double dx = ref_xy[2 * i] - v.ego[0], dy = ref_xy[2 * i + 1] - v.ego[1];
-        const double d = sqrt(dx * dx + dy * dy);
-        if (d < lateral) {
-            lateral = d;
-            idx = i;
-        }
-    }
+// reward and termination from the nearest route point (distance `lateral`, index `idx` of M), the crash flag, the ego's
+// speed and the episode's step count, all after the step
+MPC_HD StepOut score_step(double lateral, int idx, int M, bool crashed, double speed, int t) {
     const bool on_road = lateral <= kLaneHalfWidth;
     const bool arrived = idx >= M - 3 && on_road;
     double cen = lateral / kLaneHalfWidth;
     cen = 1.0 - (cen > 1.0 ? 1.0 : cen);
-    const double reward = kRewardCollision * (crashed ? 1.0 : 0.0) + kRewardHighSpeed * (v.ego[3] / 10.0) +
+    const double reward = kRewardCollision * (crashed ? 1.0 : 0.0) + kRewardHighSpeed * (speed / 10.0) +
                           kRewardArrived * (arrived ? 1.0 : 0.0) + (on_road ? kRewardCenter * cen : kRewardOffRoad);
-    *v.t += 1;
     const bool terminated = crashed || arrived;
-    const bool truncated = *v.t >= kEpisodeSteps && !terminated;
-    const bool done = terminated || truncated;
+    const bool truncated = t >= kEpisodeSteps && !terminated;
+    StepOut o;
+    o.reward = (float)reward;
+    o.done = terminated || truncated;
+    o.truncated = truncated;
+    o.crashed = crashed;
+    o.arrived = arrived;
+    return o;
+}
+
+// one policy step.  Writes the terminal observation, auto-resets a finished episode and writes the observation the policy
+// sees next.
+MPC_HD StepOut step_env(const View &v, int K, double dt, double spawn_probability, uint64_t seed, int env_id,
+                        const double *ref_xy, int M, const double *action, float *terminal_obs, float *obs) {
+    const Rng r(seed, env_id, *v.ctr);
+    *v.ctr += 1;
+    const Ego e = step_ego(load_ego(v.ego), action, dt);
+    store_ego(v.ego, e);
+    bool crashed = false;
+    for (int j = 0; j < K; ++j) {
+        bool act = v.oactive[j] != 0;
+        const bool hit = step_other(r, j, dt, spawn_probability, e.x, e.y, v.opos[2 * j], v.opos[2 * j + 1], v.ospeed[j],
+                                    v.ohead[j], act);
+        v.oactive[j] = act ? 1 : 0;
+        crashed = crashed || hit;
+    }
+    const Nearest n = nearest_route_point(ref_xy, M, 0, 1, e.x, e.y);
+    *v.t += 1;
+    const StepOut o = score_step(n.d, n.idx, M, crashed, e.sp, *v.t);
     observe(v, K, terminal_obs);
-    if (done) {
+    if (o.done) {
         reset_env(v, K, r);
         observe(v, K, obs);
     } else {
         for (int i = 0; i < kRows * kCols; ++i) obs[i] = terminal_obs[i];
     }
-    StepOut o;
-    o.reward = (float)reward;
-    o.done = done;
-    o.truncated = truncated;
-    o.crashed = crashed;
-    o.arrived = arrived;
     return o;
 }
 

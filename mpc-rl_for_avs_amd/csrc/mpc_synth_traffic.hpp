@@ -215,10 +215,7 @@ struct TrafficView {
 // fresh episode: the ego as env::reset_env draws it; vehicle j is placed unless a lower-index vehicle was drawn within 10 m
 // (whether that one was placed or not, so j decides from the draws alone)
 MPC_HD void reset_env_idm(const View &v, const TrafficView &tv, int K, const Rng &r) {
-    v.ego[0] = 2.0;
-    v.ego[1] = 45.0 + (-5.0 + 10.0 * r.u01(kSlotEgo));
-    v.ego[2] = -kPiE / 2;
-    v.ego[3] = 10.0;
+    store_ego(v.ego, fresh_ego(r));
     double qx[kMaxOthers], qy[kMaxOthers];
     for (int j = 0; j < K; ++j) {
         const Drawn o = draw_vehicle(r, kSlotReset + 4 * j, kSlotTurnReset + j, 5.0, 60.0);
@@ -239,23 +236,16 @@ MPC_HD void reset_env_idm(const View &v, const TrafficView &tv, int K, const Rng
 }
 
 // one policy step with reactive traffic; everything that concerns the ego, the reward, the termination and the observation
-// is env::step_env's.  leader_out / accel_out (optional, [K]): whom each vehicle that drove this step followed (-2 nobody,
-// -1 the ego, k vehicle k; -3 for a vehicle that was not active) and the acceleration it chose - diagnostics for the tests.
+// is env::step_env's, through the same functions.  leader_out / accel_out (optional, [K]): whom each vehicle that drove this
+// step followed (-2 nobody, -1 the ego, k vehicle k; -3 for a vehicle that was not active) and the acceleration it chose -
+// diagnostics for the tests.
 MPC_HD StepOut step_env_idm(const View &v, const TrafficView &tv, int K, double dt, double spawn_probability, uint64_t seed,
                             int env_id, const double *ref_xy, int M, const double *action, float *terminal_obs, float *obs,
                             int32_t *leader_out, double *accel_out) {
     const Rng r(seed, env_id, *v.ctr);
     *v.ctr += 1;
-    double a = action[0], delta = action[1];
-    a = a < -5.0 ? -5.0 : (a > 5.0 ? 5.0 : a);
-    delta = delta < -kPiE / 4 ? -kPiE / 4 : (delta > kPiE / 4 ? kPiE / 4 : delta);
-    const double x = v.ego[0], y = v.ego[1], th = v.ego[2], sp = v.ego[3];
-    const double beta = atan(0.5 * tan(delta));
-    v.ego[0] = x + sp * cos(th + beta) * dt;
-    v.ego[1] = y + sp * sin(th + beta) * dt;
-    v.ego[2] = th + sp / kWheelbase * sin(beta) * dt;
-    double nv = sp + a * dt;
-    v.ego[3] = nv < 0.0 ? 0.0 : (nv > 30.0 ? 30.0 : nv);
+    const Ego e0 = load_ego(v.ego), e = step_ego(e0, action, dt);
+    store_ego(v.ego, e);
     // ---- accelerations from the state before the step
     double acc[kMaxOthers];
     Leader leads[kMaxOthers];
@@ -266,7 +256,7 @@ MPC_HD StepOut step_env_idm(const View &v, const TrafficView &tv, int K, double 
         if (!v.oactive[j]) continue;
         const double xj = v.opos[2 * j], yj = v.opos[2 * j + 1], hj = v.ohead[j], cj = cos(hj), sj = sin(hj);
         Leader lead = no_leader();
-        offer_leader(lead, j, xj, yj, hj, cj, sj, -1, x, y, th, sp);
+        offer_leader(lead, j, xj, yj, hj, cj, sj, -1, e0.x, e0.y, e0.th, e0.sp);
         for (int k = 0; k < K; ++k)
             if (k != j && v.oactive[k])
                 offer_leader(lead, j, xj, yj, hj, cj, sj, k, v.opos[2 * k], v.opos[2 * k + 1], v.ohead[k], v.ospeed[k]);
@@ -294,8 +284,7 @@ MPC_HD StepOut step_env_idm(const View &v, const TrafficView &tv, int K, double 
         if (v.oactive[j]) {
             advance(acc[j], dt, tv.oprog[j], v.ospeed[j]);
             pose(tv.oroute[j], tv.oprog[j], v.opos[2 * j], v.opos[2 * j + 1], v.ohead[j]);
-            const double ax = fabs(v.opos[2 * j]), ay = fabs(v.opos[2 * j + 1]);
-            gone = (ax > ay ? ax : ay) > 65.0;
+            gone = left_the_map(v.opos[2 * j], v.opos[2 * j + 1]);
         }
         stays[j] = !gone;
         drew[j] = gone && r.u01(kSlotRespawn + 5 * j) < spawn_probability;
@@ -326,44 +315,18 @@ MPC_HD StepOut step_env_idm(const View &v, const TrafficView &tv, int K, double 
             v.ospeed[j] = cand[j].speed;
             v.ohead[j] = cand[j].h;
         }
-        if (v.oactive[j]) {
-            const double ex = v.opos[2 * j] - v.ego[0], ey = v.opos[2 * j + 1] - v.ego[1];
-            crashed = crashed || sqrt(ex * ex + ey * ey) < kCrashDistance;
-        }
+        crashed = crashed || (v.oactive[j] && hits_ego(v.opos[2 * j], v.opos[2 * j + 1], e.x, e.y));
     }
-    double lateral = INFINITY;
-    int idx = 0;
-    for (int i = 0; i < M; ++i) {
-        const double ex = ref_xy[2 * i] - v.ego[0], ey = ref_xy[2 * i + 1] - v.ego[1];
-        const double d = sqrt(ex * ex + ey * ey);
-        if (d < lateral) {
-            lateral = d;
-            idx = i;
-        }
-    }
-    const bool on_road = lateral <= kLaneHalfWidth;
-    const bool arrived = idx >= M - 3 && on_road;
-    double cen = lateral / kLaneHalfWidth;
-    cen = 1.0 - (cen > 1.0 ? 1.0 : cen);
-    const double reward = kRewardCollision * (crashed ? 1.0 : 0.0) + kRewardHighSpeed * (v.ego[3] / 10.0) +
-                          kRewardArrived * (arrived ? 1.0 : 0.0) + (on_road ? kRewardCenter * cen : kRewardOffRoad);
+    const Nearest n = nearest_route_point(ref_xy, M, 0, 1, e.x, e.y);
     *v.t += 1;
-    const bool terminated = crashed || arrived;
-    const bool truncated = *v.t >= kEpisodeSteps && !terminated;
-    const bool done = terminated || truncated;
+    const StepOut o = score_step(n.d, n.idx, M, crashed, e.sp, *v.t);
     observe(v, K, terminal_obs);
-    if (done) {
+    if (o.done) {
         reset_env_idm(v, tv, K, r);
         observe(v, K, obs);
     } else {
         for (int i = 0; i < kRows * kCols; ++i) obs[i] = terminal_obs[i];
     }
-    StepOut o;
-    o.reward = (float)reward;
-    o.done = done;
-    o.truncated = truncated;
-    o.crashed = crashed;
-    o.arrived = arrived;
     return o;
 }
 

@@ -49,8 +49,9 @@ class SyntheticIntersectionEnv:
     """B independent intersection episodes stepped together on one device (auto-reset like an SB3 VecEnv).
 
     Two implementations of the same step behind this class: on a GPU the fused HIP kernel `mpc_synth_env_step`
-    (csrc/mpc_synth_env.hpp: vehicle models, respawn, reward, termination, terminal observation, auto-reset and the next
-    observation in ONE launch, counter-based random numbers) - `backend="hip"`, the default there; on the CPU, or with
+    (the statements of csrc/mpc_synth_env.hpp run by sixteen lanes per environment, csrc/mpc_synth_lanes.hpp: vehicle models,
+    respawn, reward, termination, terminal observation, auto-reset and the next observation in ONE launch, counter-based
+    random numbers) - `backend="hip"`, the default there; on the CPU, or with
     `backend="torch"`, the vectorised torch ops below (about a hundred small kernels per step on a GPU).  Same state
     tensors, same return values; the two draw different random streams (as torch's CPU and GPU generators do), the
     deterministic part of the step is identical (tests/test_rollout_cpu.py, tests/test_predict_gpu.py).

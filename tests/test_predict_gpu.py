@@ -399,17 +399,10 @@ def test_fused_environment_step_on_the_gpu_equals_its_host_build_and_the_torch_o
     """`mpc_synth_env_step` (one launch per policy step: models, respawn, reward, termination, terminal observation,
     auto-reset, next observation) against (a) the same source compiled for the host, same seed: same episodes, resets
     and respawns included; (b) the torch implementation it replaces on the GPU, for the deterministic part."""
-    import ctypes
     import torch
     from mpc_rl_for_avs_amd import rollout
-    from test_synth_env_cpu import HostEnv
-    import subprocess, os
-    from conftest import BUILD_DIR, HOST_CXXFLAGS, ROOT
-    out = os.path.join(BUILD_DIR, "libcpu_synth_env.so")
-    if not os.path.exists(out):
-        os.makedirs(BUILD_DIR, exist_ok=True)
-        subprocess.run(["g++"] + HOST_CXXFLAGS + ["-o", out, os.path.join(ROOT, "tests", "cpu_synth_env_harness.cpp")], check=True)
-    hostlib = ctypes.CDLL(out)
+    from test_synth_env_cpu import HostEnv, load_synth_lib
+    hostlib = load_synth_lib()
     B, K = 512, 4
     dev = torch.device("cuda:0")
     g = rollout.SyntheticIntersectionEnv(B, device=dev, seed=21, n_others=K, spawn_probability=0.3)
@@ -453,17 +446,10 @@ def test_sixteen_lanes_per_environment_step_for_every_vehicle_count(K, B):
     """`mpc_synth_env_rows_kernel` (round 5: lane j of a 16-lane group = vehicle j, four environments per wave) against the
     host build of the one-thread statement `env::step_env`, same seed: no traffic, one vehicle, the most the observation
     holds (9), and batch sizes that leave the last wave partly empty.  Episodes end and vehicles respawn along the way."""
-    import ctypes
-    import subprocess
     import torch
     from mpc_rl_for_avs_amd import rollout
-    from test_synth_env_cpu import HostEnv
-    from conftest import BUILD_DIR, HOST_CXXFLAGS, ROOT
-    out = os.path.join(BUILD_DIR, "libcpu_synth_env.so")
-    if not os.path.exists(out):
-        os.makedirs(BUILD_DIR, exist_ok=True)
-        subprocess.run(["g++"] + HOST_CXXFLAGS + ["-o", out, os.path.join(ROOT, "tests", "cpu_synth_env_harness.cpp")], check=True)
-    hostlib = ctypes.CDLL(out)
+    from test_synth_env_cpu import HostEnv, load_synth_lib
+    hostlib = load_synth_lib()
     dev = torch.device("cuda:0")
     g = rollout.SyntheticIntersectionEnv(B, device=dev, seed=9, n_others=K, spawn_probability=0.5)
     assert g.backend == "hip"

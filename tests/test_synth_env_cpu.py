@@ -3,6 +3,7 @@ compiled for the host, against the torch implementation in rollout.SyntheticInte
 the deterministic part of a step (vehicle models, crash / arrival / truncation, reward, the sorted observation) must agree
 statement for statement; the random part (respawn, reset) is checked through its distributions."""
 import ctypes
+import glob
 import os
 import subprocess
 
@@ -13,15 +14,19 @@ import torch
 from conftest import BUILD_DIR, HOST_CXXFLAGS, ROOT
 
 
-@pytest.fixture(scope="module")
-def lib():
+def load_synth_lib():
     out = os.path.join(BUILD_DIR, "libcpu_synth_env.so")
     src = os.path.join(ROOT, "tests", "cpu_synth_env_harness.cpp")
-    deps = [src, os.path.join(ROOT, "mpc-rl_for_avs_amd", "csrc", "mpc_synth_env.hpp")]
+    deps = [src] + glob.glob(os.path.join(ROOT, "mpc-rl_for_avs_amd", "csrc", "*.hpp"))
     if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
         os.makedirs(BUILD_DIR, exist_ok=True)
         subprocess.run(["g++"] + HOST_CXXFLAGS + ["-o", out, src], check=True)
     return ctypes.CDLL(out)
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return load_synth_lib()
 
 
 class HostEnv:

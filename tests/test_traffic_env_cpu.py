@@ -2,6 +2,7 @@
 `mpc_synth_env_step_idm`) compiled for the host: route geometry, the IDM, the reaction to the ego, the host build against the
 torch ops of rollout.SyntheticIntersectionEnv, the spawn rule with its draws, and liveness of the yield rule."""
 import ctypes
+import glob
 import os
 import subprocess
 
@@ -17,7 +18,7 @@ PARKED = (300.0, 300.0, 0.0, 0.0)      # an ego far from every lane, standing
 def load_traffic_lib():
     out = os.path.join(BUILD_DIR, "libcpu_traffic_env.so")
     src = os.path.join(ROOT, "tests", "cpu_traffic_env_harness.cpp")
-    deps = [src] + [os.path.join(ROOT, "mpc-rl_for_avs_amd", "csrc", f) for f in ("mpc_synth_env.hpp", "mpc_synth_traffic.hpp")]
+    deps = [src] + glob.glob(os.path.join(ROOT, "mpc-rl_for_avs_amd", "csrc", "*.hpp"))
     if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
         os.makedirs(BUILD_DIR, exist_ok=True)
         subprocess.run(["g++"] + HOST_CXXFLAGS + ["-o", out, src], check=True)
