@@ -66,13 +66,18 @@ constexpr int kWaveOccGenericCC = 2;
 // and the stragglers a batch ends with run at the lone-wave rate.
 constexpr int kWaveOccLat = 2, kLatDepth = 4;
 constexpr int kRelaxLat = 7;
+// The latency builds of the fixed horizons are limited to two waves per SIMD by their registers: eight workgroups per CU, which
+// leaves LDS over.  They get the spare region of mpc_wave.hpp (CTX::kSpareLds) for values that are otherwise recomputed.  Every
+// other build - throughput (LDS is what limits it), runtime horizon, mpc_eval_kernel - keeps the common layout.
+constexpr bool wave_spare_lds(int NC, int OCC, int RELAX) { return NC > 0 && OCC == kWaveOccLat && RELAX == kRelaxLat; }
 
 // ---------------------------------------------------------------------------------------------------
 // wave-cooperative kernel: ONE wave64 per instance (mpc_wave.hpp); workgroup = 1 wave, grid = B
 // ---------------------------------------------------------------------------------------------------
-template <int NC, int RELAX = 0>
+template <int NC, int RELAX = 0, bool SPARE = false>
 struct WaveCtx : mpc::wave::WaveOpsT<RELAX> {
     static constexpr int kN = NC;
+    static constexpr bool kSpareLds = SPARE;
     const double *table;  // [M][REF_COLS] in global memory (wave-uniform index in the serial parts -> scalar loads)
     int e0, M;
     __device__ __forceinline__ WaveCtx(mpc::wave::lds_double_t *l, const double *t, int e, int m)
@@ -138,7 +143,8 @@ __global__ __launch_bounds__(kBlock, OCC) void mpc_solve_wave_kernel(
     if (nveh) P.V = min(P.V, max(0, nveh[b]));   // vehicles actually present in this instance
     const int lane = threadIdx.x;
     constexpr int SL = mpc::wave::stage_slots(CC);
-    WaveCtx<NC, RELAX> ctx((mpc::wave::lds_double_t *)smem, ref5, ego_index[b], M);
+    using Ctx = WaveCtx<NC, RELAX, wave_spare_lds(NC, OCC, RELAX)>;
+    Ctx ctx((mpc::wave::lds_double_t *)smem, ref5, ego_index[b], M);
     stage_problem<CC>(ctx, P, b, lane, N, SL, ref5, M, vref, others, Vin);
     __syncthreads();
     double x0[4];
@@ -147,8 +153,7 @@ __global__ __launch_bounds__(kBlock, OCC) void mpc_solve_wave_kernel(
     const bool collide = is_collide[b] != 0;
     const double ws_ = collide ? 100.0 : weights[(size_t)b * 3 + 0];  // agents/pure_mpc.py:143-147
     const double wcoll = (CC && collide) ? 3000.0 * w_collision : 0.0;
-    mpc::wave::Solver<CC, WaveCtx<NC, RELAX>> solver(P, ctx, x0, ws_, weights[(size_t)b * 3 + 1], weights[(size_t)b * 3 + 2],
-                                             wcoll);
+    mpc::wave::Solver<CC, Ctx> solver(P, ctx, x0, ws_, weights[(size_t)b * 3 + 1], weights[(size_t)b * 3 + 2], wcoll);
     int status, iters, cur;
     double kkt;
     // opt-in warm start: initial controls u_init[b][min(k + u_shift, N-1)] (u_shift = 1: the previous solution of this
@@ -1023,7 +1028,7 @@ int launch_wave(const mpc_handle *h, const mpc::SolveParams &P, int B, int V, hi
                 uint8_t *d_uvalid, double *d_u0, double *d_U, double *d_X, int32_t *d_status, int32_t *d_iters,
                 const int32_t *d_order) {
     auto kern = mpc_solve_wave_kernel<CC, NC, OCC, RELAX>;
-    const size_t lds = (size_t)mpc::wave::lds_doubles(CC, P.N, P.V) * sizeof(double);
+    const size_t lds = (size_t)mpc::wave::lds_doubles(CC, P.N, P.V, wave_spare_lds(NC, OCC, RELAX)) * sizeof(double);
     static LdsLimits lds_set;
     if (int rc = raise_lds_limit(reinterpret_cast<const void *>(kern), h->device, lds, lds_set)) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kBlock), lds, stream, P, B, h->d_ref, h->M, d_state, d_ego,
@@ -1060,7 +1065,9 @@ int dispatch_solve(const mpc_handle *h, int B, bool cc, int V, uint32_t flags, h
     const bool throughput = (flags & MPC_FLAG_THROUGHPUT) != 0;
 
     static_assert(MPC_MAX_HORIZON <= mpc::wave::kMaxHorizon, "lane k = stage k needs the horizon to fit a wave");
-    const size_t wlds = (size_t)mpc::wave::lds_doubles(cc, N, Vuse) * sizeof(double);
+    const bool lat = !throughput && B <= kLatDepth * (4 * h->num_cu);      // which build: see kWaveOccLat above
+    const bool spare = lat && (N == 20 || N == 16);                        // (wave_spare_lds of the build launched below)
+    const size_t wlds = (size_t)mpc::wave::lds_doubles(cc, N, Vuse, spare) * sizeof(double);
     if (wlds > h->lds_per_cu)
         return fail(MPC_ERR_INVALID_ARG, "horizon / vehicle count too large for the LDS workspace of one instance");
     int rc;
@@ -1082,7 +1089,6 @@ int dispatch_solve(const mpc_handle *h, int B, bool cc, int V, uint32_t flags, h
         HIP_TRY(hipGetLastError());
         d_order = h->d_order;
     }
-    const bool lat = !throughput && B <= kLatDepth * simds;
 #define MPC_LAUNCH_N(CCV, NCV)                                          \
     if (lat) MPC_LAUNCH_W(CCV, NCV, kWaveOccLat, kRelaxLat);            \
     else MPC_LAUNCH_W(CCV, NCV, kWaveOcc, 0)
@@ -1205,8 +1211,9 @@ int mpc_set_reference(mpc_handle *h, const double *ref, int32_t M) {
 
 int64_t mpc_workspace_bytes(const mpc_handle *h, int32_t B, int32_t V) {
     if (!h || B < 0 || V < 0 || V > MPC_MAX_OTHERS) return -1;
-    // every build of the solve kernel has the same LDS layout since round 5 (mpc_wave.hpp: lds_doubles); the workspace is
-    // per instance, so B is checked and otherwise unused by design
+    // the layout every build of the solve kernel shares since round 5 (mpc_wave.hpp: lds_doubles) - what limits the residency
+    // of the throughput build; the spare region of the latency builds (wave_spare_lds) is LDS that would lie idle and is not
+    // counted.  The workspace is per instance, so B is checked and otherwise unused by design
     const int N = h->cfg.horizon;
     return (int64_t)mpc::wave::lds_doubles(V > 0, N, V) * (int64_t)sizeof(double);
 }

@@ -186,8 +186,23 @@ enum : int { PQ = 0, PB = 8 };
 constexpr double kNoBound = 1e300;
 
 MPC_HD constexpr int stage_slots(bool cc) { return (cc ? W_SLOTS_CC : W_SLOTS) + kPreSlots; }
-// doubles of LDS one instance needs: stage arrays + constants + other vehicles
-MPC_HD constexpr int lds_doubles(bool cc, int N, int V) { return stage_slots(cc) * (N + 1) + SC_SIZE + (cc ? 4 * V : 0); }
+
+// The SPARE REGION (only in a build whose context says CTX::kSpareLds = true: the latency builds of the fixed horizons, where
+// registers and not LDS limit the residency, so that a CU has LDS left over - DESIGN.md section 4.1).  It lies behind the other
+// vehicles and holds, for vehicle j and node k, the two words at 2 (j (N + 1) + k): the position (x, y) of the vehicle at that
+// node.  A function of the inputs alone - written once per solve (init_spare), read by dist() and wall_slack(), which form it
+// from four words on every use otherwise.  (Vehicle-major: the lanes of a stage-parallel phase, lane = node, read neighbouring
+// words.)  Without the collision cost there are no vehicles and the region is empty.
+MPC_HD constexpr int spare_doubles(bool cc, int N, int V) { return cc ? 2 * V * (N + 1) : 0; }
+template <class CTX, class = void>
+struct spare_lds { static constexpr bool value = false; };
+template <class CTX>
+struct spare_lds<CTX, decltype((void)CTX::kSpareLds)> { static constexpr bool value = CTX::kSpareLds; };
+
+// doubles of LDS one instance needs: stage arrays + constants + other vehicles (+ the spare region of the builds that have one)
+MPC_HD constexpr int lds_doubles(bool cc, int N, int V, bool spare = false) {
+    return stage_slots(cc) * (N + 1) + SC_SIZE + (cc ? 4 * V : 0) + (spare ? spare_doubles(cc, N, V) : 0);
+}
 
 // section ids for CTX::tick (cycle attribution in tools/ubench/wave_sections.hip; a no-op in the product kernel)
 enum : int {
@@ -295,6 +310,8 @@ struct Solver {
     const SolveParams &P;
     CTX &c;
     const int N, SL, SCR, OTH;
+    static constexpr bool kSpare = spare_lds<CTX>::value;
+    const int SPP;               // spare region (kSpare): the vehicles' positions
     const double dt;
     double x0[4];
     double ws_, wc_, wd_, wcoll;   // read through WS() ... WCOLL(), SF()
@@ -309,7 +326,7 @@ struct Solver {
 
     MPC_HD Solver(const SolveParams &P_, CTX &c_, const double *x0_, double ws, double wc, double wd, double wcl)
         : P(P_), c(c_), N(CTX::kN > 0 ? CTX::kN : P_.N), SL(stage_slots(CC)), SCR(SL * (N + 1)), OTH(SCR + SC_SIZE),
-          dt(P_.dt), ws_(c_.uni(ws)), wc_(c_.uni(wc)), wd_(c_.uni(wd)), wcoll(c_.uni(wcl)) {
+          SPP(OTH + (CC ? 4 * P_.V : 0)), dt(P_.dt), ws_(c_.uni(ws)), wc_(c_.uni(wc)), wd_(c_.uni(wd)), wcoll(c_.uni(wcl)) {
         x0[0] = x0_[0]; x0[1] = x0_[1]; x0[2] = x0_[2]; x0[3] = x0_[3];
     }
     MPC_HD double S(int k, int slot) const { return c.ld(k * SL + slot); }
@@ -317,6 +334,20 @@ struct Solver {
     MPC_HD double sc(int i) const { return c.ld(SCR + i); }
     MPC_HD void sc(int i, double v) { c.st(SCR + i, v); }
     MPC_HD double oth(int j, int q) const { return c.ld(OTH + j * 4 + q); }
+    // position of vehicle j at node k: from the spare region where the build has one
+    MPC_HD double veh_x(int j, int k) const { return kSpare ? c.ld(SPP + 2 * (j * (N + 1) + k)) : oth(j, 0) + k * oth(j, 2); }
+    MPC_HD double veh_y(int j, int k) const { return kSpare ? c.ld(SPP + 2 * (j * (N + 1) + k) + 1) : oth(j, 1) + k * oth(j, 3); }
+    // once per solve: what the spare region holds (the same expressions as veh_x / veh_y)
+    MPC_HD void init_spare() {
+        if (!kSpare || !CC) return;
+        c.phase([&](int lane) {
+            for (int k = lane; k <= N; k += kLanes)
+                for (int j = 0; j < P.V; ++j) {
+                    c.st(SPP + 2 * (j * (N + 1) + k), oth(j, 0) + k * oth(j, 2));
+                    c.st(SPP + 2 * (j * (N + 1) + k) + 1, oth(j, 1) + k * oth(j, 3));
+                }
+        });
+    }
     // Bounds and function coefficients come from a table in LDS, not from literals: a 64-bit literal that is used in
     // more than one place gets hoisted out of the iteration loop into a register pair for the whole solve, and two dozen
     // of those are the difference between 3 and 4 resident waves per SIMD.  A table entry is loaded where it is used
@@ -626,8 +657,8 @@ struct Solver {
     MPC_HD double dist(int k, double x_0, double x_1, double *d8, int j0 = 0, int dj = 1) const {
         double J = 0.0, g0 = 0, g1 = 0, h00 = 0, h01 = 0, h11 = 0, c00 = 0, c01 = 0, c11 = 0;
         for (int j = j0; j < P.V; j += dj) {
-            const double px = x_0 - (oth(j, 0) + k * oth(j, 2));
-            const double py = x_1 - (oth(j, 1) + k * oth(j, 3));
+            const double px = x_0 - veh_x(j, k);
+            const double py = x_1 - veh_y(j, k);
             const double d2 = fma(px, px, py * py);
             const double rd = frsqrt(d2), d = d2 * rd;
             const double cst = (d2 < 1.0 ? c.fresh(1000.0) : c.fresh(100.0)) * P.w_distance;   // same expression as wall_slack() + 1
@@ -656,8 +687,8 @@ struct Solver {
     }
     // slack |p - o_jk|^2 - 1 of the wall constraint of node k and vehicle j at position (x_0, x_1), gradient (nx, ny)
     MPC_HD double wall_slack(int k, double x_0, double x_1, int j, double &nx, double &ny) const {
-        const double px = x_0 - (oth(j, 0) + k * oth(j, 2));
-        const double py = x_1 - (oth(j, 1) + k * oth(j, 3));
+        const double px = x_0 - veh_x(j, k);
+        const double py = x_1 - veh_y(j, k);
         nx = 2.0 * px;
         ny = 2.0 * py;
         return fma(px, px, py * py) - 1.0;
@@ -804,6 +835,7 @@ struct Solver {
     // reference's dynamics constraint (:220-257) is X[k+1] - xn[k] = 0.
     MPC_HD double evaluate(PerLane<double> (&xn)[4]) {
         init_tables();
+        init_spare();
         any_wall = 0;
         c.phase([&](int lane) {
             red_a.at(lane) = 0.0;
@@ -1256,6 +1288,7 @@ struct Solver {
         cur_out = 0;
         kkt_out = INFINITY;
         init_tables();
+        init_spare();
         // cold start of the reference (agents/pure_mpc.py:240-246: controls 0), multipliers 1
         c.phase([&](int lane) {
             if (lane >= N) return;
