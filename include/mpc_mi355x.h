@@ -428,6 +428,43 @@ int mpc_drive_metrics(int32_t device, int32_t B, int32_t R, int32_t Q, int32_t M
                       void *stream);
 
 /*
+ * mpc_interaction_metrics (an addition within ABI 8: old clients never call it, nothing else changes) - interaction metrics
+ * of a closed-loop evaluation of B environments with reactive traffic, per episode, beside mpc_episode_stats and
+ * mpc_drive_metrics: what the ego does to the other vehicles - how often one yields to it, how hard it makes one brake, how
+ * much speed that costs the traffic, and the post-encroachment time where a traffic route crosses the ego's (formulas, in
+ * evaluation order, and the per-environment update in csrc/mpc_interaction.hpp; the 1.5 s threshold there is this project's).
+ * Device pointers, enqueue only on `stream`, never synchronises (capturable in a hipGraph); sixteen lanes per environment, the
+ * route staged in LDS, no atomics, no scratch.  One launch per policy step, after mpc_synth_env_step_idm: unlike
+ * mpc_drive_metrics the update reads the simulator's slots, so it serves that environment only.
+ *
+ * Inputs of a step, all const: the state arrays of mpc_synth_env_step_idm after the step and its auto-reset (ego [B][4],
+ * opos [B][K][2], ospeed, ohead, oprog, otarget [B][K] f64, oactive [B][K] u8, oroute [B][K] i32), done [B] u8, ref_xy [M][2]
+ * f64 (the ego's route), conflict [12][2] f64 = per traffic route the arc length along ref_xy and along the route where the
+ * two cross (the first < 0: no crossing conflict), dt (step length, s).
+ * Running state: state_i32 [18][B] = steps, yield_steps, forced_brake_steps, forced_brake_events, conflicts, pet_critical,
+ * ego_first, episode ordinal j, the previous state's mask of hard-braking vehicles, then 9 carried oroute (-1: empty slot);
+ * state_f64 [34][B] = max_forced_decel, speed_deficit, min_pet, the carried arc length of the ego, then 12 pass times of the
+ * ego (one per route), 9 pass times of the slots and 9 carried oprog.  A pass time that is not set is -1.
+ * Records, one slot per (environment b, ordinal j < Q), the slot mpc_episode_stats writes for the same episode:
+ * rec_i32 [7][B][Q] = steps, yield_steps (states in which a vehicle's leader is the ego), forced_brake_steps (... and it brakes
+ * harder than 3 m/s^2), forced_brake_events (vehicles that begin to), conflicts (post-encroachment times evaluated),
+ * pet_critical (below 1.5 s), ego_first; rec_f64 [3][B][Q] = max_forced_decel, speed_deficit (m/s: the acceleration each
+ * yielding vehicle would have had without the ego minus the one it has, times dt, summed), min_pet (+inf when none).
+ *
+ * The states of an episode that are folded are those its decisions were made in, s_0 .. s_{T-1}; the terminal state is not.
+ * reset != 0 (issue it after the environments' reset; done may be NULL): clear the running state and fold the fresh state.
+ * Otherwise, when done[b]: if j < Q write slot [b][j] from the states folded so far, then clear and j += 1 (up to Q), and
+ * fold the current (fresh) state as state 0 of the next episode; when not done: fold the current state.  f64 without
+ * contraction; cos and sin are each build's own, so the kernel and a host build of the header agree to their rounding.
+ * Errors: B < 0, Q < 1, K outside 1 .. 9, M outside 1 .. 128, dt <= 0, any NULL array, or a NULL done of a non-reset launch.
+ */
+int mpc_interaction_metrics(int32_t device, int32_t B, int32_t K, int32_t Q, int32_t M, int32_t reset, double dt,
+                            const double *ego, const double *opos, const double *ospeed, const double *ohead,
+                            const uint8_t *oactive, const int32_t *oroute, const double *oprog, const double *otarget,
+                            const uint8_t *done, const double *ref_xy, const double *conflict, int32_t *state_i32,
+                            double *state_f64, int32_t *rec_i32, double *rec_f64, void *stream);
+
+/*
  * mpc_perceive (an addition within ABI 8: old clients never call it, nothing else changes) - a perception model between the
  * environment and the agent of a closed-loop evaluation: obs_seen is what the ego sees of the true scene obs_true under a
  * limited range, occlusion by the other vehicles' 5 m x 2 m rectangles and by static convex quadrilaterals, random dropout

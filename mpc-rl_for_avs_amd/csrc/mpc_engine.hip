@@ -31,6 +31,7 @@
 #include "mpc_rollout_glue.hpp"
 #include "mpc_drive_metrics.hpp"
 #include "mpc_perception.hpp"
+#include "mpc_interaction.hpp"
 #include "mpc_episode_stats.hpp"
 
 namespace {
@@ -747,6 +748,123 @@ __global__ __launch_bounds__(64) void mpc_drive_metrics_kernel(mpc::drive::Accou
         m.xte2 = drive::min2(m.xte2, __shfl_xor(m.xte2, off, 16));
     }
     if (live && l == 0) drive::episode_update(acc, in, b, reset != 0, m);
+}
+
+// interaction metrics of a closed-loop evaluation (mpc_interaction.hpp): sixteen lanes per environment, four environments per
+// wave, the mapping of mpc_synth_env_idm_kernel.  Lane j of a group is vehicle j: its two leaders (with and without the ego)
+// from a loop over k < K of group shuffles, both walks of the circle rule by shuffles of who[], its decision; the group's
+// counts are slices of two ballots, the largest deceleration a shuffle maximum, the imposed accelerations summed in index
+// order from shuffles.  The route is staged in LDS as in the environment kernels; its segments are strided over the lanes and
+// the (distance, index) minimum taken by shuffles (first of the nearest).  Lane r < 12 keeps the ego's pass time of route r,
+// lane j < 9 its slot's pass time and carries, lane 0 does the sequential part and writes the counters and the record.
+// Every shuffle, ballot and barrier sits in wave-uniform control flow: a lane without a vehicle decides nothing, a group
+// past the end reads the last environment; only stores are predicated.  The running state is read by every lane of a group
+// before a lane of the same wave writes it.  No atomics.
+__global__ __launch_bounds__(64) void mpc_interaction_kernel(mpc::interact::Accounts acc, mpc::interact::StepInputs in, int reset) {
+    namespace ia = mpc::interact;
+    namespace env = mpc::env;
+    namespace drive = mpc::drive;
+    __shared__ double s_ref[2 * env::kMaxRoutePoints];
+    env::stage_route(s_ref, in.ref_xy, in.M);
+    const int q = threadIdx.x & 15, g = threadIdx.x >> 4;
+    const int b_ = blockIdx.x * 4 + g;
+    const bool live = b_ < acc.B;
+    const int b = live ? b_ : acc.B - 1;
+    const size_t B = (size_t)acc.B;
+    const int K = in.K, Ks = K > 0 ? K : 1;
+    const bool mine = q < K;
+    const size_t vo = (size_t)b * Ks + (mine ? q : 0);
+    int32_t *si = acc.state_i32 + b;
+    double *sf = acc.state_f64 + b;
+    const bool fresh = reset || in.done[b] != 0;
+    const int n = fresh ? 0 : si[ia::kSteps * B];
+    const env::Ego e = env::load_ego(in.ego + (size_t)b * 4);
+    // ---- (a) vehicle q
+    double px = 0.0, py = 0.0, ps = 0.0, ph = 0.0, prog = 0.0, target = 1.0;
+    int route = -1;
+    bool act = false;
+    if (mine) {
+        px = in.opos[2 * vo]; py = in.opos[2 * vo + 1]; ps = in.ospeed[vo]; ph = in.ohead[vo];
+        act = in.oactive[vo] != 0;
+        route = in.oroute[vo]; prog = in.oprog[vo]; target = in.otarget[vo];
+    }
+    const double cj = cos(ph), sj = sin(ph);
+    env::Leader lead = env::no_leader(), alt = env::no_leader();
+    env::offer_leader(lead, q, px, py, ph, cj, sj, -1, e.x, e.y, e.th, e.sp);
+    for (int k = 0; k < K; ++k) {
+        const double kx = __shfl(px, k, 16), ky = __shfl(py, k, 16), kh = __shfl(ph, k, 16), kv = __shfl(ps, k, 16);
+        const int ka = __shfl((int)act, k, 16);
+        if (k != q && ka) {
+            env::offer_leader(lead, q, px, py, ph, cj, sj, k, kx, ky, kh, kv);
+            env::offer_leader(alt, q, px, py, ph, cj, sj, k, kx, ky, kh, kv);
+        }
+    }
+    const int who = act ? lead.who : -2;
+    int wp = who, lowest = q, ap = act ? alt.who : -2, alowest = q;
+    bool closed = false, aclosed = false;
+    for (int i = 0; i < K; ++i) {
+        const int next = __shfl(who, wp >= 0 ? wp : 0, 16), anext = __shfl(who, ap >= 0 ? ap : 0, 16);
+        env::walk_leaders(q, wp >= 0 ? next : -2, wp, lowest, closed);
+        env::walk_leaders(q, ap >= 0 ? anext : -2, ap, alowest, aclosed);
+    }
+    if (closed && lowest == q) lead = env::no_leader();
+    if (aclosed && alowest == q) alt = env::no_leader();
+    ia::Decision d = ia::inactive_decision();
+    if (act) d = ia::decide(ps, target, ph, lead, alt);
+    const int n_yield = __popcll((__ballot(d.yields) >> (16 * g)) & 0xffffull);
+    const int32_t hard_mask = (int32_t)((__ballot(d.hard) >> (16 * g)) & 0xffffull);
+    double forced = d.yields ? drive::max2(0.0, -d.a_with) : 0.0;
+    for (int off = 8; off >= 1; off >>= 1) forced = drive::max2(forced, __shfl_xor(forced, off, 16));
+    double imposed_sum = 0.0;
+    for (int k = 0; k < K; ++k) imposed_sum = imposed_sum + __shfl(d.imposed, k, 16);
+    // ---- (b) the ego's arc length, the pass times, the post-encroachment times
+    ia::Proj pr{ia::kInf, 0};
+    const int nseg = in.M > 1 ? in.M - 1 : 1;
+    for (int i = q; i < nseg; i += 16) ia::fold_proj(s_ref, in.M, i, e.x, e.y, pr);
+    double near_d2 = pr.d2;
+    int near_idx = pr.idx;
+    for (int off = 8; off >= 1; off >>= 1) {       // the smaller distance, the lower index among equal ones
+        const double od = __shfl_xor(near_d2, off, 16);
+        const int oi = __shfl_xor(near_idx, off, 16);
+        const bool take = od < near_d2 || (od == near_d2 && oi < near_idx);
+        near_d2 = take ? od : near_d2;
+        near_idx = take ? oi : near_idx;
+    }
+    const double sigma = ia::sigma_at(s_ref, in.M, near_idx, e.x, e.y);
+    const int r = q < ia::kRoutes ? q : 0;
+    bool te_fresh = false, tv_fresh = false;
+    const double te = ia::ego_pass(n, in.conflict[2 * r], fresh ? ia::kUnset : sf[(ia::kTe + r) * B], sf[ia::kCarrySigma * B],
+                                   sigma, te_fresh);
+    const int s = q < ia::kSlots ? q : 0;
+    const bool in_slot = act && q < ia::kSlots && ia::valid_route(route);
+    const int sroute = in_slot ? route : -1;
+    const double sprog = in_slot ? prog : 0.0;
+    double tv = ia::kUnset;
+    if (!fresh) tv = ia::slot_pass(n, in_slot, sroute, sprog, si[(ia::kCarryRoute + s) * B], sf[(ia::kCarryProg + s) * B],
+                                   sf[(ia::kTv + s) * B], in.conflict, tv_fresh);
+    const double te_r = __shfl(te, in_slot ? sroute : 0, 16);
+    const int te_r_fresh = __shfl((int)te_fresh, in_slot ? sroute : 0, 16);
+    ia::Pets p{0, 0, 0, ia::kInf};
+    if (in_slot) ia::fold_pet(te_r, tv, te_r_fresh != 0, tv_fresh, in.dt, p);
+    for (int off = 8; off >= 1; off >>= 1) {
+        p.conflicts += __shfl_xor(p.conflicts, off, 16);
+        p.critical += __shfl_xor(p.critical, off, 16);
+        p.ego_first += __shfl_xor(p.ego_first, off, 16);
+        p.min_pet = drive::min2(p.min_pet, __shfl_xor(p.min_pet, off, 16));
+    }
+    // ---- the sequential part (it reads the counters before it writes them), then the lanes' own fields
+    if (live && q == 0) {
+        bool f;
+        int32_t ordinal;
+        const ia::Running run = ia::open_episode(acc, in, b, reset != 0, f, ordinal);
+        ia::close_state(acc, b, in.dt, run, ordinal, n_yield, forced, hard_mask, imposed_sum, p, sigma);
+    }
+    if (live && q < ia::kRoutes) sf[(ia::kTe + q) * B] = te;
+    if (live && q < ia::kSlots) {
+        sf[(ia::kTv + q) * B] = tv;
+        sf[(ia::kCarryProg + q) * B] = sprog;
+        si[(ia::kCarryRoute + q) * B] = sroute;
+    }
 }
 
 // perception model of a closed-loop evaluation (mpc_perception.hpp): sixteen lanes per environment, four environments per
@@ -1798,6 +1916,30 @@ int mpc_drive_metrics(int32_t device, int32_t B, int32_t R, int32_t Q, int32_t M
     const mpc::drive::Accounts acc{(int)B, (int)Q, state_i32, state_f64, rec_i32, rec_f64};
     const mpc::drive::StepInputs in{(int)R, (int)M, dt, terminal_obs, obs, action, done, ref_xy};
     hipLaunchKernelGGL(mpc_drive_metrics_kernel, dim3((unsigned)((B + 3) / 4)), dim3(64), 0,
+                       reinterpret_cast<hipStream_t>(stream_), acc, in, (int)reset);
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_interaction_metrics(int32_t device, int32_t B, int32_t K, int32_t Q, int32_t M, int32_t reset, double dt,
+                            const double *ego, const double *opos, const double *ospeed, const double *ohead,
+                            const uint8_t *oactive, const int32_t *oroute, const double *oprog, const double *otarget,
+                            const uint8_t *done, const double *ref_xy, const double *conflict, int32_t *state_i32,
+                            double *state_f64, int32_t *rec_i32, double *rec_f64, void *stream_) {
+    if (B < 0 || Q < 1 || K < 1 || K > mpc::env::kMaxOthers || M < 1 || M > mpc::interact::kMaxRoute || !(dt > 0.0))
+        return fail(MPC_ERR_INVALID_ARG,
+                    "mpc_interaction_metrics: bad size (B >= 0, Q >= 1, 1 <= K <= 9, 1 <= M <= 128, dt > 0)");
+    if (!ego || !opos || !ospeed || !ohead || !oactive || !oroute || !oprog || !otarget)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_interaction_metrics: null environment state pointer");
+    if (!ref_xy || !conflict || !state_i32 || !state_f64 || !rec_i32 || !rec_f64)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_interaction_metrics: null ref_xy / conflict / state / record pointer");
+    if (!reset && !done) return fail(MPC_ERR_INVALID_ARG, "mpc_interaction_metrics: null done of a non-reset launch");
+    if (B == 0) return MPC_OK;
+    HIP_TRY(hipSetDevice(device));
+    const mpc::interact::Accounts acc{(int)B, (int)Q, state_i32, state_f64, rec_i32, rec_f64};
+    const mpc::interact::StepInputs in{(int)K, (int)M, dt, ego, opos, ospeed, ohead, oactive, oroute, oprog, otarget, done,
+                                       ref_xy, conflict};
+    hipLaunchKernelGGL(mpc_interaction_kernel, dim3((unsigned)((B + 3) / 4)), dim3(64), 0,
                        reinterpret_cast<hipStream_t>(stream_), acc, in, (int)reset);
     HIP_TRY(hipGetLastError());
     return MPC_OK;

@@ -62,7 +62,7 @@ _EXPORTS = ["mpc_version", "mpc_last_error", "mpc_default_config", "mpc_default_
             "mpc_set_reference", "mpc_solve_batch", "mpc_workspace_bytes", "mpc_predict_batch",
             "mpc_reset_env_state", "mpc_reset_env_mask", "mpc_get_env_state", "mpc_get_last_inputs",
             "mpc_ltv_solve_batch", "mpc_ltv_predict_batch", "mpc_env_state_bytes", "mpc_save_env_state",
-            "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_perceive", "mpc_eval_nlp", "mpc_streams_overlap"]
+            "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_interaction_metrics", "mpc_perceive", "mpc_eval_nlp", "mpc_streams_overlap"]
 ABI_VERSION = 8          # MPC_ABI_VERSION of include/mpc_mi355x.h this binding is written for
 MAX_OTHERS = 16
 _lib = None
@@ -160,6 +160,8 @@ def load_library(path: str | None = None):
     lib.mpc_episode_stats.restype = ctypes.c_int
     lib.mpc_drive_metrics.argtypes = [ctypes.c_int32] * 6 + [ctypes.c_double] + [vp] * 9 + [vp]
     lib.mpc_drive_metrics.restype = ctypes.c_int
+    lib.mpc_interaction_metrics.argtypes = [ctypes.c_int32] * 6 + [ctypes.c_double] + [vp] * 15 + [vp]
+    lib.mpc_interaction_metrics.restype = ctypes.c_int
     lib.mpc_perceive.argtypes = [ctypes.c_int32] * 5 + [ctypes.POINTER(PerceptionParams)] + [vp] * 6 + [vp]
     lib.mpc_perceive.restype = ctypes.c_int
     lib.mpc_eval_nlp.argtypes = [vp, ctypes.c_int32] + [vp] * 5 + [ctypes.c_int32, ctypes.c_uint32] + [vp] * 4

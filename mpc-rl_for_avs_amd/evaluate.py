@@ -23,10 +23,16 @@ same captured step (mpc_drive_metrics), or by the same update in elementwise tor
 `perception=` puts a perception model (csrc/mpc_perception.hpp, `Perception`) between the environment and the agent: limited
 range, occlusion by vehicles and by buildings (`corner_buildings`), dropout and bounded noise.  The agent acts on what is
 seen; the accounting and the drive metrics keep reading the true scene.
+
+`interaction=True` (reactive traffic only) adds the interaction metrics of csrc/mpc_interaction.hpp to every episode
+(`InteractionMetrics`: how often another vehicle yields to the ego, how hard the ego makes it brake, the speed that costs the
+traffic, post-encroachment times where a traffic route crosses the ego's), computed per step from the simulator's own slots
+inside the same captured step (mpc_interaction_metrics), or by the same update in numpy on the CPU path.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 import time
 from dataclasses import dataclass
 
@@ -50,6 +56,13 @@ MAX_ROWS, MAX_ROUTE = 17, 128                                                   
 ROW_ABSENT, ROW_SEEN, ROW_OUT_OF_RANGE, ROW_OCCLUDED, ROW_DROPPED = 0, 1, 2, 3, 4
 PERCEPTION_COUNTS = ("present", "seen", "out_of_range", "occluded", "dropped")      # mpc_perceive counts [5][B]
 PERCEPTION_SALT, UNIT_SCALE, ROW_SLOTS, MAX_OCCLUDERS = 0xC2B2AE3D27D4EB4F, 1.7320508075688772, 32, 8
+# csrc/mpc_interaction.hpp: the records, this project's critical post-encroachment time [s], traffic routes, vehicle slots, the
+# layout of the running state (counters and previous mask, carried routes; counters, carried arc length, pass times, carried oprog)
+INTERACT_I32 = ("steps", "yield_steps", "forced_brake_steps", "forced_brake_events", "conflicts", "pet_critical",
+                "ego_first")                                                        # mpc_interaction_metrics rec_i32 [7][B][Q]
+INTERACT_F64 = ("max_forced_decel", "speed_deficit", "min_pet")                     # rec_f64 [3][B][Q]
+PET_CRITICAL, ROUTES, SLOTS = 1.5, 12, 9
+INTERACT_STATE_I32, INTERACT_STATE_F64 = 9 + SLOTS, 4 + ROUTES + 2 * SLOTS
 
 
 def records_from_planes(rec_i32, rec_f64) -> dict:
@@ -338,6 +351,324 @@ class DriveMetrics:
         return drive_records_from_planes(self.rec_i32.cpu().numpy(), self.rec_f64.cpu().numpy())
 
 
+def interaction_records_from_planes(rec_i32, rec_f64) -> dict:
+    """The record planes of the interaction metrics (include/mpc_mi355x.h layout) -> dict of numpy arrays [B, Q]."""
+    rec_i32, rec_f64 = np.asarray(rec_i32), np.asarray(rec_f64)
+    out = {k: rec_i32[i].copy() for i, k in enumerate(INTERACT_I32)}
+    out.update({k: rec_f64[i].copy() for i, k in enumerate(INTERACT_F64)})
+    return out
+
+
+def _wrap_pi(a):
+    a = np.where(a > math.pi, a - 2.0 * math.pi, a)
+    return np.where(a <= -math.pi, a + 2.0 * math.pi, a)
+
+
+def route_pieces(route: int) -> list:
+    """The centre line of traffic route 3 * entry + turn (csrc/mpc_synth_traffic.hpp: pose) from its entry to the end of the
+    map, as pieces in the order they are driven: dicts with s0 (arc length where the piece begins), length, and either
+    kind="line" (p0, unit direction u, heading h) or kind="arc" (centre c, radius R, axes a0 and a1 with point(phi) = c +
+    R (a0 cos phi + a1 sin phi), heading h0 + sign * phi, phi = (s - s0) / R in [0, pi / 2])."""
+    entry, turn = divmod(int(route), 3)
+    d = np.array([(1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0)][entry])
+    n = np.array([-d[1], d[0]])
+    h0 = (0.0, math.pi / 2, math.pi, -math.pi / 2)[entry]
+    if turn == 0:                                          # |coordinate| <= 65 until s = 125
+        return [dict(kind="line", s0=0.0, length=125.0, p0=-60.0 * d + 2.0 * n, u=d, h=h0)]
+    sign, R = (1.0, 8.0) if turn == 2 else (-1.0, 12.0)    # right: about -10 d + 10 n; left: about -10 d - 10 n
+    arc = R * (math.pi / 2)
+    end = (-2.0 * d + 10.0 * n) if turn == 2 else (2.0 * d - 10.0 * n)
+    return [dict(kind="line", s0=0.0, length=50.0, p0=-60.0 * d + 2.0 * n, u=d, h=h0),
+            dict(kind="arc", s0=50.0, length=arc, c=-10.0 * d + sign * 10.0 * n, R=R, a0=-sign * n, a1=d, h0=h0, sign=sign),
+            dict(kind="line", s0=50.0 + arc, length=55.0, p0=end, u=sign * n, h=float(_wrap_pi(h0 + sign * math.pi / 2)))]
+
+
+def conflict_points(ref_xy) -> np.ndarray:
+    """[12, 2] = (sigma_c, s_c) per traffic route: the first point along the ego's polyline ref_xy [M, 2] at which the route's
+    centre line crosses it with an angle between the two directions of at least pi / 4 (the corridor rule's threshold: merging
+    and following are the IDM's business, not a crossing conflict), as arc length along the polyline and along the route;
+    sigma_c = -1 (and s_c = -1) where there is none.  Segment against line and segment against arc, in closed form."""
+    ref = np.asarray(ref_xy, dtype=np.float64)
+    if ref.ndim != 2 or ref.shape[1] != 2 or ref.shape[0] < 1:
+        raise ValueError("ref_xy must be [M, 2]")
+    cross = lambda a, b: a[0] * b[1] - a[1] * b[0]
+    out = np.full((ROUTES, 2), -1.0)
+    eps = 1e-12
+    for r in range(ROUTES):
+        best = None
+        sigma0 = 0.0
+        for i in range(ref.shape[0] - 1):
+            p0, e = ref[i], ref[i + 1] - ref[i]
+            L = math.sqrt(e[0] * e[0] + e[1] * e[1])
+            if L > 0.0:
+                he = math.atan2(e[1], e[0])
+                for pc in route_pieces(r):
+                    hits = []                              # (parameter along the segment, arc length on the route, heading)
+                    if pc["kind"] == "line":
+                        det = cross(e, pc["u"])
+                        if abs(det) > eps * L:
+                            w = pc["p0"] - p0
+                            hits.append((cross(w, pc["u"]) / det, cross(w, e) / det, pc["h"]))
+                    else:
+                        w = p0 - pc["c"]
+                        qa, qb, qc = L * L, 2.0 * (w[0] * e[0] + w[1] * e[1]), w[0] * w[0] + w[1] * w[1] - pc["R"] ** 2
+                        disc = qb * qb - 4.0 * qa * qc
+                        if disc >= 0.0:
+                            for a in ((-qb - math.sqrt(disc)) / (2.0 * qa), (-qb + math.sqrt(disc)) / (2.0 * qa)):
+                                rel = (w + a * e) / pc["R"]
+                                phi = math.atan2(rel[0] * pc["a1"][0] + rel[1] * pc["a1"][1],
+                                                 rel[0] * pc["a0"][0] + rel[1] * pc["a0"][1])
+                                hits.append((a, pc["R"] * phi, pc["h0"] + pc["sign"] * phi))
+                    for a, c, h in hits:
+                        if -eps <= a <= 1.0 + eps and -eps <= c <= pc["length"] + eps and \
+                                abs(float(_wrap_pi(_wrap_pi(h) - he))) >= math.pi / 4:
+                            sigma = sigma0 + min(max(a, 0.0), 1.0) * L
+                            if best is None or sigma < best[0]:
+                                best = (sigma, pc["s0"] + min(max(c, 0.0), pc["length"]))
+            sigma0 += L
+        if best is not None:
+            out[r] = best
+    return out
+
+
+class _Leader:
+    """mpc::env::Leader for B environments at once."""
+
+    def __init__(self, B):
+        self.ell = np.full(B, np.inf)
+        self.head, self.speed = np.zeros(B), np.zeros(B)
+        self.who = np.full(B, -2, np.int64)
+
+    def offer(self, j, xj, yj, hj, cj, sj, c, cx, cy, ch, cv, valid):
+        """mpc::env::offer_leader where `valid`"""
+        ex, ey = cx - xj, cy - yj
+        ell = ex * cj + ey * sj
+        w = ey * cj - ex * sj
+        take = valid & (ell > 0.0) & (ell <= 40.0) & (np.abs(w) <= 2.0) & (ell < self.ell)
+        if c >= 0:
+            take = take & (ell > 5.0) & ((c < j) | (np.abs(_wrap_pi(ch - hj)) < math.pi / 4))
+        self.ell, self.head = np.where(take, ell, self.ell), np.where(take, ch, self.head)
+        self.speed, self.who = np.where(take, cv, self.speed), np.where(take, c, self.who)
+
+    def drop(self, where):
+        """no_leader() where `where`"""
+        self.ell, self.head = np.where(where, np.inf, self.ell), np.where(where, 0.0, self.head)
+        self.speed, self.who = np.where(where, 0.0, self.speed), np.where(where, -2, self.who)
+
+
+def _idm_acceleration(v, v0, hj, lead):
+    """mpc::env::idm_acceleration"""
+    r = v / v0
+    r2 = r * r
+    has = lead.who != -2
+    gap = np.where(has, lead.ell, 10.0) - 5.0
+    gap = np.where(gap < 0.1, 0.1, gap)
+    dv = v - lead.speed * np.cos(lead.head - hj)
+    dyn = v * 1.5 + v * dv / 7.745966692414834
+    dyn = np.where(dyn < 0.0, 0.0, dyn)
+    q = (5.0 + dyn) / gap
+    a = 3.0 * (1.0 - r2 * r2 - np.where(has, q * q, 0.0))
+    return np.where(a < -6.0, -6.0, np.where(a > 3.0, 3.0, a))
+
+
+def _drives_free(j, first, who):
+    """The circle rule (mpc::env::walk_leaders, K steps) from vehicle j whose leader is first [B], along who [B, K]."""
+    B, K = who.shape
+    p, lowest, closed = first.copy(), np.full(B, j, np.int64), np.zeros(B, bool)
+    rows = np.arange(B)
+    for _ in range(K):
+        go = (p >= 0) & ~closed
+        closed = closed | (go & (p == j))
+        go = go & ~closed
+        lowest = np.where(go, np.minimum(lowest, p), lowest)
+        p = np.where(go, who[rows, np.clip(p, 0, K - 1)], p)
+    return closed & (lowest == j)
+
+
+class InteractionMetrics:
+    """Running state and records of the interaction metrics, as device tensors in the layout of mpc_interaction_metrics
+    (include/mpc_mi355x.h; formulas in csrc/mpc_interaction.hpp); `update(env, done)` after the environment's step is the
+    kernel (backend "hip") or the same update in numpy on the CPU (backend "torch": the feature works wherever the environment
+    does; cos and sin are numpy's, so it agrees with the kernel to their rounding).  It reads the slots of a
+    SyntheticIntersectionEnv with traffic="idm".  ref_xy [M, 2]: the ego's route; dt: the step length; K: the other vehicles."""
+
+    def __init__(self, B: int, Q: int, device, backend: str = "torch", ref_xy=None, dt: float = 0.1, K: int = 4):
+        if Q < 1:
+            raise ValueError("episodes_per_env must be >= 1")
+        if backend not in ("hip", "torch"):
+            raise ValueError("backend must be 'hip' or 'torch'")
+        if not 1 <= int(K) <= SLOTS:
+            raise ValueError(f"K must be 1..{SLOTS}")
+        if not float(dt) > 0:
+            raise ValueError("dt must be > 0")
+        if ref_xy is None:
+            raise ValueError("InteractionMetrics needs the ego's route ref_xy [M, 2]")
+        self.B, self.Q, self.K, self.device, self.backend = int(B), int(Q), int(K), torch.device(device), backend
+        self.dt = float(dt)
+        ref = torch.as_tensor(ref_xy, dtype=torch.float64).cpu().contiguous()
+        if ref.ndim != 2 or ref.shape[1] != 2 or not 1 <= ref.shape[0] <= MAX_ROUTE:
+            raise ValueError(f"ref_xy must be [M, 2] with 1 <= M <= {MAX_ROUTE}")
+        self.M = int(ref.shape[0])
+        self.ref_xy = ref.to(self.device)
+        self.conflict = torch.from_numpy(conflict_points(ref.numpy())).to(self.device)
+        z = lambda *s, dt: torch.zeros(s, dtype=dt, device=self.device)
+        self.state_i32 = z(INTERACT_STATE_I32, B, dt=torch.int32)
+        self.state_f64 = z(INTERACT_STATE_F64, B, dt=torch.float64)
+        self.rec_i32 = z(len(INTERACT_I32), B, Q, dt=torch.int32)
+        self.rec_f64 = z(len(INTERACT_F64), B, Q, dt=torch.float64)
+        if backend == "hip":
+            from . import engine as _engine
+            self._lib = _engine.load_library()
+
+    def update(self, env, done, reset=False):
+        B, K = self.B, self.K
+        if getattr(env, "traffic", None) != "idm":
+            raise ValueError("the interaction metrics need an environment with traffic='idm'")
+        shapes = dict(ego=((B, 4), torch.float64), opos=((B, K, 2), torch.float64), ospeed=((B, K), torch.float64),
+                      ohead=((B, K), torch.float64), oactive=((B, K), torch.bool), oroute=((B, K), torch.int32),
+                      oprog=((B, K), torch.float64), otarget=((B, K), torch.float64))
+        arrays = {}
+        for name, (shape, dtype) in shapes.items():
+            t = getattr(env, name)
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"env.{name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+            arrays[name] = _u8(t)
+        if not reset:
+            done = _u8(done)
+            if done.dtype != torch.uint8 or tuple(done.shape) != (B,) or not done.is_contiguous():
+                raise ValueError(f"done must be a contiguous bool / uint8 tensor of shape {(B,)}")
+        if self.backend == "torch":
+            self._numpy_update({k: v.cpu().numpy() for k, v in arrays.items()}, None if reset else done.cpu().numpy(), reset)
+            return
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        rc = self._lib.mpc_interaction_metrics(
+            self.device.index, B, K, self.Q, self.M, 1 if reset else 0, self.dt,
+            *[p(arrays[k]) for k in ("ego", "opos", "ospeed", "ohead", "oactive", "oroute", "oprog", "otarget")],
+            None if reset else p(done), p(self.ref_xy), p(self.conflict), p(self.state_i32), p(self.state_f64),
+            p(self.rec_i32), p(self.rec_f64), ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        if rc != 0:
+            raise RuntimeError(f"mpc_interaction_metrics failed ({rc}): {self._lib.mpc_last_error().decode()}")
+
+    def _sigma(self, x, y):
+        """The ego's arc length along ref_xy [B] (csrc/mpc_interaction.hpp: sigma)."""
+        ref, M = self.ref_xy.cpu().numpy(), self.M
+        nseg = max(M - 1, 1)
+        e0 = ref[:nseg]
+        d = ref[np.minimum(np.arange(nseg) + 1, M - 1)] - e0
+        sx, sy = x[:, None] - e0[None, :, 0], y[:, None] - e0[None, :, 1]
+        dx, dy = d[None, :, 0], d[None, :, 1]
+        dd = dx * dx + dy * dy
+        pos = dd > 0.0
+        t = np.where(pos, (sx * dx + sy * dy) / np.where(pos, dd, 1.0), 0.0)
+        t = np.where(t < 0.0, 0.0, t)
+        t = np.where(t > 1.0, 1.0, t)
+        cx, cy = sx - t * dx, sy - t * dy
+        idx = np.argmin(cx * cx + cy * cy, axis=1)                       # the first of the nearest
+        length = np.sqrt(dd[0])
+        before = np.concatenate([[0.0], np.cumsum(length)])[idx]         # left to right
+        rows = np.arange(x.shape[0])
+        return before + t[rows, idx] * length[idx]
+
+    def _numpy_update(self, s, done, reset):
+        B, K, Q, dt = self.B, self.K, self.Q, self.dt
+        si, sf = self.state_i32.cpu().numpy(), self.state_f64.cpu().numpy()
+        rec_i, rec_f = self.rec_i32.cpu().numpy(), self.rec_f64.cpu().numpy()
+        rows = np.arange(B)
+        fresh = np.ones(B, bool) if reset else done != 0
+        ordinal = np.zeros(B, np.int32) if reset else si[7].copy()
+        if not reset:                                    # the episodes that ended: their records, from the states folded so far
+            w = np.nonzero(fresh & (ordinal < Q))[0]
+            rec_i[:, w, ordinal[w]] = si[:7, w]
+            rec_f[:, w, ordinal[w]] = sf[:3, w]
+            ordinal[w] += 1
+        run_i = np.where(fresh[None], 0, si[:9])
+        run_f = np.where(fresh[None], np.array([0.0, 0.0, np.inf])[:, None], sf[:3])
+        n = run_i[0].astype(np.int64)
+        x, y, th, sp = (s["ego"][:, i] for i in range(4))
+        act = s["oactive"] != 0
+        # ---- (a) yielding and forced braking
+        leads, alts = [], []
+        who = np.full((B, K), -2, np.int64)
+        for j in range(K):
+            xj, yj, hj = s["opos"][:, j, 0], s["opos"][:, j, 1], s["ohead"][:, j]
+            cj, sj = np.cos(hj), np.sin(hj)
+            lead, alt = _Leader(B), _Leader(B)
+            lead.offer(j, xj, yj, hj, cj, sj, -1, x, y, th, sp, act[:, j])
+            for k in range(K):
+                if k != j:
+                    cand = (j, xj, yj, hj, cj, sj, k, s["opos"][:, k, 0], s["opos"][:, k, 1], s["ohead"][:, k], s["ospeed"][:, k],
+                            act[:, j] & act[:, k])
+                    lead.offer(*cand)
+                    alt.offer(*cand)
+            who[:, j] = lead.who
+            leads.append(lead)
+            alts.append(alt)
+        n_yield, hard_mask = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        forced, imposed_sum = np.zeros(B), np.zeros(B)
+        for j in range(K):
+            lead, alt = leads[j], alts[j]
+            v, v0, hj = s["ospeed"][:, j], np.where(act[:, j], s["otarget"][:, j], 1.0), s["ohead"][:, j]
+            lead.drop(_drives_free(j, who[:, j], who))
+            yields = act[:, j] & (lead.who == -1)
+            alt.drop(_drives_free(j, alt.who, who))
+            a_with = _idm_acceleration(v, v0, hj, lead)
+            imposed = np.where(yields, _idm_acceleration(v, v0, hj, alt) - a_with, 0.0)
+            n_yield += yields
+            forced = np.where(yields & (-a_with > forced), -a_with, forced)
+            hard_mask |= (yields & (a_with < -HARD_BRAKE)).astype(np.int32) << j
+            imposed_sum = imposed_sum + imposed
+        # ---- (b) post-encroachment time
+        conflict = self.conflict.cpu().numpy()
+        sigma_c, s_c = conflict[:, 0], conflict[:, 1]
+        sigma, sigma_prev = self._sigma(x, y), sf[3]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            te_old = np.where(fresh[None], -1.0, sf[4:4 + ROUTES])
+            te_new = (n >= 1)[None] & (sigma_c >= 0.0)[:, None] & (te_old < 0.0) & (sigma_prev[None] < sigma_c[:, None]) & \
+                (sigma_c[:, None] <= sigma[None])
+            tau = (n - 1).astype(np.float64)[None] + (sigma_c[:, None] - sigma_prev[None]) / (sigma - sigma_prev)[None]
+            te = np.where(te_new, tau, te_old)
+            conflicts, critical, ego_first = (np.zeros(B, np.int32) for _ in range(3))
+            min_pet = np.full(B, np.inf)
+            for j in range(SLOTS):
+                inside = j < K
+                route_j = s["oroute"][:, j] if inside else np.full(B, -1, np.int32)
+                active = (act[:, j] if inside else np.zeros(B, bool)) & (route_j >= 0) & (route_j < ROUTES)
+                route = np.where(active, route_j, -1).astype(np.int32)
+                prog = np.where(active, s["oprog"][:, j], 0.0) if inside else np.zeros(B)
+                croute, cprog, tv_old = si[9 + j], sf[4 + ROUTES + SLOTS + j], sf[4 + ROUTES + j]
+                same = ~fresh & (n >= 1) & active & (croute == route) & (prog >= cprog)
+                rr = np.clip(route, 0, ROUTES - 1)
+                tv_new = same & (sigma_c[rr] >= 0.0) & (tv_old < 0.0) & (cprog < s_c[rr]) & (s_c[rr] <= prog)
+                tv = np.where(tv_new, (n - 1).astype(np.float64) + (s_c[rr] - cprog) / (prog - cprog),
+                              np.where(same, tv_old, -1.0))
+                te_r, te_r_new = te[rr, rows], te_new[rr, rows]
+                ev = active & (te_r >= 0.0) & (tv >= 0.0) & (te_r_new | tv_new)
+                pet = np.abs(te_r - tv) * dt
+                conflicts += ev
+                critical += ev & (pet < PET_CRITICAL)
+                ego_first += ev & (te_r < tv)
+                min_pet = np.where(ev & (pet < min_pet), pet, min_pet)
+                sf[4 + ROUTES + j], sf[4 + ROUTES + SLOTS + j], si[9 + j] = tv, prog, route
+        sf[4:4 + ROUTES] = te
+        events = hard_mask & ~run_i[8]
+        si[0] = run_i[0] + 1
+        si[1] = run_i[1] + (n_yield > 0)
+        si[2] = run_i[2] + (hard_mask != 0)
+        si[3] = run_i[3] + np.array([bin(int(v)).count("1") for v in events], np.int32)
+        si[4], si[5], si[6] = run_i[4] + conflicts, run_i[5] + critical, run_i[6] + ego_first
+        si[7], si[8] = ordinal, hard_mask
+        sf[0] = np.where(forced > run_f[0], forced, run_f[0])
+        sf[1] = run_f[1] + imposed_sum * dt
+        sf[2] = np.where(min_pet < run_f[2], min_pet, run_f[2])
+        sf[3] = sigma
+        for dst, src in ((self.state_i32, si), (self.state_f64, sf), (self.rec_i32, rec_i), (self.rec_f64, rec_f)):
+            if dst.device.type != "cpu" or dst.data_ptr() != src.ctypes.data:
+                dst.copy_(torch.from_numpy(src))
+
+    def records(self) -> dict:
+        return interaction_records_from_planes(self.rec_i32.cpu().numpy(), self.rec_f64.cpu().numpy())
+
+
 def corner_buildings(setback: float = 6.0, size: float = 30.0, road_half_width: float = 4.0) -> np.ndarray:
     """The four buildings on the corners of the junction of csrc/mpc_synth_env.hpp (lane centres at +-2 m, lane half width
     2 m, so the carriageway ends at +-4 m) as static occluders [4][4][2]: axis-aligned squares, one per quadrant in the order
@@ -533,7 +864,9 @@ class EvalResult:
     synchronise); drive: the drive metrics' records (dict of numpy arrays [B, Q], keys DRIVE_I32 + DRIVE_F64; slot [b, j]
     is the episode of records' slot [b, j]) when the evaluation ran with metrics=True, else None; perception: the totals of
     the perception model (`Perception.totals()`: rows present, seen, out_of_range, occluded, dropped over the whole
-    evaluation, idle steps included) when the evaluation ran with one, else None."""
+    evaluation, idle steps included) when the evaluation ran with one, else None; interaction: the interaction metrics'
+    records (dict of numpy arrays [B, Q], keys INTERACT_I32 + INTERACT_F64, the same slots) when the evaluation ran with
+    interaction=True, else None."""
     records: dict
     dt: float
     steps: int
@@ -541,6 +874,7 @@ class EvalResult:
     seconds: float
     drive: dict | None = None
     perception: dict | None = None
+    interaction: dict | None = None
 
     @property
     def travel_time(self):
@@ -555,14 +889,38 @@ class EvalResult:
         hard_brake_rate (steps below TTC_THRESHOLD / braking harder than HARD_BRAKE, over all steps), the means over
         episodes max_abs_alon_mean, max_abs_alat_mean, rms_jerk_mean, max_steer_rate_mean, mean_xte, and max_xte (the
         largest of any episode).  With a perception model also seen_frac, occluded_frac, out_of_range_frac and dropped_frac:
-        each class as a share of the present rows (0 when no row was ever present)."""
+        each class as a share of the present rows (0 when no row was ever present).  With the interaction metrics also:
+        yield_step_frac and forced_brake_step_frac (states in which a vehicle yields to the ego / brakes for it harder than
+        HARD_BRAKE, over all folded states), forced_brake_events_per_episode, max_forced_decel_mean and max_forced_decel_max
+        over episodes, speed_deficit_per_episode [m/s], conflicts_per_episode, pet_critical_frac and ego_first_frac (of the
+        conflicts; 0 when there is none) and min_pet_p05 (the 5th percentile of min_pet over the episodes with a conflict;
+        inf when there is none)."""
         out = self._base_summary()
         if self.drive is not None:
             out.update(self._drive_summary())
         if self.perception is not None:
             present = max(self.perception["present"], 1)
             out.update({f"{k}_frac": self.perception[k] / present for k in ("seen", "occluded", "out_of_range", "dropped")})
+        if self.interaction is not None:
+            out.update(self._interaction_summary())
         return out
+
+    def _interaction_summary(self) -> dict:
+        d = self.interaction
+        n = int(d["steps"].size)
+        steps_total = max(int(d["steps"].sum()), 1)
+        conflicts = int(d["conflicts"].sum())
+        pets = d["min_pet"][d["conflicts"] > 0]
+        return dict(yield_step_frac=int(d["yield_steps"].sum()) / steps_total,
+                    forced_brake_events_per_episode=int(d["forced_brake_events"].sum()) / n,
+                    forced_brake_step_frac=int(d["forced_brake_steps"].sum()) / steps_total,
+                    max_forced_decel_mean=float(d["max_forced_decel"].mean()),
+                    max_forced_decel_max=float(d["max_forced_decel"].max()),
+                    speed_deficit_per_episode=float(d["speed_deficit"].sum()) / n,
+                    conflicts_per_episode=conflicts / n,
+                    pet_critical_frac=int(d["pet_critical"].sum()) / max(conflicts, 1),
+                    ego_first_frac=int(d["ego_first"].sum()) / max(conflicts, 1),
+                    min_pet_p05=float(np.percentile(pets, 5)) if pets.size else float("inf"))
 
     def _drive_summary(self) -> dict:
         r, d = self.records, self.drive
@@ -606,7 +964,7 @@ def _env_state_names(env):
 @torch.no_grad()
 def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = False, reset_mpc_on_done: bool = False,
                    use_graph: bool | None = None, poll_every: int = 16, seed: int = 0, on_step=None,
-                   metrics: bool = False, perception=None) -> EvalResult:
+                   metrics: bool = False, perception=None, interaction: bool = False) -> EvalResult:
     """Run `agent` in closed loop on the B environments of `env` (a SyntheticIntersectionEnv) until each environment has
     finished `episodes_per_env` episodes; returns their records.
 
@@ -626,6 +984,9 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     step inside the step (so inside the captured graph); the accounting and the drive metrics keep reading the true scene
     and the environment's own flags.  on_step's dict then also holds obs (the true observation), seen (what the agent gets;
     the buffer is overwritten by the next step) and row_class; EvalResult.perception holds the totals.  None: nothing changes.
+    interaction=True: also the interaction metrics of every episode (`InteractionMetrics`, EvalResult.interaction), updated
+    after the drive metrics inside the step (so inside the captured graph) from the environment's slots; ValueError unless the
+    environment has traffic="idm".  on_step's dict is unchanged.
     Every episode ends by EPISODE_STEPS (200) steps, so Q * 200 steps bound the loop; RuntimeError if the episodes are not
     all recorded by then."""
     Q = int(episodes_per_env)
@@ -649,6 +1010,9 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     stats = EpisodeStats(B, Q, dev, "hip" if hip else "torch")
     obs = torch.zeros((B, VEHICLES_COUNT, 8), dtype=torch.float32, device=dev)     # the observation the agent acts on
     drive = DriveMetrics(B, Q, dev, "hip" if hip else "torch", env.ref_xy, env.dt, VEHICLES_COUNT) if metrics else None
+    if interaction and getattr(env, "traffic", None) != "idm":
+        raise ValueError("interaction=True needs an environment with traffic='idm'")
+    inter = InteractionMetrics(B, Q, dev, "hip" if hip else "torch", env.ref_xy, env.dt, env.K) if interaction else None
     if isinstance(perception, dict):
         pkw = dict(env_offset=int(getattr(env, "env_offset", 0)))
         pkw.update(perception)
@@ -670,6 +1034,8 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
         if drive is not None:
             drive.update(info["terminal_obs"], new_obs, out["act"], done)
             inputs.update(terminal_obs=info["terminal_obs"], obs=new_obs, act=out["act"])
+        if inter is not None:
+            inter.update(env, done)
         if perception is None:
             obs.copy_(new_obs)
         else:
@@ -721,6 +1087,8 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     stats.update(env.ego, reset=True)
     if drive is not None:
         drive.update(None, true0, None, None, reset=True)
+    if inter is not None:
+        inter.update(env, None, reset=True)
     if on_step is not None:
         first = dict(reset=True, ego=env.ego, obs=true0) if drive is not None else dict(reset=True, ego=env.ego)
         if perception is not None:
@@ -750,16 +1118,20 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
         raise RuntimeError(f"only {recorded} of {target} episodes recorded after {n} steps (bound {max_steps})")
     return EvalResult(records=stats.records(), dt=float(env.dt), steps=n, env_steps=n * B, seconds=seconds,
                       drive=None if drive is None else drive.records(),
-                      perception=None if perception is None else perception.totals())
+                      perception=None if perception is None else perception.totals(),
+                      interaction=None if inter is None else inter.records())
 
 
-def compare(agents: dict, make_env, episodes_per_env: int = 1, metrics: bool = False, perception=None, **kw) -> dict:
+def compare(agents: dict, make_env, episodes_per_env: int = 1, metrics: bool = False, perception=None,
+            interaction: bool = False, **kw) -> dict:
     """Evaluate every agent on a fresh environment from make_env() (same seed: the HIP environment keys its draws by seed and
     environment id, so every agent meets the same initial episodes) -> {name: summary}; metrics=True adds the drive metrics'
     keys to every summary.  perception (a dict of `Perception`'s keyword arguments, or a Perception whose configuration is
-    copied): every agent gets a fresh Perception with the same seed, hence the same draws on the same steps."""
+    copied): every agent gets a fresh Perception with the same seed, hence the same draws on the same steps.
+    interaction=True adds the interaction metrics' keys (the environments must have traffic="idm")."""
     if isinstance(perception, Perception):
         perception = perception.config
+    extra = dict(interaction=True) if interaction else {}
     return {name: evaluate_agent(agent, make_env(), episodes_per_env, metrics=metrics,
-                                 perception=None if perception is None else dict(perception), **kw).summary()
+                                 perception=None if perception is None else dict(perception), **extra, **kw).summary()
             for name, agent in agents.items()}

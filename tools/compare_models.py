@@ -13,6 +13,7 @@ Agents: pure MPC with the collision cost off and on, the iterative-linear (LTV) 
   python tools/compare_models.py --envs 256 --episodes-per-env 1 --fixture
   python tools/compare_models.py --metrics --traffic idm --envs 256 --fixture
   python tools/compare_models.py --metrics --traffic idm --occlusion buildings --range 60 --sigma-pos 0.2
+  python tools/compare_models.py --metrics --traffic idm --interaction --envs 256
 """
 import argparse
 import json
@@ -34,6 +35,9 @@ def main():
     ap.add_argument("--traffic", default="constant", choices=("constant", "idm"),
                     help="the other vehicles: constant velocity on the approach lanes, or IDM on turning routes")
     ap.add_argument("--metrics", action="store_true", help="also the safety and comfort metrics (evaluate.DriveMetrics)")
+    ap.add_argument("--interaction", action="store_true",
+                    help="also the interaction metrics (evaluate.InteractionMetrics): yielding, forced braking, "
+                         "post-encroachment time; needs --traffic idm")
     ap.add_argument("--range", type=float, default=float("inf"), help="perception: sensing range [m] (default: unlimited)")
     ap.add_argument("--occlusion", default="off", choices=("off", "vehicles", "buildings"),
                     help="perception: vehicles hide what is behind them; buildings: also the four corner buildings "
@@ -46,6 +50,8 @@ def main():
     src.add_argument("--mpcrl", help="an SB3 checkpoint (.zip) of the reference's MPC-RL agent")
     src.add_argument("--fixture", action="store_true", help="MPC-RL: the v0 PPO policy of tests/golden/sb3_policies.npz")
     args = ap.parse_args()
+    if args.interaction and args.traffic != "idm":
+        ap.error("--interaction requires --traffic idm")
 
     import math
 
@@ -85,7 +91,8 @@ def main():
     echo = {} if perception is None else dict(perception={k: finite(v) for k, v in flags.items()})
     for name, agent in agents.items():
         s = evaluate.compare({name: agent}, make_env, args.episodes_per_env, deterministic=args.deterministic,
-                             seed=args.seed, metrics=args.metrics, perception=perception)[name]
+                             seed=args.seed, metrics=args.metrics, perception=perception,
+                             interaction=args.interaction)[name]
         s = {k: finite(v) for k, v in s.items()}
         print(json.dumps(dict(agent=name, traffic=args.traffic, envs=args.envs, episodes_per_env=args.episodes_per_env,
                               **echo, **s)), flush=True)
