@@ -71,14 +71,18 @@ constexpr int kRelaxLat = 7;
 // leaves LDS over.  They get the spare region of mpc_wave.hpp (CTX::kSpareLds) for values that are otherwise recomputed.  Every
 // other build - throughput (LDS is what limits it), runtime horizon, mpc_eval_kernel - keeps the common layout.
 constexpr bool wave_spare_lds(int NC, int OCC, int RELAX) { return NC > 0 && OCC == kWaveOccLat && RELAX == kRelaxLat; }
+// The same builds have registers to spare below their limit of 256: they keep same-lane values between neighbouring
+// stage-parallel phases in registers (CTX::kCarry, the phase carry of mpc_wave.hpp).  No other build does.
+constexpr bool wave_phase_carry(int NC, int OCC, int RELAX) { return wave_spare_lds(NC, OCC, RELAX); }
 
 // ---------------------------------------------------------------------------------------------------
 // wave-cooperative kernel: ONE wave64 per instance (mpc_wave.hpp); workgroup = 1 wave, grid = B
 // ---------------------------------------------------------------------------------------------------
-template <int NC, int RELAX = 0, bool SPARE = false>
+template <int NC, int RELAX = 0, bool SPARE = false, bool CARRY = false>
 struct WaveCtx : mpc::wave::WaveOpsT<RELAX> {
     static constexpr int kN = NC;
     static constexpr bool kSpareLds = SPARE;
+    static constexpr bool kCarry = CARRY;
     const double *table;  // [M][REF_COLS] in global memory (wave-uniform index in the serial parts -> scalar loads)
     int e0, M;
     __device__ __forceinline__ WaveCtx(mpc::wave::lds_double_t *l, const double *t, int e, int m)
@@ -144,7 +148,7 @@ __global__ __launch_bounds__(kBlock, OCC) void mpc_solve_wave_kernel(
     if (nveh) P.V = min(P.V, max(0, nveh[b]));   // vehicles actually present in this instance
     const int lane = threadIdx.x;
     constexpr int SL = mpc::wave::stage_slots(CC);
-    using Ctx = WaveCtx<NC, RELAX, wave_spare_lds(NC, OCC, RELAX)>;
+    using Ctx = WaveCtx<NC, RELAX, wave_spare_lds(NC, OCC, RELAX), wave_phase_carry(NC, OCC, RELAX)>;
     Ctx ctx((mpc::wave::lds_double_t *)smem, ref5, ego_index[b], M);
     stage_problem<CC>(ctx, P, b, lane, N, SL, ref5, M, vref, others, Vin);
     __syncthreads();

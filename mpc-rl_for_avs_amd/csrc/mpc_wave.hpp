@@ -199,6 +199,26 @@ struct spare_lds { static constexpr bool value = false; };
 template <class CTX>
 struct spare_lds<CTX, decltype((void)CTX::kSpareLds)> { static constexpr bool value = CTX::kSpareLds; };
 
+// The PHASE CARRY (only in a build whose context says CTX::kCarry = true: the same latency builds): values that lane k = stage k
+// forms in one stage-parallel phase and forms again, from the same words, in a later phase of the same iteration stay in the
+// lane's registers in between (PerLane locals of the iteration) - no store, no load, no wait.  Which values: Solver::kCarry*.
+template <class CTX, class = void>
+struct phase_carry { static constexpr bool value = false; };
+template <class CTX>
+struct phase_carry<CTX, decltype((void)CTX::kCarry)> { static constexpr bool value = CTX::kCarry; };
+// a x b + c rounded once on the device and twice on the host, whose build contracts nothing: for the sums below that the
+// device build without the carry contracts in one particular way, which the build with the carry has to state
+MPC_HD double fused(double a, double b, double c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return fma(a, b, c);
+#else
+    return a * b + c;
+#endif
+}
+#ifndef MPC_CARRY_PARTS
+#define MPC_CARRY_PARTS 7   // development aid (A/B builds): bit 0 dual step, bit 1 dynamics trigonometry, bit 2 the sweep's fallback
+#endif
+
 // doubles of LDS one instance needs: stage arrays + constants + other vehicles (+ the spare region of the builds that have one)
 MPC_HD constexpr int lds_doubles(bool cc, int N, int V, bool spare = false) {
     return stage_slots(cc) * (N + 1) + SC_SIZE + (cc ? 4 * V : 0) + (spare ? spare_doubles(cc, N, V) : 0);
@@ -372,6 +392,20 @@ struct Solver {
 
     PerLane<double> red_a, red_b, red_c, red_w;   // per-lane operands of the wave reductions
     PerLane<int> ls_feas;                  // line search: the lanes of row t = trial t stayed inside the fraction-to-the-boundary box
+    // phase carry (see phase_carry above), lane k = stage k:
+    //   kCarryDual   the dual step of the lane's four bound pairs (controls of stage k, theta and v of node k + 1):
+    //                step-length phase -> dual update of the same iteration
+    //   kCarryTrig   sin / cos(theta + beta), sin / cos(beta), beta', beta'' at (theta_k, delta_k) of the current iterate:
+    //                preparation phase -> every exact assembly attempt of the same iteration
+    //   kCarrySweep  the sweep's per-stage Gauss-Newton fallback takes the six of stage k from lane k (needs kCarryTrig)
+    static constexpr bool kCarry = phase_carry<CTX>::value;
+    static constexpr bool kCarryDual = kCarry && (MPC_CARRY_PARTS & 1) != 0;
+    static constexpr bool kCarryTrig = kCarry && (MPC_CARRY_PARTS & 2) != 0;
+    static constexpr bool kCarrySweep = kCarryTrig && (MPC_CARRY_PARTS & 4) != 0;
+    // Both are locals of one iteration, not members: the lanes beyond the horizon never write them, and a member that only
+    // some lanes write is carried around the iteration loop for the others - live through every phase of the solve.
+    struct DualCarry { PerLane<double> dzl[4], dzu[4]; };
+    struct TrigCarry { PerLane<double> sn, cn, sb, cb, bp, bpp; };
     // d = 1 discontinuity of the collision cost (archive/pure_mpc.py:189-196: 100/d^2 outside, 1000/d^2 inside).  A
     // vehicle that a rejected trial took across d = 1 inwards is kept outside from then on by the constraint
     // |p_k - o_jk|^2 - 1 >= 0 of that node (one per node, multiplier W_ZW): the cost jumps upwards there, so a minimiser
@@ -475,7 +509,7 @@ struct Solver {
     }
     // one backward sweep over the stages with the stage Hessians / gradients the assembly phase left in LDS; false: a stage's
     // control block was not positive definite (also not with its Gauss-Newton terms alone)
-    MPC_HD bool sweep4(int CB, int AB, double mu, double delta_w, bool gn, double &dV1) {
+    MPC_HD bool sweep4(int CB, int AB, double mu, double delta_w, bool gn, double &dV1, TrigCarry &trc) {
         // ---- terminal value function: barrier terms of (theta, v)_N
         double tsig[2], tgr[2];
         for (int i = 0; i < 2; ++i) {
@@ -570,16 +604,31 @@ struct Solver {
                 {
                     const double v = S(k, CB + W_X + 3);
                     double Sn, Cn, sb, cb_, bp, bpp;
-                    dyn_eval(trig(), S(k, CB + W_X + 2), S(k, CB + W_U + 1), Sn, Cn, sb, cb_);
-                    beta_derivs(sb, cb_, bp, bpp);
+                    if constexpr (kCarrySweep) {   // what lane k formed in the preparation phase
+                        Sn = c.lane_get(trc.sn, k); Cn = c.lane_get(trc.cn, k); sb = c.lane_get(trc.sb, k);
+                        cb_ = c.lane_get(trc.cb, k); bp = c.lane_get(trc.bp, k); bpp = c.lane_get(trc.bpp, k);
+                    } else {
+                        dyn_eval(trig(), S(k, CB + W_X + 2), S(k, CB + W_U + 1), Sn, Cn, sb, cb_);
+                        beta_derivs(sb, cb_, bp, bpp);
+                    }
                     const double yy0 = S(k + 1, W_Y + 0), yy1 = S(k + 1, W_Y + 1), yy2 = S(k + 1, W_Y + 2);
-                    const double g = -(yy0 * Cn + yy1 * Sn), h = -(yy0 * Sn - yy1 * Cn);
-                    wdd = dt * v * (g * bp * bp + h * bpp) + dt * yy2 * v * kInvWheelbase * (-sb * bp * bp + cb_ * bpp);
+                    double g, h;
+                    if constexpr (kCarrySweep) {   // (as in the assembly phase: this site's own contractions of the build that recomputes)
+                        g = -fused(yy0, Cn, yy1 * Sn);
+                        h = -fused(yy0, Sn, -(yy1 * Cn));
+                        const double cg = fused(g * bp, bp, h * bpp), cy = fused(cb_, bpp, -sb * bp * bp);
+                        wdd = fused(dt * v, cg, dt * yy2 * v * kInvWheelbase * cy);
+                    } else {
+                        g = -(yy0 * Cn + yy1 * Sn);
+                        h = -(yy0 * Sn - yy1 * Cn);
+                        wdd = dt * v * (g * bp * bp + h * bpp) + dt * yy2 * v * kInvWheelbase * (-sb * bp * bp + cb_ * bpp);
+                    }
                     if (k >= 1) {
                         wtt = dt * v * g;
                         wtv = dt * h;
                         wtd = dt * v * g * bp;
-                        wvd = dt * h * bp + dt * yy2 * cb_ * bp * kInvWheelbase;
+                        if constexpr (kCarrySweep) wvd = fused(dt * h, bp, dt * yy2 * cb_ * bp * kInvWheelbase);
+                        else wvd = dt * h * bp + dt * yy2 * cb_ * bp * kInvWheelbase;
                         if (CC) {
                             q00 = S(k, W_QG + 0) - S(k, W_Q + 0);
                             q01 = S(k, W_QG + 1) - S(k, W_Q + 1);
@@ -1369,6 +1418,8 @@ struct Solver {
 
         for (iter = 0; iter <= P.max_iter; ++iter) {
             const int CB = cur * 6;
+            DualCarry dlc;   // phase carry of this iteration (kCarryDual, kCarryTrig); unused and gone in the other builds
+            TrigCarry trc;
             if (iter == kBoostIter) c.template set_priority<3>();
             c.tick(T_DUALUPD);
             // ============ collision potential: gradient, exact and Gauss-Newton curvature at the nodes 1 .. N - 1 - a loop over
@@ -1409,6 +1460,10 @@ struct Solver {
                     double Sn, Cn, sb, cb_, bp, bpp;
                     dyn_eval(trig(), xk2, u1, Sn, Cn, sb, cb_);
                     beta_derivs(sb, cb_, bp, bpp);
+                    if constexpr (kCarryTrig) {
+                        trc.sn.at(lane) = Sn; trc.cn.at(lane) = Cn; trc.sb.at(lane) = sb;
+                        trc.cb.at(lane) = cb_; trc.bp.at(lane) = bp; trc.bpp.at(lane) = bpp;
+                    }
                     S(k, W_LIN + 2, 0.0); S(k, W_LIN + 3, 0.0); S(k, W_LIN + 7, 0.0); S(k, W_LIN + 11, 0.0);   // the structural zeros of F[c][i]
                     S(k, W_LIN + LIN_A02, -dt * xk3 * Sn);
                     S(k, W_LIN + LIN_A03, dt * Cn);
@@ -1654,15 +1709,33 @@ struct Solver {
                     double wdd = 0.0, wtt = 0.0, wtv = 0.0, wtd = 0.0, wvd = 0.0;
                     if (!gn) {
                         double Sn, Cn, sb, cb_, bp, bpp;
-                        dyn_eval(trig(), S(k, CB + W_X + 2), u1, Sn, Cn, sb, cb_);
-                        beta_derivs(sb, cb_, bp, bpp);
+                        if constexpr (kCarryTrig) {   // the preparation phase's, of the same (theta_k, delta_k)
+                            Sn = trc.sn.at(lane); Cn = trc.cn.at(lane); sb = trc.sb.at(lane);
+                            cb_ = trc.cb.at(lane); bp = trc.bp.at(lane); bpp = trc.bpp.at(lane);
+                        } else {
+                            dyn_eval(trig(), S(k, CB + W_X + 2), u1, Sn, Cn, sb, cb_);
+                            beta_derivs(sb, cb_, bp, bpp);
+                        }
                         const double yy0 = S(k + 1, W_Y + 0), yy1 = S(k + 1, W_Y + 1), yy2 = S(k + 1, W_Y + 2);
-                        const double g = -(yy0 * Cn + yy1 * Sn), h = -(yy0 * Sn - yy1 * Cn);
-                        wdd = dt * v * (g * bp * bp + h * bpp) + dt * yy2 * v * kInvWheelbase * (-sb * bp * bp + cb_ * bpp);
-                        wtt = dt * v * g;
-                        wtv = dt * h;
-                        wtd = dt * v * g * bp;
-                        wvd = dt * h * bp + dt * yy2 * cb_ * bp * kInvWheelbase;
+                        if constexpr (kCarryTrig) {
+                            // The same sums with the contractions of the build that recomputes stated: left to itself the compiler
+                            // moves what depends on the carried values alone into the preparation phase and contracts it there
+                            // in another way.
+                            const double g = -fused(yy0, Cn, yy1 * Sn), h = -fused(yy0, Sn, -(yy1 * Cn));
+                            const double cg = fused(g * bp, bp, h * bpp), cy = fused(cb_, bpp, -sb * bp * bp);
+                            wdd = fused(dt * yy2 * v * kInvWheelbase, cy, dt * v * cg);
+                            wtt = dt * v * g;
+                            wtv = dt * h;
+                            wtd = dt * v * g * bp;
+                            wvd = fused(dt * yy2 * cb_ * bp, kInvWheelbase, dt * h * bp);
+                        } else {
+                            const double g = -(yy0 * Cn + yy1 * Sn), h = -(yy0 * Sn - yy1 * Cn);
+                            wdd = dt * v * (g * bp * bp + h * bpp) + dt * yy2 * v * kInvWheelbase * (-sb * bp * bp + cb_ * bpp);
+                            wtt = dt * v * g;
+                            wtv = dt * h;
+                            wtd = dt * v * g * bp;
+                            wvd = dt * h * bp + dt * yy2 * cb_ * bp * kInvWheelbase;
+                        }
                     }
                     double l00 = 0.0, l01 = 0.0, l11 = 0.0, h22 = 0.0, h23 = 0.0, h33 = 0.0, hv0 = 0.0, hv1 = 0.0, hv2 = 0.0,
                            hv3 = 0.0;
@@ -1729,7 +1802,7 @@ struct Solver {
                     S(k, A_HV6, rc * u0 + rdk * (u0 - um0) + sgr[2]);
                     S(k, A_HV7, rc * u1 + rdk * (u1 - um1) + sgr[3]);
                 });
-                ok = sweep4(CB, AB, mu, delta_w, gn, dV1);
+                ok = sweep4(CB, AB, mu, delta_w, gn, dV1, trc);
                 if (!ok) {
                     ++nmod;
                     if (gn_skip > 0) skipped_gn = true;
@@ -1814,6 +1887,10 @@ struct Solver {
                     const double dzl = (mu - zl * d) * rsl - zl, dzu = (mu + zu * d) * rsu - zu;
                     if (-dzl * rdd > rdn * zl) { rdn = -dzl; rdd = zl; }
                     if (-dzu * rdd > rdn * zu) { rdn = -dzu; rdd = zu; }
+                    if constexpr (kCarryDual) {
+                        dlc.dzl[i].at(lane) = dzl;
+                        dlc.dzu[i].at(lane) = dzu;
+                    }
                 }
                 if (CC && any_wall && k + 1 < N) {
                     const double wjv = S(k + 1, W_WJ);
@@ -1861,9 +1938,17 @@ struct Solver {
                         const int kk = isu ? k : k + 1;
                         const int sv = isu ? (W_U + j) : (W_X + 2 + j);
                         const int szl = isu ? (W_ZUL + j) : (W_ZXL + j), szu = isu ? (W_ZUU + j) : (W_ZXU + j);
-                        const double val = S(kk, CB + sv), d = S(kk, W_Y + i);
-                        const double zl = S(kk, szl), zu = S(kk, szu);
-                        const double dzl = (mu - zl * d) * frcp(val - lo) - zl, dzu = (mu + zu * d) * frcp(hi - val) - zu;
+                        double zl, zu, dzl, dzu;
+                        if constexpr (kCarryDual) {   // the step-length phase's, of the same words
+                            zl = S(kk, szl); zu = S(kk, szu);
+                            dzl = dlc.dzl[i].at(lane);
+                            dzu = dlc.dzu[i].at(lane);
+                        } else {
+                            const double val = S(kk, CB + sv), d = S(kk, W_Y + i);
+                            zl = S(kk, szl); zu = S(kk, szu);
+                            dzl = (mu - zl * d) * frcp(val - lo) - zl;
+                            dzu = (mu + zu * d) * frcp(hi - val) - zu;
+                        }
                         const double vn = S(kk, NB + sv);
                         const double ml = mu * frcp(vn - lo), mh = mu * frcp(hi - vn);
                         S(kk, szl, fmax2(fmin2(zl + (dzl > 0.0 ? 1.0 : a_du) * dzl, c.fresh(1e10) * ml), c.fresh(1e-10) * ml));

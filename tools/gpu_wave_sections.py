@@ -54,7 +54,11 @@ def run(inp, idx, cc, V, label):
 
 
 inp = synth.solver_inputs(4096, 8, seed=0, N=20)
-run(inp, np.array([0]), True, 8, "typical instance alone")
-run(inp, np.array([77]), True, 8, "straggler (instance 77) alone")
+if "--instances" in sys.argv:      # --instances 0,1037: each of them alone
+    for i in sys.argv[sys.argv.index("--instances") + 1].split(","):
+        run(inp, np.array([int(i)]), True, 8, f"instance {int(i)} alone")
+else:
+    run(inp, np.array([0]), True, 8, "typical instance alone")
+    run(inp, np.array([77]), True, 8, "straggler (instance 77) alone")
 if "--batch" in sys.argv:
     run(inp, np.arange(4096), True, 8, "whole batch (config 3)")

@@ -17,9 +17,13 @@ namespace {
 #ifndef PROF_RELAX
 #define PROF_RELAX 0      // 15: the latency build's configuration (everything hoisted, fused linear step, precomputed trial bounds)
 #endif
+#ifndef PROF_CARRY
+#define PROF_CARRY 0      // 1: with the phase carry of the latency builds (CTX::kCarry)
+#endif
 struct ProfCtx : mpc::wave::WaveOpsT<PROF_RELAX> {
     static constexpr int kN = 20;
     static constexpr bool kFine = PROF_FINE != 0;     // also attribute the parts of a rollout stage
+    static constexpr bool kCarry = PROF_CARRY != 0;
     const double *table;
     int e0, M;
     unsigned long long *acc;   // [T_COUNT] accumulators of this instance in LDS, behind the solver's words (lane 0 adds)
