@@ -363,6 +363,39 @@ int mpc_rollout_finish(int32_t device, int32_t T, int32_t B, int32_t A, int32_t 
                        double gae_lambda, float *advantages, float *returns, void *stream);
 
 /*
+ * mpc_policy_control (an addition within ABI 8: old clients never call it, nothing else changes) - the step of the end-to-end
+ * baseline, the reference's fourth model (agents/ppo_agent.py: an SB3 MlpPolicy whose two outputs are the vehicle's controls,
+ * no MPC in between).  The network, weight layout, noise and outputs of mpc_policy_act at A = 2 (Gaussian policies only; the
+ * baseline does not use gSDE): actions [B][2] = mean + std * noise, values [B], log_probs [B] are bit for bit what
+ * mpc_policy_act writes for the same inputs, and noise [B][2] is read (noise_step == NULL) or drawn and left there, keyed by
+ * (noise_seed, env_offset + b, noise_step[0], component), exactly as there.  control [B][2] f64 is the action in physical
+ * units, as highway-env's ContinuousAction maps it: clip to [-1, 1] (always: the clip belongs to the environment's action
+ * type, not to the algorithm; `actions` stays unclipped), then acceleration = 5 * a0 m/s^2 and steering = pi / 4 * a1 rad
+ * (acceleration_range / steering_range of config/config.py:27-32) - what mpc_synth_env_step takes as `action`.
+ * Device pointers, enqueue only on `stream`, never synchronises (capturable in a hipGraph); no scratch, no atomics.  From
+ * MPC_POLICY_CONTROL_TILE_FROM environments on, one workgroup serves MPC_POLICY_CONTROL_TILE consecutive environments (each
+ * weight is loaded once per tile, not once per environment); below, where the tiles would leave most of the GPU idle, one
+ * environment per workgroup as in mpc_policy_act.  The results do not depend on the tile.  DESIGN.md 5.2 has the measurement
+ * behind both numbers.
+ * Errors (MPC_ERR_INVALID_ARG): B < 0, H2 odd, < 2 or > 256, a NULL pointer other than noise_step / stream.  B == 0: nothing
+ * to do, no device call.
+ *
+ * mpc_policy_control_tile: the same launch with the tile chosen by the caller, tile = 1, 2, 4, 8 or 16 (anything else is
+ * refused) - every tile computes the same bits; it exists so that tools/bench_policy_control.py can time them side by side.
+ */
+#define MPC_POLICY_CONTROL_TILE 4
+#define MPC_POLICY_CONTROL_TILE_FROM 2048
+int mpc_policy_control(int32_t device, int32_t B, int32_t H2, const float *obs, const float *w1, const float *b1, const float *w2,
+                       const float *b2, const float *wh, const float *bh, const float *std_, const float *c0, float *noise,
+                       uint64_t noise_seed, int32_t env_offset, const int64_t *noise_step, float *actions, float *values,
+                       float *log_probs, double *control, void *stream);
+int mpc_policy_control_tile(int32_t tile, int32_t device, int32_t B, int32_t H2, const float *obs, const float *w1,
+                            const float *b1, const float *w2, const float *b2, const float *wh, const float *bh,
+                            const float *std_, const float *c0, float *noise, uint64_t noise_seed, int32_t env_offset,
+                            const int64_t *noise_step, float *actions, float *values, float *log_probs, double *control,
+                            void *stream);
+
+/*
  * mpc_episode_stats (an addition within ABI 8: old clients never call it, nothing else changes) - per-episode accounting of
  * a closed-loop evaluation of B environments (the reference's model comparison, main/model_comparison.py:40-100, with the
  * per-environment update in csrc/mpc_episode_stats.hpp).  Device pointers, enqueue only on `stream`, never synchronises

@@ -686,6 +686,67 @@ __global__ __launch_bounds__(mpc::glue::kMaxHidden2) void mpc_policy_act_sde_ker
                                 mpc_weights ? mpc_weights + (size_t)b * 3 : nullptr, mpc_ref_speed ? mpc_ref_speed + b : nullptr);
 }
 
+// the end-to-end baseline's step (agents/ppo_agent.py: the policy's two outputs are the controls, no MPC): the network of
+// mpc_policy_act_kernel at A = 2 for a tile of E consecutive environments per workgroup.  Without a solve behind it the forward
+// IS the step, and at one workgroup per environment every workgroup reads all weights again; here thread j holds unit j of
+// all E environments, loads each weight once and feeds E running sums from LDS (inputs interleaved [i][E], read as a
+// broadcast).  Each sum is accumulated as mpc_policy_act_kernel accumulates it, so the outputs agree bit for bit.
+// LDS (dynamic): x [80][E] | h1 [2H][E] | h2 [2H][E] | heads [3][E].  An environment the last tile lacks reads environment
+// B - 1 and writes nothing; every thread reaches every barrier.
+template <int E>
+__global__ __launch_bounds__(mpc::glue::kMaxHidden2) void mpc_policy_control_kernel(
+    int B, int H2, const float *__restrict__ obs, mpc::glue::PolicyWeights W, float *noise, unsigned long long noise_seed,
+    int env_offset, const long long *__restrict__ noise_step, float *__restrict__ actions, float *__restrict__ values,
+    float *__restrict__ log_probs, double *__restrict__ control) {
+    namespace glue = mpc::glue;
+    constexpr int O = glue::kObsDim;
+    extern __shared__ float s_tile[];
+    float *s_x = s_tile, *s_h1 = s_x + O * E, *s_h2 = s_h1 + H2 * E, *s_head = s_h2 + H2 * E;
+    const int b0 = blockIdx.x * E, j = threadIdx.x;
+    glue::stage_tile<E>(obs, B, b0, j, (int)blockDim.x, s_x);
+    // thread e < E finishes environment b0 + e; its noise stays in registers: drawn here (and left in `noise`) or handed in
+    const bool mine = j < E && b0 + j < B;
+    float z[2] = {0.0f, 0.0f};
+    if (mine) {
+        const int b = b0 + j;
+        if (noise_step) {
+            for (int a = 0; a < 2; ++a) z[a] = noise[(size_t)b * 2 + a] = glue::policy_noise(noise_seed, env_offset + b, *noise_step, a);
+        } else {
+            for (int a = 0; a < 2; ++a) z[a] = noise[(size_t)b * 2 + a];
+        }
+    }
+    __syncthreads();
+    if (j < H2) glue::layer1_tile<E>(W, H2, s_x, j, s_h1 + j * E);
+    __syncthreads();
+    if (j < H2) glue::layer2_tile<E>(W, H2, s_h1, j, s_h2 + j * E);
+    __syncthreads();
+    if (j <= 2) glue::head_tile<E>(W, H2, 2, s_h2, j, s_head + j * E);
+    __syncthreads();
+    if (mine) {
+        const int b = b0 + j;
+        float out4[4];
+        double u[2];
+        glue::finish_control<E>(W, s_head, j, z, out4, u);
+        actions[(size_t)b * 2 + 0] = out4[0];
+        actions[(size_t)b * 2 + 1] = out4[1];
+        values[b] = out4[2];
+        log_probs[b] = out4[3];
+        control[(size_t)b * 2 + 0] = u[0];
+        control[(size_t)b * 2 + 1] = u[1];
+    }
+}
+
+template <int E>
+static void launch_policy_control(hipStream_t stream, int B, int H2, const float *obs, const mpc::glue::PolicyWeights &W, float *noise,
+                                  uint64_t noise_seed, int env_offset, const int64_t *noise_step, float *actions, float *values,
+                                  float *log_probs, double *control) {
+    const int threads = (H2 + 63) / 64 * 64;
+    const size_t lds = (size_t)(mpc::glue::kObsDim + 2 * H2 + 3) * E * sizeof(float);
+    hipLaunchKernelGGL(mpc_policy_control_kernel<E>, dim3((unsigned)((B + E - 1) / E)), dim3((unsigned)threads), lds, stream, B, H2, obs,
+                       W, noise, (unsigned long long)noise_seed, env_offset, reinterpret_cast<const long long *>(noise_step), actions,
+                       values, log_probs, control);
+}
+
 __global__ __launch_bounds__(128) void mpc_rollout_record_kernel(mpc::glue::RecordArgs R, int T, long long *__restrict__ pos_dev,
                                                                  int32_t *__restrict__ ticket,
                                                                  unsigned long long *__restrict__ counts,
@@ -1840,6 +1901,43 @@ int mpc_policy_act_sde(int32_t device, int32_t B, int32_t A, int32_t H2, const f
                        actions, values, log_probs, version_v1 ? mpc_weights : nullptr, version_v1 ? nullptr : mpc_ref_speed);
     HIP_TRY(hipGetLastError());
     return MPC_OK;
+}
+
+int mpc_policy_control_tile(int32_t tile, int32_t device, int32_t B, int32_t H2, const float *obs, const float *w1, const float *b1,
+                            const float *w2, const float *b2, const float *wh, const float *bh, const float *std_, const float *c0,
+                            float *noise, uint64_t noise_seed, int32_t env_offset, const int64_t *noise_step, float *actions,
+                            float *values, float *log_probs, double *control, void *stream_) {
+    if (B < 0 || H2 < 2 || H2 > mpc::glue::kMaxHidden2 || (H2 & 1))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_policy_control: bad size (2 x hidden even and <= 256)");
+    if (tile != 1 && tile != 2 && tile != 4 && tile != 8 && tile != 16)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_policy_control_tile: tile must be 1, 2, 4, 8 or 16");
+    if (!obs || !w1 || !b1 || !w2 || !b2 || !wh || !bh || !std_ || !c0 || !noise || !actions || !values || !log_probs || !control)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_policy_control: null pointer");
+    if (B == 0) return MPC_OK;
+    HIP_TRY(hipSetDevice(device));
+    const mpc::glue::PolicyWeights W{w1, b1, w2, b2, wh, bh, std_, c0};
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+#define MPC_CONTROL_TILE(E) \
+    case E: launch_policy_control<E>(stream, B, H2, obs, W, noise, noise_seed, env_offset, noise_step, actions, values, log_probs, control); break
+    switch (tile) {
+        MPC_CONTROL_TILE(1);
+        MPC_CONTROL_TILE(2);
+        MPC_CONTROL_TILE(4);
+        MPC_CONTROL_TILE(8);
+        MPC_CONTROL_TILE(16);
+    }
+#undef MPC_CONTROL_TILE
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_policy_control(int32_t device, int32_t B, int32_t H2, const float *obs, const float *w1, const float *b1, const float *w2,
+                       const float *b2, const float *wh, const float *bh, const float *std_, const float *c0, float *noise,
+                       uint64_t noise_seed, int32_t env_offset, const int64_t *noise_step, float *actions, float *values,
+                       float *log_probs, double *control, void *stream_) {
+    // the tile pays once its workgroups still fill the GPU (measured: DESIGN.md 5.2); the bits are the same either way
+    return mpc_policy_control_tile(B >= MPC_POLICY_CONTROL_TILE_FROM ? MPC_POLICY_CONTROL_TILE : 1, device, B, H2, obs, w1, b1, w2, b2, wh, bh, std_, c0, noise, noise_seed,
+                                   env_offset, noise_step, actions, values, log_probs, control, stream_);
 }
 
 int mpc_rollout_record(int32_t device, int32_t T, int32_t B, int32_t A, int32_t cols, int32_t keep_terminal, float *row,

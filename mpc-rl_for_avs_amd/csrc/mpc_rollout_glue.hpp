@@ -1,4 +1,4 @@
-// mpc_rollout_glue.hpp - the two pieces of a rollout step (BASELINE configs 4-5) that are neither the MPC nor the environment:
+// mpc_rollout_glue.hpp - the pieces of a rollout step (BASELINE configs 4-5) that are neither the MPC nor the environment:
 //
 //   policy_act      the SB3 `MlpPolicy` shaped actor-critic the reference's PPO_MPC / A2C_MPC build (trainers/trainer.py:375-449,
 //                   net_arch default [64, 64], tanh; obs 10 x 8 = 80 inputs; agents/ppo_mpc.py:390-394 `self.policy(obs_tensor)`):
@@ -6,6 +6,9 @@
 //                   diagonal, both heads in one matrix - the layout ActorCritic.refresh_fused() keeps), the Gaussian sample
 //                   mean + std * noise, its log-probability, the clip to the Box(-1, 1) action space (:399-407) and the mapping
 //                   of the action onto the MPC's inputs (v0 :410-414 reference speed, v1 :416-420 cost weights).
+//   policy_control  the end-to-end baseline's step (agents/ppo_agent.py: the policy's two outputs are the controls, no MPC): the same
+//                   network at A = 2 for a tile of E environments per workgroup (stage_tile .. finish_control), and map_control,
+//                   highway-env's ContinuousAction mapping of the action onto acceleration and steering.
 //   rollout_record  the buffer row of the step (rollout_buffer.add, :462-469), the carry-over of observation and episode
 //                   starts to the next step, and the episode counters.
 //   rollout_finish  what ends a rollout (:471-476 `rollout_buffer.compute_returns_and_advantage`, SB3's RolloutBuffer used as
@@ -73,6 +76,56 @@ MPC_HD float head_unit(const PolicyWeights &W, int H2, int A, const float *h2, i
     for (int i = lo; i < lo + H; ++i) s = fmaf(h2[i], W.wh[i * (A + 1) + o], s);
     return s;
 }
+// ---- mpc_policy_control: a tile of E consecutive environments per workgroup, thread j = hidden unit j of all of them.
+// thread j of `nthreads` stages its share of the tile's observations (environments b0 .. b0 + E - 1) as x [80][E]; an
+// environment the batch lacks reads environment B - 1 (its results are never written)
+template <int E>
+MPC_HD void stage_tile(const float *obs, int B, int b0, int j, int nthreads, float *x) {
+    for (int k = j; k < kObsDim * E; k += nthreads) {
+        const int e = k / kObsDim, i = k - e * kObsDim;
+        const int b = b0 + e < B ? b0 + e : B - 1;
+        x[i * E + e] = obs[(size_t)b * kObsDim + i];
+    }
+}
+// layer1_unit / layer2_unit / head_unit for a TILE of E environments: unit j for all E of them.  The inputs lie
+// interleaved, x [80][E] / h [2H][E], so the E values of input i are adjacent; each weight is loaded once and feeds E running
+// sums, and every sum still takes its inputs in index order with the same fused multiply-adds - bit for bit what
+// layer1_unit / layer2_unit / head_unit return for each environment alone.  out [E].
+template <int E>
+MPC_HD void layer1_tile(const PolicyWeights &W, int H2, const float *x, int j, float *out) {
+    float s[E];
+    for (int e = 0; e < E; ++e) s[e] = W.b1[j];
+#pragma unroll 16
+    for (int i = 0; i < kObsDim; ++i) {
+        const float w = W.w1[i * H2 + j];
+        for (int e = 0; e < E; ++e) s[e] = fmaf(x[i * E + e], w, s[e]);
+    }
+    for (int e = 0; e < E; ++e) out[e] = tanhf(s[e]);
+}
+template <int E>
+MPC_HD void layer2_tile(const PolicyWeights &W, int H2, const float *h1, int j, float *out) {
+    const int H = H2 / 2, lo = j < H ? 0 : H;
+    float s[E];
+    for (int e = 0; e < E; ++e) s[e] = W.b2[j];
+#pragma unroll 16
+    for (int i = lo; i < lo + H; ++i) {
+        const float w = W.w2[i * H2 + j];
+        for (int e = 0; e < E; ++e) s[e] = fmaf(h1[i * E + e], w, s[e]);
+    }
+    for (int e = 0; e < E; ++e) out[e] = tanhf(s[e]);
+}
+template <int E>
+MPC_HD void head_tile(const PolicyWeights &W, int H2, int A, const float *h2, int o, float *out) {
+    const int H = H2 / 2, lo = o < A ? 0 : H;
+    float s[E];
+    for (int e = 0; e < E; ++e) s[e] = W.bh[o];
+#pragma unroll 16
+    for (int i = lo; i < lo + H; ++i) {
+        const float w = W.wh[i * (A + 1) + o];
+        for (int e = 0; e < E; ++e) s[e] = fmaf(h2[i * E + e], w, s[e]);
+    }
+    for (int e = 0; e < E; ++e) out[e] = s[e];
+}
 // the clip to the Box(-1, 1) action space (PPO) and the mapping of the action onto the MPC's inputs (v0: reference speed,
 // v1: the three cost weights)
 MPC_HD void map_action(const float *actions, int version_v1, int clip, const double *default_weights, double *mpc_weights,
@@ -90,6 +143,19 @@ MPC_HD void map_action(const float *actions, int version_v1, int clip, const dou
         if (mpc_ref_speed) *mpc_ref_speed = clipped(0);
     }
 }
+// the end-to-end baseline (agents/ppo_agent.py): the policy's two outputs ARE the vehicle's controls.  highway-env's
+// ContinuousAction clips the action to [-1, 1] and maps it linearly onto acceleration_range / steering_range
+// (config/config.py:27-32: [-5, 5] m/s^2 and [-pi/4, pi/4] rad); for these symmetric ranges that is a multiplication by the upper
+// bound.  The clip belongs to the environment's action type, so it is applied whatever the algorithm; the stored action stays
+// unclipped.
+MPC_HD void map_control(const float *actions, double *control) {
+    auto clipped = [&](int a) {
+        const float v = actions[a];
+        return (double)(v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v));
+    };
+    control[0] = 5.0 * clipped(0);
+    control[1] = (env::kPiE / 4) * clipped(1);
+}
 // sample, log-probability, clip, MPC inputs of one environment.  out_mean [A + 1] = heads; noise [A]
 MPC_HD void finish_action(const PolicyWeights &W, int A, const float *heads, const float *noise, int version_v1, int clip,
                           const double *default_weights, float *actions, float *value, float *log_prob, double *mpc_weights,
@@ -102,6 +168,31 @@ MPC_HD void finish_action(const PolicyWeights &W, int A, const float *heads, con
     *value = heads[A];
     *log_prob = -0.5f * q - W.c0[0];
     map_action(actions, version_v1, clip, default_weights, mpc_weights, mpc_ref_speed);
+}
+
+// environment e of a tile (mpc_policy_control, A = 2): heads [3][E] as head_tile leaves them, noise [2] -> finish_action's
+// sample, value and log-probability and the controls of map_control.  out4 = action 0, action 1, value, log-probability
+template <int E>
+MPC_HD void finish_control(const PolicyWeights &W, const float *heads, int e, const float *noise, float *out4, double *control) {
+    const float h[3] = {heads[e], heads[E + e], heads[2 * E + e]};
+#if defined(__HIP_DEVICE_COMPILE__)
+    // finish_action leaves the contraction of q += noise * noise to the compiler, and the compiler decides by context: in
+    // mpc_policy_act_kernel (a loop over a run-time A) hipcc makes every term a fused multiply-add, q = fma(n1, n1, n0 * n0),
+    // while the same source inlined here at a constant A = 2 became a packed multiply and an add (two rounded squares, one
+    // ulp apart in the log-probability).  So the device form of that arithmetic is stated, not left to the context;
+    // -0.5 * q is exact, fused or not.  tests/test_ppo_baseline_gpu.py holds the two kernels to the same bits.
+    {
+#pragma clang fp contract(off)
+        out4[0] = fmaf(noise[0], W.std[0], h[0]);
+        out4[1] = fmaf(noise[1], W.std[1], h[1]);
+        out4[2] = h[2];
+        const float q = fmaf(noise[1], noise[1], noise[0] * noise[0]);
+        out4[3] = -0.5f * q - W.c0[0];
+    }
+#else
+    finish_action(W, 2, h, noise, 0, 1, nullptr, out4, out4 + 2, out4 + 3, nullptr, nullptr);
+#endif
+    map_control(out4, control);
 }
 
 // ---- gSDE (generalized State-Dependent Exploration, stable-baselines3's StateDependentNoiseDistribution at the settings of

@@ -62,7 +62,7 @@ _EXPORTS = ["mpc_version", "mpc_last_error", "mpc_default_config", "mpc_default_
             "mpc_set_reference", "mpc_solve_batch", "mpc_workspace_bytes", "mpc_predict_batch",
             "mpc_reset_env_state", "mpc_reset_env_mask", "mpc_get_env_state", "mpc_get_last_inputs",
             "mpc_ltv_solve_batch", "mpc_ltv_predict_batch", "mpc_env_state_bytes", "mpc_save_env_state",
-            "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_interaction_metrics", "mpc_perceive", "mpc_eval_nlp", "mpc_streams_overlap"]
+            "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_policy_control", "mpc_policy_control_tile", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_interaction_metrics", "mpc_perceive", "mpc_eval_nlp", "mpc_streams_overlap"]
 ABI_VERSION = 8          # MPC_ABI_VERSION of include/mpc_mi355x.h this binding is written for
 MAX_OTHERS = 16
 _lib = None
@@ -152,6 +152,11 @@ def load_library(path: str | None = None):
     lib.mpc_policy_act_sde.argtypes = [ctypes.c_int32] * 4 + [vp] * 9 + [ctypes.c_uint64, ctypes.c_int32, vp, vp] + \
         [ctypes.c_int32] * 3 + [vp] * 6
     lib.mpc_policy_act_sde.restype = ctypes.c_int
+    # device, B, H2, obs + 8 weight pointers + noise, noise_seed, env_offset, noise_step, actions, values, log_probs, control, stream
+    lib.mpc_policy_control.argtypes = [ctypes.c_int32] * 3 + [vp] * 10 + [ctypes.c_uint64, ctypes.c_int32, vp] + [vp] * 5
+    lib.mpc_policy_control.restype = ctypes.c_int
+    lib.mpc_policy_control_tile.argtypes = [ctypes.c_int32] + lib.mpc_policy_control.argtypes
+    lib.mpc_policy_control_tile.restype = ctypes.c_int
     lib.mpc_rollout_record.argtypes = [ctypes.c_int32] * 6 + [vp] * 22
     lib.mpc_rollout_record.restype = ctypes.c_int
     lib.mpc_rollout_finish.argtypes = [ctypes.c_int32] * 6 + [vp] * 4 + [ctypes.c_double] * 2 + [vp] * 3

@@ -968,7 +968,8 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     """Run `agent` in closed loop on the B environments of `env` (a SyntheticIntersectionEnv) until each environment has
     finished `episodes_per_env` episodes; returns their records.
 
-    agent: PureMPC_Agent, IterativeLinearMPC_Agent or MPCRLAgent (anything with `act_batch_torch`).  The MPC's action goes to the
+    agent: PureMPC_Agent, IterativeLinearMPC_Agent, MPCRLAgent or PPOAgent (anything with `act_batch_torch`; the end-to-end
+    PPOAgent may have no engine at all, there is then no MPC state to reset or reserve).  The MPC's action goes to the
     environment in physical units (acceleration m/s^2, steering rad), as in the collector; the reference divides it by 5 and
     pi / 3 (model_comparison.py:55) only because highway-env's ContinuousAction rescales it again.
     deterministic: MPC-RL policies act with their mean; otherwise they sample, keyed by `seed` (and the environment's global id
@@ -996,7 +997,7 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
         raise ValueError("poll_every must be >= 1")
     if not callable(getattr(agent, "act_batch_torch", None)):
         raise ValueError(f"unsupported agent {type(agent).__name__}: needs act_batch_torch (PureMPC_Agent, "
-                         "IterativeLinearMPC_Agent, MPCRLAgent)")
+                         "IterativeLinearMPC_Agent, MPCRLAgent, PPOAgent)")
     B, dev = env.num_envs, env.device
     hip = getattr(env, "backend", "torch") == "hip"
     eng = _engine_of(agent)
@@ -1024,7 +1025,7 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     def step():
         out = agent.act_batch_torch(obs, **kw)
         new_obs, reward, done, info = env.step(out["act"])
-        if reset_mpc_on_done:
+        if reset_mpc_on_done and eng is not None:
             eng.reset_env_mask_torch(_u8(done))
         elif warm:                    # a new episode must not start from the old one's plan
             eng.reset_env_mask_torch(_u8(done), warm_only=True)
@@ -1055,7 +1056,8 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     if use_graph:
         # warm-up and capture really step the environment: its state is put back afterwards, and the resets below start the
         # evaluation from there, so a graph run and an eager run see the same episodes
-        eng.reserve_envs(B)
+        if eng is not None:
+            eng.reserve_envs(B)
         names = _env_state_names(env)
         snap = {n: getattr(env, n).clone() for n in names}
         gen_state = env.gen.get_state()

@@ -576,6 +576,57 @@ class ActorCritic(torch.nn.Module):
                     sde_sample_freq=int(data.get("sde_sample_freq", -1)), action_dim=A, algorithm=algorithm)
         return pol, meta
 
+    def save_sb3(self, path, version=None, algorithm="ppo", **extra):
+        """The inverse of load_sb3: a zip with `policy.pth` (the state dict under stable-baselines3's names, _SB3_KEYS, on the
+        CPU) and a `data` JSON with use_sde, sde_sample_freq (-1 unless given), version and the fields load_sb3 tells the
+        algorithm by: "ppo" writes clip_range, n_epochs and gae_lambda, "a2c" gae_lambda alone, None neither.  `extra`
+        adds or overrides JSON fields (n_steps, sde_sample_freq, ...; JSON-serialisable values only).  It stores a trained
+        policy of this package for a later load_sb3 / from_sb3 - the reference's save / load.  Loading the file with
+        stable-baselines3 itself is NOT verified here (stable-baselines3 is not available to this project's tests): SB3's own
+        `data` holds more fields, several of them pickled, than this file carries."""
+        import io
+        import json
+        import zipfile
+        if algorithm not in ("ppo", "a2c", None):
+            raise ValueError("algorithm must be ppo, a2c or None")
+        data = dict(use_sde=self.use_sde, sde_sample_freq=-1, version=version)
+        if algorithm == "ppo":
+            data.update(clip_range=0.2, n_epochs=10, gae_lambda=0.95)
+        elif algorithm == "a2c":
+            data.update(gae_lambda=1.0)
+        data.update(extra)
+        own = self.state_dict()
+        sd = {k: own[name].detach().to("cpu").contiguous().clone() for k, name in self._SB3_KEYS.items()}
+        blob = io.BytesIO()
+        torch.save(sd, blob)
+        with zipfile.ZipFile(path, "w") as z:
+            z.writestr("data", json.dumps(data))
+            z.writestr("policy.pth", blob.getvalue())
+
+
+CONTROL_SCALE = (5.0, math.pi / 4)     # acceleration_range / steering_range upper bounds (config/config.py:27-32)
+
+
+def control_scale(device):
+    return torch.tensor(CONTROL_SCALE, dtype=torch.float64, device=device)
+
+
+def map_control(actions, out=None, scale=None):
+    """The end-to-end baseline's action [B, 2] -> physical controls [B, 2] float64 (acceleration m/s^2, steering rad) as
+    highway-env's ContinuousAction maps it: clip to [-1, 1], then scale onto the symmetric acceleration / steering ranges.
+    The torch form of csrc/mpc_rollout_glue.hpp::map_control, same bits.  `out`: written in place (fixed address); `scale`:
+    control_scale(device) made beforehand (inside a captured graph nothing may be copied from the host)."""
+    c = torch.clamp(actions, -1.0, 1.0).to(torch.float64)
+    return torch.mul(c, control_scale(actions.device) if scale is None else scale, out=out)
+
+
+def _check_direct_policy(policy):
+    if int(getattr(policy, "action_dim", 0)) != 2:
+        raise ValueError("the end-to-end baseline needs a policy with action_dim 2 (acceleration, steering)")
+    if getattr(policy, "use_sde", False):
+        raise ValueError("the end-to-end baseline is a Gaussian policy: gSDE (use_sde=True) is not supported "
+                         "(the reference's agents/ppo_agent.py leaves SB3's default, off)")
+
 
 class RolloutBuffer:
     """[n_steps, B, ...] device tensors + GAE (the arithmetic of SB3's RolloutBuffer, which the reference uses as is).
@@ -663,6 +714,12 @@ class BatchedCollector:
 
     version "v0": the policy's 1-d action is the reference-speed override (agents/ppo_mpc.py:410-414);
     version "v1": its first three components are the cost weights (agents/ppo_mpc.py:416-420).
+    version "direct": the end-to-end baseline (agents/ppo_agent.py) - the policy's two outputs are the controls (map_control:
+    clipped to [-1, 1] whatever the algorithm, then 5 m/s^2 and pi / 4 rad per unit) and NO MPC runs: a step is policy ->
+    controls -> env.step -> buffer row.  `engine` is only the library handle of the fused step (mpc_policy_control) and may
+    be None on the torch path; last_mpc = dict(act, status, iters) with zero status / iters, mpc_unconverged stays 0.  The
+    MPC's settings (collision_cost, warm_start, reset_mpc_on_done, gather_actions, throughput), an action_dim other than 2
+    and gSDE are refused.
     algorithm "ppo" clips the action to the Box(-1, 1) bounds before use and bootstraps truncated episodes with the
     value of the terminal observation (agents/ppo_mpc.py:399-407, 451-461); "a2c" does neither
     (agents/a2c_mpc.py:138-144).
@@ -685,10 +742,18 @@ class BatchedCollector:
                  gather_actions: bool = False, seed: int = 0, warm_start: bool = False,
                  use_graph: bool | None = None, throughput: bool = False, fused_glue: bool | None = None,
                  sde_sample_freq: int = -1):
-        if version not in ("v0", "v1") or algorithm not in ("ppo", "a2c"):
-            raise ValueError("version must be v0|v1 and algorithm ppo|a2c")
+        if version not in ("v0", "v1", "direct") or algorithm not in ("ppo", "a2c"):
+            raise ValueError("version must be v0|v1|direct and algorithm ppo|a2c")
         if version == "v1" and policy.action_dim < 3:
             raise ValueError("v1 needs an action of at least 3 components (speed, control, input_diff weights)")
+        self.direct = version == "direct"
+        if self.direct:
+            _check_direct_policy(policy)
+            given = dict(collision_cost=collision_cost, warm_start=warm_start, reset_mpc_on_done=reset_mpc_on_done,
+                         gather_actions=gather_actions, throughput=throughput)
+            bad = [k for k, v in given.items() if v]
+            if bad:
+                raise ValueError(f"version 'direct' runs no MPC: {', '.join(bad)} cannot be set")
         self.env, self.policy, self.engine = env, policy, engine
         self.version, self.algorithm = version, algorithm
         self.collision_cost, self.reset_mpc_on_done, self.gather_actions = collision_cost, reset_mpc_on_done, gather_actions
@@ -721,7 +786,7 @@ class BatchedCollector:
         # + MPC inputs in ONE launch (mpc_policy_act) and buffer row + carry-over + counters in one (mpc_rollout_record)
         # instead of ~40 torch kernels - csrc/mpc_rollout_glue.hpp
         can_fuse = (dev.type == "cuda" and getattr(env, "backend", "") == "hip" and isinstance(policy, ActorCritic) and
-                    hasattr(engine, "predict_batch_torch") and hasattr(engine, "_lib") and
+                    (self.direct or hasattr(engine, "predict_batch_torch")) and hasattr(engine, "_lib") and
                     policy.pi[0].in_features == VEHICLES_COUNT * 8 and 2 * policy.pi[0].out_features <= 256 and
                     policy.action_dim <= 8 and policy.log_std.dtype == torch.float32)
         if fused_glue and not can_fuse:
@@ -735,12 +800,20 @@ class BatchedCollector:
             self._fg = dict(act=z(B, A), val=z(B), logp=z(B), w=z(B, 3, dt=torch.float64), rs=z(B, dt=torch.float64),
                             ticket=z(1, dt=torch.int32), noise=z(B, A), step=z(1, dt=torch.int64))
             self._noise_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+            if self.direct:
+                self._fg.update(ctrl=z(B, 2, dt=torch.float64))
             if self.use_sde:
                 # gSDE: the exploration epoch the kernel keys its matrices by; a rollout draws from epochs sde_epoch ..
                 # sde_epoch + span - 1 (one per sde_sample_freq steps), and _begin_rollout moves past them
                 self._fg["sde_epoch"] = z(1, dt=torch.int64)
                 f = self.sde_sample_freq
                 self._sde_span = 1 if f <= 0 else -(-int(n_steps) // f)
+        if self.direct:
+            # what stands in for the MPC's outputs: the controls (written by the step) and a solve status that is always 0
+            zi = lambda: torch.zeros(B, dtype=torch.int32, device=dev)
+            self._direct = dict(act=self._fg["ctrl"] if self.fused_glue else torch.zeros((B, 2), dtype=torch.float64, device=dev),
+                                status=zi(), iters=zi())
+            self._control_scale = control_scale(dev)
         if self.use_sde and not self.fused_glue:
             H = policy.log_std.shape[0]
             self.sde_noise = torch.zeros((B, H, policy.action_dim), dtype=policy.log_std.dtype, device=dev)
@@ -748,7 +821,8 @@ class BatchedCollector:
         # captured once as a hipGraph and replayed; eager on the CPU, with stand-in engines, and when the actions are
         # all-gathered (the collective stays outside the graph)
         if use_graph is None:
-            use_graph = dev.type == "cuda" and hasattr(engine, "reserve_envs") and hasattr(engine, "predict_batch_torch")
+            use_graph = dev.type == "cuda" and (self.fused_glue if self.direct else
+                                                hasattr(engine, "reserve_envs") and hasattr(engine, "predict_batch_torch"))
         self.use_graph = bool(use_graph)
         self._graph = None
         self.graph_fallback_reason = None
@@ -855,9 +929,40 @@ class BatchedCollector:
             raise RuntimeError(f"mpc_rollout_record failed ({rc}): {lib.mpc_last_error().decode()}")
 
     @torch.no_grad()
+    def _rollout_step_direct_fused(self):
+        """version "direct" with the glue kernels: mpc_policy_control (policy, sample, controls), the environment, and
+        mpc_rollout_record with the controls in the MPC action's place and the all-zero status."""
+        import ctypes
+        lib, env, pol, buf, fg = self.engine._lib, self.env, self.policy, self.buffer, self._fg
+        f, B, dev = pol._fz, env.num_envs, env.device
+        p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        rc = lib.mpc_policy_control(dev.index, B, f["b1"].numel(), p(self._last_obs), p(f["w1"]), p(f["b1"]), p(f["w2"]),
+                                    p(f["b2"]), p(f["wh"]), p(f["bh"]), p(f["std"]), p(f["c0"]), p(fg["noise"]),
+                                    self._noise_seed, int(getattr(env, "env_offset", 0)), p(fg["step"]), p(fg["act"]),
+                                    p(fg["val"]), p(fg["logp"]), p(fg["ctrl"]), stream)
+        if rc != 0:
+            raise RuntimeError(f"mpc_policy_control failed ({rc}): {lib.mpc_last_error().decode()}")
+        self.last_mpc = self._direct
+        env.step(fg["ctrl"])
+        o = env._out
+        keep = buf.terminal_obs is not None
+        rc = lib.mpc_rollout_record(dev.index, buf.n_steps, B, 2, buf._cols, 1 if keep else 0, p(buf._row), p(buf.mpc_actions),
+                                    p(buf.pos_dev), p(fg["ticket"]), p(self._last_obs), p(self._last_episode_starts), p(fg["act"]),
+                                    p(fg["val"]), p(fg["logp"]), p(fg["ctrl"]), p(self._direct["status"]), p(o["obs"]),
+                                    p(o["reward"]), p(o["done"]), p(o["terminal_obs"]) if keep else None,
+                                    p(o["truncated"]) if keep else None, p(o["crashed"]), p(o["arrived"]),
+                                    p(self._roll["counts"]), p(self._roll["dones"]), p(fg["step"]), stream)
+        if rc != 0:
+            raise RuntimeError(f"mpc_rollout_record failed ({rc}): {lib.mpc_last_error().decode()}")
+
+    @torch.no_grad()
     def _rollout_step(self, device_pos: bool = False):
         if self.fused_glue:
-            self._rollout_step_fused()
+            if self.direct:
+                self._rollout_step_direct_fused()
+            else:
+                self._rollout_step_fused()
             if not device_pos:
                 self.buffer.pos += 1
             return
@@ -867,10 +972,14 @@ class BatchedCollector:
         feed = getattr(self, "noise_feed", None)
         noise = feed.pop(0) if feed else (self.sde_noise if self.use_sde else None)
         actions, values, log_probs = self.policy.act(obs, generator=self.gen, noise=noise)
-        weights, ref_speed = self.mpc_inputs(actions)
-        self._mpc_out = self.engine.predict_batch_torch(obs, weights, ref_speed, collision_cost=self.collision_cost,
-                                                        warm_start=self.warm_start, out=self._mpc_out, **self._mpc_kw)
-        self.last_mpc = self._mpc_out
+        if self.direct:                  # the end-to-end baseline: the action is the control, nothing to solve
+            map_control(actions, out=self._direct["act"], scale=self._control_scale)
+            self.last_mpc = self._direct
+        else:
+            weights, ref_speed = self.mpc_inputs(actions)
+            self._mpc_out = self.engine.predict_batch_torch(obs, weights, ref_speed, collision_cost=self.collision_cost,
+                                                            warm_start=self.warm_start, out=self._mpc_out, **self._mpc_kw)
+            self.last_mpc = self._mpc_out
         mpc_action = self.last_mpc["act"]
         if self.gather_actions:
             from . import sharding
@@ -1342,3 +1451,106 @@ class MPCRLAgent:
         out = self.predict_batch(torch.as_tensor(obs, dtype=torch.float32)[None], deterministic, generator)
         act = out["act"][0]
         return act.cpu().numpy() if isinstance(act, torch.Tensor) else act
+
+
+class PPOAgent:
+    """The reference's end-to-end baseline (agents/ppo_agent.py `PPOAgent`, the `ppo` model of main/model_comparison.py): an SB3
+    MlpPolicy whose two outputs are the vehicle's controls, with no MPC in between.  The environment's action type
+    (highway-env's ContinuousAction) clips the action to [-1, 1] and scales it onto the acceleration / steering ranges
+    (map_control); here that mapping is part of the agent, because the batched environments take physical controls.
+    Gaussian policies with action_dim 2 only.  `engine` (an MPCEngine) is used for its library alone - the fused policy step
+    mpc_policy_control on a GPU; None runs the policy in torch, on any device."""
+
+    def __init__(self, policy: ActorCritic, engine=None):
+        _check_direct_policy(policy)
+        self.policy, self.engine = policy, engine
+
+    @classmethod
+    def from_sb3(cls, path, engine=None, device="cpu"):
+        """Load a checkpoint (ActorCritic.load_sb3; what ActorCritic.save_sb3 writes) and wrap it -> (agent, meta)."""
+        pol, meta = ActorCritic.load_sb3(path, device=device)
+        return cls(pol, engine), meta
+
+    @torch.no_grad()
+    def policy_output(self, obs, deterministic: bool = True, generator=None):
+        self.policy.eval()
+        obs = torch.as_tensor(obs, dtype=torch.float32, device=self.policy.log_std.device)
+        actions, _, _ = self.policy(obs, deterministic=deterministic, generator=generator)
+        return actions
+
+    def predict(self, obs, deterministic: bool = True, generator=None):
+        """One observation [10, 8] -> the normalised action [2] float32 clipped to [-1, 1], what SB3's `model.predict`
+        returns and the reference hands to env.step (agents/ppo_agent.py; deterministic=True is its default)."""
+        actions = self.policy_output(torch.as_tensor(obs, dtype=torch.float32)[None], deterministic, generator)
+        return torch.clamp(actions[0], -1.0, 1.0).cpu().numpy()
+
+    @torch.no_grad()
+    def predict_batch(self, obs_batch, deterministic: bool = True, generator=None):
+        """obs_batch [B, 10, 8] -> dict(act [B, 2] f64 physical controls, rl_action [B, 2] the unclipped action, status and
+        iters [B] int32 zeros: there is no solve)."""
+        actions = self.policy_output(obs_batch, deterministic, generator)
+        zi = lambda: torch.zeros(actions.shape[0], dtype=torch.int32, device=actions.device)
+        return dict(act=map_control(actions), rl_action=actions, status=zi(), iters=zi())
+
+    # ---- closed-loop evaluation (evaluate.evaluate_agent): the contract of MPCRLAgent.act_batch_torch ---------------------
+    @torch.no_grad()
+    def act_batch_torch(self, obs, deterministic: bool = False, seed: int = 0, env_offset: int = 0):
+        """obs float32 device tensor [B, 10, 8] -> dict(act [B, 2] f64 controls, status, iters (zeros), step, generator).
+        Enqueue-only, the same output tensors every call.  On a GPU with an engine one mpc_policy_control launch, its noise
+        keyed by (seed, env_offset + b, step) - `step` the int64 [1] counter the caller advances once per step
+        (mpc_episode_stats does); otherwise ActorCritic.act, drawing from `generator` (seeded by seed), and map_control.
+        deterministic: the mean.  restart_actions() puts the counter / generator back to the start."""
+        import ctypes
+        B, dev = int(obs.shape[0]), obs.device
+        key = (B, dev, bool(deterministic), int(seed), int(env_offset))
+        st = getattr(self, "_act_state", None)
+        if st is None or st["key"] != key:
+            st = self._act_init(key)
+        pol = self.policy
+        if st["fused"]:
+            f, lib = pol._fz, self.engine._lib
+            p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+            rc = lib.mpc_policy_control(dev.index, B, f["b1"].numel(), p(obs), p(f["w1"]), p(f["b1"]), p(f["w2"]), p(f["b2"]),
+                                        p(f["wh"]), p(f["bh"]), p(f["std"]), p(f["c0"]), p(st["noise"]),
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset), p(st["step"]), p(st["actions"]),
+                                        p(st["val"]), p(st["logp"]), p(st["out"]["act"]),
+                                        ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            if rc != 0:
+                raise RuntimeError(f"mpc_policy_control failed ({rc}): {lib.mpc_last_error().decode()}")
+        else:
+            actions, _, _ = pol.act(obs, generator=st["gen"], noise=st["noise"] if deterministic else None)
+            map_control(actions, out=st["out"]["act"], scale=st["scale"])
+        return dict(st["out"], step=st["step"], generator=st["gen"])
+
+    def _act_init(self, key):
+        B, dev, deterministic, seed, _ = key
+        pol = self.policy
+        pol.eval()
+        pol.refresh_fused()
+        z = lambda *sh, dt=torch.float32: torch.zeros(sh, dtype=dt, device=dev)
+        fused = (dev.type == "cuda" and hasattr(self.engine, "_lib") and pol.pi[0].in_features == VEHICLES_COUNT * 8 and
+                 2 * pol.pi[0].out_features <= 256 and pol.log_std.dtype == torch.float32)
+        st = dict(key=key, fused=fused, step=None, gen=None, noise=z(B, 2), scale=control_scale(dev),
+                  out=dict(act=z(B, 2, dt=torch.float64), status=z(B, dt=torch.int32), iters=z(B, dt=torch.int32)))
+        if fused:
+            st.update(actions=z(B, 2), val=z(B), logp=z(B))
+            if not deterministic:              # drawn by the kernel; deterministic reads the all-zero noise instead
+                st["step"] = z(1, dt=torch.int64)
+        elif not deterministic:
+            st["gen"] = torch.Generator(device=dev)
+            st["gen"].manual_seed(seed)
+        self._act_state = st
+        return st
+
+    @torch.no_grad()
+    def restart_actions(self):
+        """Put the evaluation's noise counter / generator back to where act_batch_torch started them (in place: a captured
+        graph reads them at their addresses)."""
+        st = getattr(self, "_act_state", None)
+        if st is None:
+            return
+        self.policy.refresh_fused()
+        if st["step"] is not None:
+            st["step"].zero_()
+        if st["gen"] is not None:
+            st["gen"].manual_seed(st["key"][3])

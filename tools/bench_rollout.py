@@ -6,6 +6,8 @@ Prints one JSON line per configuration: env-steps/s (= MPC solves/s) and the tim
   python tools/bench_rollout.py --envs 256 2048                    # one GPU (config 4 and config 5's total on one GPU)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 tools/bench_rollout.py \
          --envs 2048                                               # config 5: 256 envs per GPU, RCCL gather of actions
+  python tools/bench_rollout.py --version direct --envs 256 8192 65536 --rollouts 20
+                                                                   # the end-to-end PPO baseline: policy -> controls, no MPC
 """
 import argparse
 import json
@@ -22,7 +24,9 @@ def main():
     ap.add_argument("--envs", type=int, nargs="+", default=[256, 2048])
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--others", type=int, default=4)
-    ap.add_argument("--version", default="v0")
+    ap.add_argument("--version", default="v0", choices=("v0", "v1", "direct"),
+                    help="v0 / v1: MPC-RL; direct: the end-to-end baseline, the policy's outputs are the controls (no MPC)")
+    ap.add_argument("--rollouts", type=int, default=1, help="rollouts in the timed window (a direct step is short: time several)")
     ap.add_argument("--algorithm", default="ppo", choices=("ppo", "a2c"))
     ap.add_argument("--no-graph", dest="graph", action="store_false",
                     help="run the step eagerly (launches from Python, MPC time measured with events) instead of replaying the "
@@ -86,7 +90,8 @@ def main():
         B = hi - lo
         G = max(1, min(a.groups, B))
         torch.manual_seed(1234)          # the same untrained policy in every run and on every rank: reproducible rows
-        pol = rollout.ActorCritic(3 if a.version == "v1" else 1, use_sde=a.sde).to(dev)
+        direct = a.version == "direct"
+        pol = rollout.ActorCritic({"v1": 3, "direct": 2}.get(a.version, 1), use_sde=a.sde).to(dev)
         engs, cols = [], []
         for g in range(G):
             glo, ghi = sharding.shard_range(B, g, G)
@@ -95,8 +100,8 @@ def main():
                                                    backend=a.env_backend, env_offset=lo + glo, traffic=a.traffic)
             engs.append(e_g)
             cols.append(rollout.BatchedCollector(env, pol, e_g, version=a.version, algorithm=a.algorithm, n_steps=a.steps,
-                                                 collision_cost=False, gather_actions=use_dist and G == 1,
-                                                 seed=g, use_graph=a.graph, throughput=G > 1,
+                                                 collision_cost=False, gather_actions=use_dist and G == 1 and not direct,
+                                                 seed=g, use_graph=a.graph, throughput=G > 1 and not direct,
                                                  sde_sample_freq=a.sde_sample_freq))
         col = cols[0] if G == 1 else rollout.PipelinedCollector(cols)
         col.collect_rollouts()                                   # warm-up (allocations, first launches)
@@ -113,24 +118,25 @@ def main():
             return call
 
         graph = all(c._graph is not None for c in cols)          # sharded runs capture the RCCL gather inside the graph
-        if not graph:                                            # a replayed graph does not pass through Python
+        if not graph and not direct:                             # a replayed graph does not pass through Python
             for e_g in engs:
                 e_g.predict_batch_torch = timed(e_g.predict_batch_torch)
         torch.cuda.synchronize()
         if use_dist:
             dist.barrier()
         t0 = time.perf_counter()
-        stats = col.collect_rollouts()
+        for _ in range(max(1, a.rollouts)):
+            stats = col.collect_rollouts()
         torch.cuda.synchronize()
         if use_dist:
             dist.barrier()
-        dt = time.perf_counter() - t0
+        dt = (time.perf_counter() - t0) / max(1, a.rollouts)
         if use_dist:
             tt = torch.tensor([dt], dtype=torch.float64, device=dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
         dist_info = None
-        if use_dist and G == 1:
+        if use_dist and G == 1 and not direct:
             assert col.gathered_actions.shape == (total, 2) and col.gathered_status.shape == (total,)
             dist_info = dict(backend=dist.get_backend(), world_size=world,
                              gathered_actions_shape=list(col.gathered_actions.shape),
@@ -140,10 +146,10 @@ def main():
         dm = sum(e0.elapsed_time(e1) for e0, e1 in events) * 1e-3
         st = torch.cat([c.last_mpc["status"] for c in cols]).cpu().numpy()
         if rank == 0:
-            print(json.dumps(dict(config=f"{total} envs on {world} GPU(s), {a.others} other vehicles, {a.version}/{a.algorithm}, "
-                                         f"horizon 20, max_iter {a.max_iter}, tol {a.tol:g}" + (f", {G} groups on {G} streams" if G > 1 else "") + (", hipGraph step" if graph else ", eager step") + f", {cols[0].env.backend} environment, {a.traffic} traffic" + (f", gSDE (sample freq {a.sde_sample_freq})" if a.sde else ""),
+            print(json.dumps(dict(config=f"{total} envs on {world} GPU(s), {a.others} other vehicles, {a.version}/{a.algorithm}, " +
+                                         ("no MPC" if direct else f"horizon 20, max_iter {a.max_iter}, tol {a.tol:g}") + (f", {G} groups on {G} streams" if G > 1 else "") + (", hipGraph step" if graph else ", eager step") + f", {cols[0].env.backend} environment, {a.traffic} traffic" + (f", gSDE (sample freq {a.sde_sample_freq})" if a.sde else ""),
                               envs=total, n_gpus=world, distributed=dist_info, graph_fallback_reason=cols[0].graph_fallback_reason, fused_glue=cols[0].fused_glue, groups=G, graph=bool(graph), env_backend=cols[0].env.backend, traffic=a.traffic,
-                              steps_per_env=a.steps, env_steps_per_s=total * a.steps / dt, ms_per_step=dt / a.steps * 1e3,
+                              steps_per_env=a.steps, rollouts_timed=max(1, a.rollouts), env_steps_per_s=total * a.steps / dt, ms_per_step=dt / a.steps * 1e3,
                               mpc_ms_per_step=(dm / a.steps * 1e3) if events else None, episodes=stats["episodes"], crashed=stats["crashed"],
                               arrived=stats["arrived"], converged_frac=float(((st == 0) | ((st >= 5) & (st <= 7))).mean()),
                               converged_frac_rollout=1.0 - stats["mpc_unconverged"] / float(total * a.steps) * world)), flush=True)

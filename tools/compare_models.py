@@ -8,12 +8,15 @@ route keeping; a value that does not exist, such as the closest gap when no vehi
 in the JSON line, which then also holds the share of present rows that were seen, occluded, out of range and dropped.
 
 Agents: pure MPC with the collision cost off and on, the iterative-linear (LTV) agent, and MPC-RL - an SB3 `.zip` given with
---mpcrl, or with --fixture the v0 PPO (gSDE) policy rebuilt from tests/golden/sb3_policies.npz.
+--mpcrl, or with --fixture the v0 PPO (gSDE) policy rebuilt from tests/golden/sb3_policies.npz.  --ppo PATH adds the reference's
+fourth model, the end-to-end PPO baseline (rollout.PPOAgent: the policy's outputs are the controls, no MPC), from a checkpoint
+in the layout ActorCritic.save_sb3 writes; --ppo-random adds it with a seeded untrained policy, so the row exists anywhere.
 
   python tools/compare_models.py --envs 256 --episodes-per-env 1 --fixture
   python tools/compare_models.py --metrics --traffic idm --envs 256 --fixture
   python tools/compare_models.py --metrics --traffic idm --occlusion buildings --range 60 --sigma-pos 0.2
   python tools/compare_models.py --metrics --traffic idm --interaction --envs 256
+  python tools/compare_models.py --envs 256 --fixture --ppo baseline.zip
 """
 import argparse
 import json
@@ -49,6 +52,9 @@ def main():
     src = ap.add_mutually_exclusive_group()
     src.add_argument("--mpcrl", help="an SB3 checkpoint (.zip) of the reference's MPC-RL agent")
     src.add_argument("--fixture", action="store_true", help="MPC-RL: the v0 PPO policy of tests/golden/sb3_policies.npz")
+    base = ap.add_mutually_exclusive_group()
+    base.add_argument("--ppo", metavar="PATH", help="the end-to-end PPO baseline: a checkpoint (.zip) as ActorCritic.save_sb3 writes it")
+    base.add_argument("--ppo-random", action="store_true", help="the end-to-end PPO baseline with an untrained policy seeded by --seed")
     args = ap.parse_args()
     if args.interaction and args.traffic != "idm":
         ap.error("--interaction requires --traffic idm")
@@ -78,6 +84,11 @@ def main():
         path = sde_host.sb3_zip(tmp.name, "ppo_v0")
     if path:
         agents["mpcrl"], _ = rollout.MPCRLAgent.from_sb3(path, MPCEngine(horizon=20, device=0), device=dev)
+    if args.ppo:
+        agents["ppo"], _ = rollout.PPOAgent.from_sb3(args.ppo, MPCEngine(horizon=20, device=0), device=dev)
+    elif args.ppo_random:
+        torch.manual_seed(args.seed)
+        agents["ppo"] = rollout.PPOAgent(rollout.ActorCritic(2).to(dev), MPCEngine(horizon=20, device=0))
     make_env = lambda: rollout.SyntheticIntersectionEnv(args.envs, device=dev, seed=args.seed, n_others=4,
                                                          traffic=args.traffic)
     flags = dict(range=args.range, occlusion=args.occlusion, dropout=args.dropout,
