@@ -1,4 +1,6 @@
-"""ctypes binding of the C ABI (include/mpc_mi355x.h) - the only way Python reaches the HIP kernels.
+"""ctypes binding of the C ABI (include/mpc_mi355x.h) - the only way Python reaches the HIP kernels: the entry points that
+take an engine handle through `MPCEngine`'s methods, the handle-less ones (environment step, policy step, rollout glue,
+evaluation accounting, perception) through `call` / `caller`, by parameter name, in the order of `SIGNATURES`.
 
 There is no CPU fallback: if the shared library is missing, or no MI355X is visible, construction fails
 loudly (`EngineError`).  Host numpy arrays are copied by the library; torch device tensors are passed
@@ -56,6 +58,48 @@ class PerceptionParams(ctypes.Structure):
                 ("env_offset", ctypes.c_int32), ("range", ctypes.c_double), ("p_drop", ctypes.c_double),
                 ("sigma_pos", ctypes.c_double), ("sigma_vel", ctypes.c_double), ("sigma_head", ctypes.c_double),
                 ("seed", ctypes.c_uint64)]
+
+
+# The handle-less entry points: every parameter of the prototype in include/mpc_mi355x.h, in its order, as name:kind - i32
+# (int32_t), u64 (uint64_t), f64 (double), ptr (any pointer, the stream included), perception (const mpc_perception *).
+# load_library builds their argtypes from this table and `caller` orders its named arguments by it; tests/test_abi.py holds
+# it against the header.
+_POLICY_IN = "obs:ptr w1:ptr b1:ptr w2:ptr b2:ptr wh:ptr bh:ptr"
+_POLICY_OUT = "actions:ptr values:ptr log_probs:ptr"
+_SYNTH_IN = ("device:i32 B:i32 K:i32 dt:f64 spawn_probability:f64 seed:u64 env_offset:i32 ref_xy:ptr M:i32 action:ptr ego:ptr "
+             "opos:ptr ospeed:ptr ohead:ptr oactive:ptr")
+_SYNTH_OUT = ("t:ptr rng_counter:ptr obs:ptr terminal_obs:ptr reward:ptr done:ptr truncated:ptr crashed:ptr arrived:ptr "
+              "reset_all:i32 stream:ptr")
+_CONTROL = (f"device:i32 B:i32 H2:i32 {_POLICY_IN} std_:ptr c0:ptr noise:ptr noise_seed:u64 env_offset:i32 noise_step:ptr "
+            f"{_POLICY_OUT} control:ptr stream:ptr")
+_RECORDS = "state_i32:ptr state_f64:ptr rec_i32:ptr rec_f64:ptr"
+_KINDS = dict(i32=ctypes.c_int32, u64=ctypes.c_uint64, f64=ctypes.c_double, ptr=ctypes.c_void_p,
+              perception=ctypes.POINTER(PerceptionParams))
+SIGNATURES = {name: tuple(tuple(word.split(":")) for word in text.split()) for name, text in dict(
+    mpc_synth_env_step=f"{_SYNTH_IN} {_SYNTH_OUT}",
+    mpc_synth_env_step_idm=f"{_SYNTH_IN} oroute:ptr oprog:ptr otarget:ptr {_SYNTH_OUT}",
+    mpc_policy_act=f"device:i32 B:i32 A:i32 H2:i32 {_POLICY_IN} std_:ptr c0:ptr noise:ptr noise_seed:u64 env_offset:i32 "
+                   f"noise_step:ptr version_v1:i32 clip:i32 {_POLICY_OUT} mpc_weights:ptr mpc_ref_speed:ptr stream:ptr",
+    mpc_policy_act_sde=f"device:i32 B:i32 A:i32 H2:i32 {_POLICY_IN} sde_std:ptr sde_noise:ptr noise_seed:u64 env_offset:i32 "
+                       f"sde_epoch:ptr sde_step:ptr sde_sample_freq:i32 version_v1:i32 clip:i32 {_POLICY_OUT} "
+                       "mpc_weights:ptr mpc_ref_speed:ptr stream:ptr",
+    mpc_policy_control=_CONTROL,
+    mpc_policy_control_tile=f"tile:i32 {_CONTROL}",
+    mpc_rollout_record="device:i32 T:i32 B:i32 A:i32 cols:i32 keep_terminal:i32 row:ptr mpc_actions_buf:ptr pos_dev:ptr "
+                       "ticket:ptr last_obs:ptr last_starts:ptr actions:ptr values:ptr log_probs:ptr mpc_act:ptr "
+                       "mpc_status:ptr new_obs:ptr reward:ptr done:ptr terminal_obs:ptr truncated:ptr crashed:ptr "
+                       "arrived:ptr counts:ptr dones_out:ptr step_counter:ptr stream:ptr",
+    mpc_rollout_finish="device:i32 T:i32 B:i32 A:i32 cols:i32 keep_terminal:i32 row:ptr last_values:ptr dones:ptr "
+                       "terminal_values:ptr gamma:f64 gae_lambda:f64 advantages:ptr returns:ptr stream:ptr",
+    mpc_episode_stats="device:i32 B:i32 Q:i32 reset:i32 done:ptr truncated:ptr crashed:ptr arrived:ptr reward:ptr ego:ptr "
+                      f"status:ptr iters:ptr {_RECORDS} recorded:ptr step_counter:ptr stream:ptr",
+    mpc_drive_metrics="device:i32 B:i32 R:i32 Q:i32 M:i32 reset:i32 dt:f64 terminal_obs:ptr obs:ptr action:ptr done:ptr "
+                      f"ref_xy:ptr {_RECORDS} stream:ptr",
+    mpc_interaction_metrics="device:i32 B:i32 K:i32 Q:i32 M:i32 reset:i32 dt:f64 ego:ptr opos:ptr ospeed:ptr ohead:ptr "
+                            f"oactive:ptr oroute:ptr oprog:ptr otarget:ptr done:ptr ref_xy:ptr conflict:ptr {_RECORDS} "
+                            "stream:ptr",
+    mpc_perceive="device:i32 B:i32 R:i32 S:i32 reset:i32 params:perception obs_true:ptr occluders:ptr obs_seen:ptr "
+                 "row_class:ptr counts:ptr ctr:ptr stream:ptr").items()}
 
 
 _EXPORTS = ["mpc_version", "mpc_last_error", "mpc_default_config", "mpc_default_config_sized", "mpc_create", "mpc_destroy",
@@ -135,40 +179,15 @@ def load_library(path: str | None = None):
     lib.mpc_set_env_state.restype = ctypes.c_int
     lib.mpc_reserve_envs.argtypes = [vp, ctypes.c_int32]
     lib.mpc_reserve_envs.restype = ctypes.c_int
-    lib.mpc_synth_env_step.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
-                                       ctypes.c_uint64, ctypes.c_int32, dp, ctypes.c_int32] + [vp] * 15 + [ctypes.c_int32, vp]
-    lib.mpc_synth_env_step.restype = ctypes.c_int
-    lib.mpc_synth_env_step_idm.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_double,
-                                           ctypes.c_uint64, ctypes.c_int32, dp, ctypes.c_int32] + [vp] * 18 + [ctypes.c_int32, vp]
-    lib.mpc_synth_env_step_idm.restype = ctypes.c_int
     lib.mpc_get_last_inputs.argtypes = [vp, ctypes.c_int32, dp, ip, dp, vp, dp, ip]
     lib.mpc_get_last_inputs.restype = ctypes.c_int
     lib.mpc_set_diagnostics.argtypes = [vp, ctypes.c_int32]
     lib.mpc_set_diagnostics.restype = ctypes.c_int
     lib.mpc_get_last_paths.argtypes = [vp, ctypes.c_int32, dp, ip, vp]
     lib.mpc_get_last_paths.restype = ctypes.c_int
-    lib.mpc_policy_act.argtypes = [ctypes.c_int32] * 4 + [vp] * 10 + [ctypes.c_uint64, ctypes.c_int32, vp] + [ctypes.c_int32] * 2 + [vp] * 6
-    lib.mpc_policy_act.restype = ctypes.c_int
-    lib.mpc_policy_act_sde.argtypes = [ctypes.c_int32] * 4 + [vp] * 9 + [ctypes.c_uint64, ctypes.c_int32, vp, vp] + \
-        [ctypes.c_int32] * 3 + [vp] * 6
-    lib.mpc_policy_act_sde.restype = ctypes.c_int
-    # device, B, H2, obs + 8 weight pointers + noise, noise_seed, env_offset, noise_step, actions, values, log_probs, control, stream
-    lib.mpc_policy_control.argtypes = [ctypes.c_int32] * 3 + [vp] * 10 + [ctypes.c_uint64, ctypes.c_int32, vp] + [vp] * 5
-    lib.mpc_policy_control.restype = ctypes.c_int
-    lib.mpc_policy_control_tile.argtypes = [ctypes.c_int32] + lib.mpc_policy_control.argtypes
-    lib.mpc_policy_control_tile.restype = ctypes.c_int
-    lib.mpc_rollout_record.argtypes = [ctypes.c_int32] * 6 + [vp] * 22
-    lib.mpc_rollout_record.restype = ctypes.c_int
-    lib.mpc_rollout_finish.argtypes = [ctypes.c_int32] * 6 + [vp] * 4 + [ctypes.c_double] * 2 + [vp] * 3
-    lib.mpc_rollout_finish.restype = ctypes.c_int
-    lib.mpc_episode_stats.argtypes = [ctypes.c_int32] * 4 + [vp] * 14 + [vp]
-    lib.mpc_episode_stats.restype = ctypes.c_int
-    lib.mpc_drive_metrics.argtypes = [ctypes.c_int32] * 6 + [ctypes.c_double] + [vp] * 9 + [vp]
-    lib.mpc_drive_metrics.restype = ctypes.c_int
-    lib.mpc_interaction_metrics.argtypes = [ctypes.c_int32] * 6 + [ctypes.c_double] + [vp] * 15 + [vp]
-    lib.mpc_interaction_metrics.restype = ctypes.c_int
-    lib.mpc_perceive.argtypes = [ctypes.c_int32] * 5 + [ctypes.POINTER(PerceptionParams)] + [vp] * 6 + [vp]
-    lib.mpc_perceive.restype = ctypes.c_int
+    for name, sig in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = [_KINDS[kind] for _, kind in sig], ctypes.c_int
     lib.mpc_eval_nlp.argtypes = [vp, ctypes.c_int32] + [vp] * 5 + [ctypes.c_int32, ctypes.c_uint32] + [vp] * 4
     lib.mpc_eval_nlp.restype = ctypes.c_int
     lib.mpc_streams_overlap.argtypes = [ctypes.c_int32, vp, vp, vp]
@@ -177,17 +196,59 @@ def load_library(path: str | None = None):
     return lib
 
 
+def _stream_handle(stream):
+    return None if stream is None else ctypes.c_void_p(getattr(stream, "cuda_stream", stream))
+
+
+def _caller(name, sig):
+    """`def name(*, lib=None, <the parameters of sig>)` written out and compiled: the entry point called positionally in
+    sig's order, each argument converted by its kind.  A function per entry point instead of a loop over the table because
+    an eager step makes three such calls: Python binds the keywords to the names itself, and raises the TypeError that
+    names the entry point and the missing or unexpected parameter."""
+    convert = dict(i32="{0}", u64="{0}", f64="{0}", ptr="None if {0} is None else c_void_p({0}.data_ptr())",
+                   perception="None if {0} is None else byref({0})")
+    args = ", ".join("_stream_handle(stream)" if n == "stream" else convert[kind].format(n) for n, kind in sig)
+    scope = dict(c_void_p=ctypes.c_void_p, byref=ctypes.byref, _stream_handle=_stream_handle, EngineError=EngineError,
+                 load_library=load_library)
+    exec(f"def {name}(*, lib=None, {', '.join(n for n, _ in sig)}):\n"
+         f"    if lib is None:\n"
+         f"        lib = load_library()\n"
+         f"    rc = lib.{name}({args})\n"
+         f"    if rc != 0:\n"
+         f"        raise EngineError(f'{name} failed ({{rc}}): {{lib.mpc_last_error().decode()}}')\n", scope)
+    return scope[name]
+
+
+_CALLERS = {name: _caller(name, sig) for name, sig in SIGNATURES.items()}
+
+
+def caller(name: str):
+    """The handle-less entry point `name` as a function of keywords alone: every one of SIGNATURES[name] and no other (TypeError
+    naming the entry point and the parameter otherwise, before anything is called).  Python ints and floats pass through;
+    a pointer is a torch tensor (its address; a bool tensor's bytes are the uint8 the kernels read) or None; `stream` is a
+    torch stream, its raw handle or None; `params` of mpc_perceive a PerceptionParams.  Enqueue only; EngineError with the
+    library's text when the entry point refuses.  lib: the library, load_library() by default."""
+    return _CALLERS[name]
+
+
+def call(name: str, *, lib=None, **named) -> None:
+    """caller(name)(lib=lib, **named).  Collecting the keywords and handing them on costs about as much again as the
+    conversion itself, so what runs once per step calls caller(name) directly."""
+    _CALLERS[name](lib=lib, **named)
+
+
+def current_stream(device):
+    """torch's current stream on a GPU `device`, which the enqueue-only calls run on; None for the CPU (no stream to name)."""
+    import torch
+    return torch.cuda.current_stream(device) if device.type == "cuda" else None
+
+
 def perceive(device: int, B: int, R: int, S: int, reset: bool, params: dict, obs_true, occluders, obs_seen, row_class,
              counts, ctr, stream) -> None:
-    """mpc_perceive on device pointers (ints or None): `params` holds the fields of mpc_perception but struct_size.
-    Enqueue only; EngineError with the library's text when it refuses the arguments."""
-    lib = load_library()
-    p = PerceptionParams(struct_size=ctypes.sizeof(PerceptionParams), **params)
-    vp = lambda a: None if a is None else ctypes.c_void_p(a)
-    rc = lib.mpc_perceive(device, B, R, S, 1 if reset else 0, ctypes.byref(p), vp(obs_true), vp(occluders), vp(obs_seen),
-                          vp(row_class), vp(counts), vp(ctr), vp(stream))
-    if rc != 0:
-        raise EngineError(f"mpc_perceive failed ({rc}): {lib.mpc_last_error().decode()}")
+    """mpc_perceive on device tensors (None where optional): `params` holds the fields of mpc_perception but struct_size.  Enqueue only; EngineError with the library's text when it refuses the arguments."""
+    caller("mpc_perceive")(device=device, B=B, R=R, S=S, reset=1 if reset else 0,
+         params=PerceptionParams(struct_size=ctypes.sizeof(PerceptionParams), **params), obs_true=obs_true,
+         occluders=occluders, obs_seen=obs_seen, row_class=row_class, counts=counts, ctr=ctr, stream=stream)
 
 
 def streams_overlap(a, b, device: int = 0) -> bool:

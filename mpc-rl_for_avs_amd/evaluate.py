@@ -31,7 +31,6 @@ inside the same captured step (mpc_interaction_metrics), or by the same update i
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import time
 from dataclasses import dataclass
@@ -39,6 +38,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from . import engine as _engine
 from .rollout import EPISODE_STEPS, VEHICLES_COUNT
 
 REC_I32 = ("steps", "success", "collision", "truncated", "unsolved", "max_iters")   # rec_i32 [6][B][Q]
@@ -95,9 +95,6 @@ class EpisodeStats:
         self.rec_i32 = z(6, B, Q, dt=torch.int32)
         self.rec_f64 = z(2, B, Q, dt=torch.float64)
         self.recorded = z(1, dt=torch.int64)
-        if backend == "hip":
-            from . import engine as _engine
-            self._lib = _engine.load_library()
 
     def update(self, ego, done=None, truncated=None, crashed=None, arrived=None, reward=None, status=None, iters=None,
                reset=False, step_counter=None):
@@ -106,13 +103,11 @@ class EpisodeStats:
             if step_counter is not None and not reset:
                 step_counter += 1
             return
-        p = lambda t: None if t is None else ctypes.c_void_p(_u8(t).data_ptr())
-        rc = self._lib.mpc_episode_stats(
-            self.device.index, self.B, self.Q, 1 if reset else 0, p(done), p(truncated), p(crashed), p(arrived), p(reward),
-            p(ego), p(status), p(iters), p(self.state_i32), p(self.state_f64), p(self.rec_i32), p(self.rec_f64),
-            p(self.recorded), p(step_counter), ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"mpc_episode_stats failed ({rc}): {self._lib.mpc_last_error().decode()}")
+        _engine.caller("mpc_episode_stats")(
+            device=self.device.index, B=self.B, Q=self.Q, reset=1 if reset else 0, done=done, truncated=truncated,
+            crashed=crashed, arrived=arrived, reward=reward, ego=ego, status=status, iters=iters, state_i32=self.state_i32,
+            state_f64=self.state_f64, rec_i32=self.rec_i32, rec_f64=self.rec_f64, recorded=self.recorded,
+            step_counter=step_counter, stream=_engine.current_stream(self.device))
 
     @torch.no_grad()
     def _torch_update(self, ego, done, truncated, crashed, arrived, reward, status, iters, reset):
@@ -248,10 +243,7 @@ class DriveMetrics:
         self.state_f64 = z(17, B, dt=torch.float64)     # ten running values, then the carries vx vy cos sin ax ay steer
         self.rec_i32 = z(4, B, Q, dt=torch.int32)
         self.rec_f64 = z(10, B, Q, dt=torch.float64)
-        if backend == "hip":
-            from . import engine as _engine
-            self._lib = _engine.load_library()
-        else:                                            # the route's segments: start and end - start
+        if backend != "hip":                             # the route's segments: start and end - start
             nseg = max(self.M - 1, 1)
             end = self.ref_xy[torch.clamp(torch.arange(nseg, device=self.device) + 1, max=self.M - 1)]
             self._e0, self._d = self.ref_xy[:nseg], end - self.ref_xy[:nseg]
@@ -271,13 +263,11 @@ class DriveMetrics:
         if self.backend == "torch":
             self._torch_update(terminal_obs, obs, action, done, reset)
             return
-        p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        rc = self._lib.mpc_drive_metrics(
-            self.device.index, B, R, self.Q, self.M, 1 if reset else 0, self.dt, None if reset else p(terminal_obs), p(obs),
-            None if reset else p(action), None if reset else p(done), p(self.ref_xy), p(self.state_i32), p(self.state_f64),
-            p(self.rec_i32), p(self.rec_f64), ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"mpc_drive_metrics failed ({rc}): {self._lib.mpc_last_error().decode()}")
+        _engine.caller("mpc_drive_metrics")(
+            device=self.device.index, B=B, R=R, Q=self.Q, M=self.M, reset=1 if reset else 0, dt=self.dt,
+            terminal_obs=None if reset else terminal_obs, obs=obs, action=None if reset else action,
+            done=None if reset else done, ref_xy=self.ref_xy, state_i32=self.state_i32, state_f64=self.state_f64,
+            rec_i32=self.rec_i32, rec_f64=self.rec_f64, stream=_engine.current_stream(self.device))
 
     def _gaps(self, t):
         """Minima over the present rows of the scene t [B, R, 8] (f64): centre gap, box gap, time to collision [B]."""
@@ -516,9 +506,6 @@ class InteractionMetrics:
         self.state_f64 = z(INTERACT_STATE_F64, B, dt=torch.float64)
         self.rec_i32 = z(len(INTERACT_I32), B, Q, dt=torch.int32)
         self.rec_f64 = z(len(INTERACT_F64), B, Q, dt=torch.float64)
-        if backend == "hip":
-            from . import engine as _engine
-            self._lib = _engine.load_library()
 
     def update(self, env, done, reset=False):
         B, K = self.B, self.K
@@ -540,14 +527,10 @@ class InteractionMetrics:
         if self.backend == "torch":
             self._numpy_update({k: v.cpu().numpy() for k, v in arrays.items()}, None if reset else done.cpu().numpy(), reset)
             return
-        p = lambda t: ctypes.c_void_p(t.data_ptr())
-        rc = self._lib.mpc_interaction_metrics(
-            self.device.index, B, K, self.Q, self.M, 1 if reset else 0, self.dt,
-            *[p(arrays[k]) for k in ("ego", "opos", "ospeed", "ohead", "oactive", "oroute", "oprog", "otarget")],
-            None if reset else p(done), p(self.ref_xy), p(self.conflict), p(self.state_i32), p(self.state_f64),
-            p(self.rec_i32), p(self.rec_f64), ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"mpc_interaction_metrics failed ({rc}): {self._lib.mpc_last_error().decode()}")
+        _engine.caller("mpc_interaction_metrics")(
+            device=self.device.index, B=B, K=K, Q=self.Q, M=self.M, reset=1 if reset else 0, dt=self.dt, **arrays,
+            done=None if reset else done, ref_xy=self.ref_xy, conflict=self.conflict, state_i32=self.state_i32,
+            state_f64=self.state_f64, rec_i32=self.rec_i32, rec_f64=self.rec_f64, stream=_engine.current_stream(self.device))
 
     def _sigma(self, x, y):
         """The ego's arc length along ref_xy [B] (csrc/mpc_interaction.hpp: sigma)."""
@@ -662,8 +645,9 @@ class InteractionMetrics:
         sf[2] = np.where(min_pet < run_f[2], min_pet, run_f[2])
         sf[3] = sigma
         for dst, src in ((self.state_i32, si), (self.state_f64, sf), (self.rec_i32, rec_i), (self.rec_f64, rec_f)):
-            if dst.device.type != "cpu" or dst.data_ptr() != src.ctypes.data:
-                dst.copy_(torch.from_numpy(src))
+            src = torch.from_numpy(src)
+            if dst.data_ptr() != src.data_ptr():         # on the CPU the arrays above are the tensors' own memory
+                dst.copy_(src)
 
     def records(self) -> dict:
         return interaction_records_from_planes(self.rec_i32.cpu().numpy(), self.rec_f64.cpu().numpy())
@@ -768,13 +752,12 @@ class Perception:
             seen = self._numpy_apply(obs_true.cpu().numpy(), bool(reset))
             out.copy_(torch.from_numpy(seen))
             return out
-        from . import engine as _engine
         params = dict(occlusion=int(self.occlusion), min_points=self.min_points, env_offset=self.env_offset, range=self.range,
                       p_drop=self.p_drop, sigma_pos=self.sigma_pos, sigma_vel=self.sigma_vel, sigma_head=self.sigma_head,
                       seed=self.seed)
-        _engine.perceive(self.device.index, self.B, self.R, self.S, bool(reset), params, obs_true.data_ptr(),
-                         self.occluders.data_ptr() if self.S else None, out.data_ptr(), self.row_class.data_ptr(),
-                         self.counts.data_ptr(), self.ctr.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+        _engine.perceive(self.device.index, self.B, self.R, self.S, bool(reset), params, obs_true,
+                         self.occluders if self.S else None, out, self.row_class, self.counts, self.ctr,
+                         _engine.current_stream(self.device))
         return out
 
     def _hidden(self, t, present):
@@ -956,11 +939,6 @@ def _engine_of(agent):
     return e if e is not None else getattr(agent, "engine", None)
 
 
-def _env_state_names(env):
-    return [n for n in ("ego", "opos", "ospeed", "ohead", "oactive", "oroute", "oprog", "otarget", "t", "rng_counter")
-            if hasattr(env, n)]
-
-
 @torch.no_grad()
 def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = False, reset_mpc_on_done: bool = False,
                    use_graph: bool | None = None, poll_every: int = 16, seed: int = 0, on_step=None,
@@ -1058,8 +1036,7 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
         # evaluation from there, so a graph run and an eager run see the same episodes
         if eng is not None:
             eng.reserve_envs(B)
-        names = _env_state_names(env)
-        snap = {n: getattr(env, n).clone() for n in names}
+        snap = {n: t.clone() for n, t in env.state_tensors().items()}
         gen_state = env.gen.get_state()
         first_obs(False)
         side = torch.cuda.Stream(dev)
@@ -1075,8 +1052,8 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
         with torch.cuda.graph(graph, stream=side):
             step()
         torch.cuda.synchronize(dev)
-        for n in names:
-            getattr(env, n).copy_(snap[n])
+        for n, t in env.state_tensors().items():
+            t.copy_(snap[n])
         env.gen.set_state(gen_state)
 
     true0 = first_obs(True)                  # `obs` itself without a perception model

@@ -35,6 +35,7 @@ import math
 import numpy as np
 import torch
 
+from . import engine as _engine
 from .reference_path import reference_states
 
 VEHICLES_COUNT = 10        # config/cfg.yaml:2
@@ -100,8 +101,7 @@ class SyntheticIntersectionEnv:
             self._lane_dx = torch.tensor([1.0, 0.0, -1.0, 0.0], dtype=torch.float64, device=self.device)
             self._lane_dy = torch.tensor([0.0, 1.0, 0.0, -1.0], dtype=torch.float64, device=self.device)
         if self.backend == "hip":
-            from . import engine as _engine
-            self._lib = _engine.load_library()
+            _engine.load_library()          # a missing library fails here, not at the first step
             self.rng_counter = torch.zeros(B, dtype=torch.int64, device=self.device)
             u8 = lambda: torch.zeros(B, dtype=torch.uint8, device=self.device)
             # outputs of the step live at fixed addresses (a captured hipGraph replays against them)
@@ -112,27 +112,19 @@ class SyntheticIntersectionEnv:
 
     # ---- fused implementation (csrc/mpc_synth_env.hpp) ---------------------------------------------------------------
     def _hip_call(self, action, reset_all):
-        import ctypes
-        o = self._out
-        p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        if self.traffic == "idm":
-            rc = self._lib.mpc_synth_env_step_idm(
-                self.device.index, self.num_envs, self.K, self.dt, self.spawn_probability, self.seed, self.env_offset,
-                p(self.ref_xy), self.M, p(action), p(self.ego), p(self.opos), p(self.ospeed), p(self.ohead), p(self.oactive),
-                p(self.oroute), p(self.oprog), p(self.otarget), p(self.t), p(self.rng_counter), p(o["obs"]),
-                p(o["terminal_obs"]), p(o["reward"]), p(o["done"]), p(o["truncated"]), p(o["crashed"]), p(o["arrived"]),
-                1 if reset_all else 0, stream)
-            if rc != 0:
-                raise RuntimeError(f"mpc_synth_env_step_idm failed ({rc}): {self._lib.mpc_last_error().decode()}")
-            return
-        rc = self._lib.mpc_synth_env_step(
-            self.device.index, self.num_envs, self.K, self.dt, self.spawn_probability, self.seed, self.env_offset,
-            p(self.ref_xy), self.M, p(action), p(self.ego), p(self.opos), p(self.ospeed), p(self.ohead), p(self.oactive),
-            p(self.t), p(self.rng_counter), p(o["obs"]), p(o["terminal_obs"]), p(o["reward"]), p(o["done"]),
-            p(o["truncated"]), p(o["crashed"]), p(o["arrived"]), 1 if reset_all else 0, stream)
-        if rc != 0:
-            raise RuntimeError(f"mpc_synth_env_step failed ({rc}): {self._lib.mpc_last_error().decode()}")
+        idm = {n: getattr(self, n) for n in ("oroute", "oprog", "otarget")} if self.traffic == "idm" else {}
+        _engine.caller("mpc_synth_env_step_idm" if idm else "mpc_synth_env_step")(
+            device=self.device.index, B=self.num_envs, K=self.K, dt=self.dt, spawn_probability=self.spawn_probability,
+            seed=self.seed, env_offset=self.env_offset, ref_xy=self.ref_xy, M=self.M, action=action, ego=self.ego,
+            opos=self.opos, ospeed=self.ospeed, ohead=self.ohead, oactive=self.oactive, **idm, t=self.t,
+            rng_counter=self.rng_counter, **self._out, reset_all=1 if reset_all else 0,
+            stream=_engine.current_stream(self.device))
+
+    def state_tensors(self) -> dict:
+        """name -> tensor of everything a step changes besides its outputs and the torch generator `gen`: what a caller
+        that steps for a graph capture snapshots and puts back (in place: the graph replays against these addresses)."""
+        names = ("ego", "opos", "ospeed", "ohead", "oactive", "oroute", "oprog", "otarget", "t", "rng_counter")
+        return {n: getattr(self, n) for n in names if hasattr(self, n)}
 
     # ---- random helpers ------------------------------------------------------------------------------------
     def _u(self, shape, lo, hi):
@@ -628,6 +620,77 @@ def _check_direct_policy(policy):
                          "(the reference's agents/ppo_agent.py leaves SB3's default, off)")
 
 
+def mpc_inputs(actions, version, default_weights, clip=False):
+    """RL action -> (weights[B,3] float64, ref_speed[B] float64 or None) as the reference maps them: "v0" action 0 is the
+    reference speed beside default_weights [B, 3], "v1" actions 0..2 are the weights.  clip: to the Box(-1, 1) bounds first
+    (PPO's collector, agents/ppo_mpc.py:399-407)."""
+    if clip:
+        actions = torch.clamp(actions, -1.0, 1.0)
+    if version == "v0":
+        return default_weights, actions[:, 0].to(torch.float64).contiguous()
+    return actions[:, :3].to(torch.float64).contiguous(), None
+
+
+def fits_fused_policy(policy, engine):
+    """Whether the fused policy kernels (FusedPolicy) can run `policy`: SB3's MlpPolicy shape with 80 inputs, both towers side
+    by side in 256 columns, at most 8 actions, float32, and an engine that carries the library.  Where the tensors live is
+    the caller's part: the collector asks for the HIP environment, the agents for an observation on a GPU."""
+    return (isinstance(policy, ActorCritic) and hasattr(engine, "_lib") and policy.pi[0].in_features == VEHICLES_COUNT * 8 and
+            2 * policy.pi[0].out_features <= 256 and policy.action_dim <= 8 and policy.log_std.dtype == torch.float32)
+
+
+class FusedPolicy:
+    """The policy step as ONE launch (csrc/mpc_rollout_glue.hpp): forward of both towers, sample, log-probability and what
+    the step's next stage reads - mode "v0" / "v1": the MPC's inputs (mpc_policy_act, or mpc_policy_act_sde for a gSDE
+    policy), mode "direct": the controls (mpc_policy_control).  `tensors` are the launch's fixed-address buffers:
+      act, val, logp   the action [B, A], the value and the log-probability [B]
+      w, rs            "v1" the MPC's weights [B, 3] f64, "v0" its reference speed [B] f64
+      ctrl             "direct": the controls [B, 2] f64
+      noise            Gaussian: the sample's draws [B, A], written by the kernel when it draws and read by it when not;
+                       gSDE: None (the kernel draws the matrices and keeps none), deterministic the zero matrices [B, H, A]
+      step             int64 [1], the policy steps taken so far, which key the Gaussian draws with (seed, env_offset + b); the
+                       caller's accounting advances it (mpc_rollout_record, mpc_episode_stats).  None when deterministic.
+      sde_epoch        gSDE, int64 [1]: the epoch that keys the matrices with (seed, env_offset + b); with sde_sample_freq > 0
+                       the kernel adds sde_step // sde_sample_freq, `sde_step` an int64 [1] device counter of the caller's.
+                       None when deterministic.
+    clip: the MPC's inputs from the action clipped to [-1, 1] (PPO's collector)."""
+
+    def __init__(self, policy, B, device, lib, mode, clip=False, seed=0, env_offset=0, deterministic=False,
+                 sde_sample_freq=-1, sde_step=None):
+        A, H, sde = policy.action_dim, policy.pi[0].out_features, bool(policy.use_sde)
+        z = lambda *sh, dt=torch.float32: torch.zeros(sh, dtype=dt, device=device)
+        self.policy, self.device, self.mode = policy, device, mode
+        t = self.tensors = dict(act=z(B, A), val=z(B), logp=z(B), w=z(B, 3, dt=torch.float64), rs=z(B, dt=torch.float64),
+                                noise=(z(B, H, A) if deterministic else None) if sde else z(B, A),
+                                ctrl=z(B, 2, dt=torch.float64) if mode == "direct" else None,
+                                step=None if deterministic else z(1, dt=torch.int64),
+                                sde_epoch=z(1, dt=torch.int64) if sde and not deterministic else None)
+        # what every launch passes unchanged (the buffers above are never rebound); launch adds the observation, the
+        # policy's weights as they are then, and the stream
+        self._fixed = dict(lib=lib, device=device.index, B=int(B), noise_seed=int(seed) & 0xFFFFFFFFFFFFFFFF,
+                           env_offset=int(env_offset), actions=t["act"], values=t["val"], log_probs=t["logp"])
+        if sde:
+            self._fixed.update(sde_noise=t["noise"], sde_epoch=t["sde_epoch"], sde_step=sde_step,
+                               sde_sample_freq=int(sde_sample_freq))
+        else:
+            self._fixed.update(noise=t["noise"], noise_step=t["step"])
+        if mode == "direct":
+            entry = "mpc_policy_control"
+            self._fixed.update(control=t["ctrl"])
+        else:
+            v1 = mode == "v1"
+            entry = "mpc_policy_act_sde" if sde else "mpc_policy_act"
+            self._fixed.update(A=A, version_v1=1 if v1 else 0, clip=1 if clip else 0, mpc_weights=t["w"] if v1 else None,
+                               mpc_ref_speed=None if v1 else t["rs"])
+        self._entry = _engine.caller(entry)
+
+    def launch(self, obs):
+        f = self.policy._fz
+        std = dict(sde_std=f["std"]) if self.policy.use_sde else dict(std_=f["std"], c0=f["c0"])
+        self._entry(obs=obs, H2=f["b1"].numel(), w1=f["w1"], b1=f["b1"], w2=f["w2"], b2=f["b2"], wh=f["wh"],
+                    bh=f["bh"], **std, stream=_engine.current_stream(self.device), **self._fixed)
+
+
 class RolloutBuffer:
     """[n_steps, B, ...] device tensors + GAE (the arithmetic of SB3's RolloutBuffer, which the reference uses as is).
 
@@ -785,27 +848,21 @@ class BatchedCollector:
         # fused_glue (None = whenever possible: fused HIP environment, SB3-shaped policy, real engine): policy forward + sample
         # + MPC inputs in ONE launch (mpc_policy_act) and buffer row + carry-over + counters in one (mpc_rollout_record)
         # instead of ~40 torch kernels - csrc/mpc_rollout_glue.hpp
-        can_fuse = (dev.type == "cuda" and getattr(env, "backend", "") == "hip" and isinstance(policy, ActorCritic) and
-                    (self.direct or hasattr(engine, "predict_batch_torch")) and hasattr(engine, "_lib") and
-                    policy.pi[0].in_features == VEHICLES_COUNT * 8 and 2 * policy.pi[0].out_features <= 256 and
-                    policy.action_dim <= 8 and policy.log_std.dtype == torch.float32)
+        can_fuse = (getattr(env, "backend", "") == "hip" and fits_fused_policy(policy, engine) and
+                    (self.direct or hasattr(engine, "predict_batch_torch")))
         if fused_glue and not can_fuse:
             raise ValueError("fused_glue needs the fused HIP environment, an ActorCritic policy (80 inputs, hidden <= 128) and the real engine")
         self.fused_glue = can_fuse if fused_glue is None else bool(fused_glue)
         if self.fused_glue:
-            A = policy.action_dim
-            z = lambda *sh, dt=torch.float32: torch.zeros(sh, dtype=dt, device=dev)
-            # noise: the Gaussian sample's draws of the last step, made by the kernel itself (counter-based, keyed by seed,
-            # global environment id and `step`, the number of policy steps taken so far, which mpc_rollout_record advances)
-            self._fg = dict(act=z(B, A), val=z(B), logp=z(B), w=z(B, 3, dt=torch.float64), rs=z(B, dt=torch.float64),
-                            ticket=z(1, dt=torch.int32), noise=z(B, A), step=z(1, dt=torch.int64))
-            self._noise_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-            if self.direct:
-                self._fg.update(ctrl=z(B, 2, dt=torch.float64))
+            # (the Gaussian sample's draws of the last step stay in _fg["noise"]; mpc_rollout_record advances _fg["step"])
+            self._policy_step = FusedPolicy(policy, B, dev, engine._lib, version, clip=algorithm == "ppo", seed=seed,
+                                            env_offset=getattr(env, "env_offset", 0), sde_sample_freq=self.sde_sample_freq,
+                                            sde_step=self.buffer.pos_dev)
+            self._fg = self._policy_step.tensors
+            self._ticket = torch.zeros(1, dtype=torch.int32, device=dev)
             if self.use_sde:
-                # gSDE: the exploration epoch the kernel keys its matrices by; a rollout draws from epochs sde_epoch ..
-                # sde_epoch + span - 1 (one per sde_sample_freq steps), and _begin_rollout moves past them
-                self._fg["sde_epoch"] = z(1, dt=torch.int64)
+                # gSDE: a rollout draws from epochs sde_epoch .. sde_epoch + span - 1 (one per sde_sample_freq steps), and
+                # _begin_rollout moves past them
                 f = self.sde_sample_freq
                 self._sde_span = 1 if f <= 0 else -(-int(n_steps) // f)
         if self.direct:
@@ -849,13 +906,6 @@ class BatchedCollector:
                         raise RuntimeError("hipGraph capture of the sharded rollout step failed (" + self.graph_fallback_reason +
                                            "); set MPC_ALLOW_EAGER_COLLECTIVE_FALLBACK=1 to step eagerly instead") from e
 
-    def mpc_inputs(self, actions):
-        """RL action -> (weights[B,3] float64, ref_speed[B] float64 or None) as the reference maps them."""
-        clipped = torch.clamp(actions, -1.0, 1.0) if self.algorithm == "ppo" else actions
-        if self.version == "v0":
-            return self.default_weights, clipped[:, 0].to(torch.float64).contiguous()
-        return clipped[:, :3].to(torch.float64).contiguous(), None
-
     # ---- one rollout = begin, n steps, finish; split so that the step can be captured in a hipGraph and several
     #      collectors can be interleaved (PipelinedCollector)
     @torch.no_grad()
@@ -876,93 +926,48 @@ class BatchedCollector:
 
     @torch.no_grad()
     def _rollout_step_fused(self):
-        """The same step with the two glue kernels: identical data flow; the float32 sums of the three small matrix products
+        """The same step with the glue kernels: identical data flow; the float32 sums of the three small matrix products
         are accumulated in index order instead of hipBLASLt's, and the Gaussian sample's noise is drawn by the kernel
         (counter-based; left in self._fg["noise"]) instead of by torch's generator - fed the same noise, ActorCritic.act
-        returns the same actions (tests/test_predict_gpu.py::test_fused_glue_step_equals_the_torch_step)."""
-        import ctypes
-        lib, env, pol, buf, fg = self.engine._lib, self.env, self.policy, self.buffer, self._fg
-        f, A, B = pol._fz, pol.action_dim, env.num_envs
-        H2 = f["b1"].numel()
-        dev = env.device
-        p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        obs = self._last_obs
-        v1 = self.version == "v1"
-        if self.use_sde:
-            # gSDE: the matrices of epoch sde_epoch + pos // sde_sample_freq, drawn in the kernel (pos: the buffer's device row)
-            rc = lib.mpc_policy_act_sde(dev.index, B, A, H2, p(obs), p(f["w1"]), p(f["b1"]), p(f["w2"]), p(f["b2"]), p(f["wh"]),
-                                        p(f["bh"]), p(f["std"]), None, self._noise_seed, int(getattr(env, "env_offset", 0)),
-                                        p(fg["sde_epoch"]), p(buf.pos_dev), self.sde_sample_freq, 1 if v1 else 0,
-                                        1 if self.algorithm == "ppo" else 0, p(fg["act"]), p(fg["val"]), p(fg["logp"]),
-                                        p(fg["w"]) if v1 else None, None if v1 else p(fg["rs"]), stream)
+        returns the same actions (tests/test_predict_gpu.py::test_fused_glue_step_equals_the_torch_step).  version "direct":
+        the policy launch leaves the controls where the MPC's action would be, and the status is the all-zero one."""
+        obs, fg = self._last_obs, self._fg
+        self._policy_step.launch(obs)
+        if self.direct:
+            self.last_mpc = self._direct
         else:
-            rc = lib.mpc_policy_act(dev.index, B, A, H2, p(obs), p(f["w1"]), p(f["b1"]), p(f["w2"]), p(f["b2"]), p(f["wh"]),
-                                    p(f["bh"]), p(f["std"]), p(f["c0"]), p(fg["noise"]), self._noise_seed,
-                                    int(getattr(env, "env_offset", 0)), p(fg["step"]), 1 if v1 else 0,
-                                    1 if self.algorithm == "ppo" else 0, p(fg["act"]), p(fg["val"]), p(fg["logp"]),
-                                    p(fg["w"]) if v1 else None, None if v1 else p(fg["rs"]), stream)
-        if rc != 0:
-            raise RuntimeError(f"mpc_policy_act failed ({rc}): {lib.mpc_last_error().decode()}")
-        weights, ref_speed = (fg["w"], None) if v1 else (self.default_weights, fg["rs"])
-        self._mpc_out = self.engine.predict_batch_torch(obs, weights, ref_speed, collision_cost=self.collision_cost,
-                                                        warm_start=self.warm_start, out=self._mpc_out, **self._mpc_kw)
-        self.last_mpc = self._mpc_out
+            weights, ref_speed = (fg["w"], None) if self.version == "v1" else (self.default_weights, fg["rs"])
+            self._mpc_out = self.engine.predict_batch_torch(obs, weights, ref_speed, collision_cost=self.collision_cost,
+                                                            warm_start=self.warm_start, out=self._mpc_out, **self._mpc_kw)
+            self.last_mpc = self._mpc_out
         mpc_action = self.last_mpc["act"]
         if self.gather_actions:
             from . import sharding
             self.gathered_actions, self.gathered_status = sharding.all_gather_results(mpc_action, self.last_mpc["status"])
-        env.step(mpc_action)
-        o = env._out
+        self.env.step(mpc_action)
         if self.reset_mpc_on_done:
-            self.engine.reset_env_mask_torch(o["done"])
+            self.engine.reset_env_mask_torch(self.env._out["done"])
         elif self.warm_start:
-            self.engine.reset_env_mask_torch(o["done"], warm_only=True)
-        keep = buf.terminal_obs is not None
-        rc = lib.mpc_rollout_record(dev.index, buf.n_steps, B, A, buf._cols, 1 if keep else 0, p(buf._row), p(buf.mpc_actions), p(buf.pos_dev),
-                                    p(fg["ticket"]), p(self._last_obs), p(self._last_episode_starts), p(fg["act"]), p(fg["val"]),
-                                    p(fg["logp"]), p(mpc_action), p(self.last_mpc["status"]), p(o["obs"]), p(o["reward"]),
-                                    p(o["done"]), p(o["terminal_obs"]) if keep else None, p(o["truncated"]) if keep else None,
-                                    p(o["crashed"]), p(o["arrived"]), p(self._roll["counts"]), p(self._roll["dones"]),
-                                    p(fg["step"]), stream)
-        if rc != 0:
-            raise RuntimeError(f"mpc_rollout_record failed ({rc}): {lib.mpc_last_error().decode()}")
+            self.engine.reset_env_mask_torch(self.env._out["done"], warm_only=True)
+        self._record(mpc_action, self.last_mpc["status"])
 
-    @torch.no_grad()
-    def _rollout_step_direct_fused(self):
-        """version "direct" with the glue kernels: mpc_policy_control (policy, sample, controls), the environment, and
-        mpc_rollout_record with the controls in the MPC action's place and the all-zero status."""
-        import ctypes
-        lib, env, pol, buf, fg = self.engine._lib, self.env, self.policy, self.buffer, self._fg
-        f, B, dev = pol._fz, env.num_envs, env.device
-        p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        rc = lib.mpc_policy_control(dev.index, B, f["b1"].numel(), p(self._last_obs), p(f["w1"]), p(f["b1"]), p(f["w2"]),
-                                    p(f["b2"]), p(f["wh"]), p(f["bh"]), p(f["std"]), p(f["c0"]), p(fg["noise"]),
-                                    self._noise_seed, int(getattr(env, "env_offset", 0)), p(fg["step"]), p(fg["act"]),
-                                    p(fg["val"]), p(fg["logp"]), p(fg["ctrl"]), stream)
-        if rc != 0:
-            raise RuntimeError(f"mpc_policy_control failed ({rc}): {lib.mpc_last_error().decode()}")
-        self.last_mpc = self._direct
-        env.step(fg["ctrl"])
-        o = env._out
+    def _record(self, mpc_action, status):
+        """Buffer row, carry-over to the next step and the rollout's counters in one launch (mpc_rollout_record)."""
+        buf, fg, o, r = self.buffer, self._fg, self.env._out, self._roll
         keep = buf.terminal_obs is not None
-        rc = lib.mpc_rollout_record(dev.index, buf.n_steps, B, 2, buf._cols, 1 if keep else 0, p(buf._row), p(buf.mpc_actions),
-                                    p(buf.pos_dev), p(fg["ticket"]), p(self._last_obs), p(self._last_episode_starts), p(fg["act"]),
-                                    p(fg["val"]), p(fg["logp"]), p(fg["ctrl"]), p(self._direct["status"]), p(o["obs"]),
-                                    p(o["reward"]), p(o["done"]), p(o["terminal_obs"]) if keep else None,
-                                    p(o["truncated"]) if keep else None, p(o["crashed"]), p(o["arrived"]),
-                                    p(self._roll["counts"]), p(self._roll["dones"]), p(fg["step"]), stream)
-        if rc != 0:
-            raise RuntimeError(f"mpc_rollout_record failed ({rc}): {lib.mpc_last_error().decode()}")
+        _engine.caller("mpc_rollout_record")(
+            lib=self.engine._lib, device=self.env.device.index, T=buf.n_steps, B=self.env.num_envs, A=self.policy.action_dim,
+            cols=buf._cols, keep_terminal=1 if keep else 0, row=buf._row, mpc_actions_buf=buf.mpc_actions, pos_dev=buf.pos_dev,
+            ticket=self._ticket, last_obs=self._last_obs, last_starts=self._last_episode_starts, actions=fg["act"],
+            values=fg["val"], log_probs=fg["logp"], mpc_act=mpc_action, mpc_status=status, new_obs=o["obs"],
+            reward=o["reward"], done=o["done"], terminal_obs=o["terminal_obs"] if keep else None,
+            truncated=o["truncated"] if keep else None, crashed=o["crashed"], arrived=o["arrived"], counts=r["counts"],
+            dones_out=r["dones"], step_counter=fg["step"], stream=_engine.current_stream(self.env.device))
 
     @torch.no_grad()
     def _rollout_step(self, device_pos: bool = False):
         if self.fused_glue:
-            if self.direct:
-                self._rollout_step_direct_fused()
-            else:
-                self._rollout_step_fused()
+            self._rollout_step_fused()
             if not device_pos:
                 self.buffer.pos += 1
             return
@@ -976,7 +981,7 @@ class BatchedCollector:
             map_control(actions, out=self._direct["act"], scale=self._control_scale)
             self.last_mpc = self._direct
         else:
-            weights, ref_speed = self.mpc_inputs(actions)
+            weights, ref_speed = mpc_inputs(actions, self.version, self.default_weights, clip=self.algorithm == "ppo")
             self._mpc_out = self.engine.predict_batch_torch(obs, weights, ref_speed, collision_cost=self.collision_cost,
                                                             warm_start=self.warm_start, out=self._mpc_out, **self._mpc_kw)
             self.last_mpc = self._mpc_out
@@ -1022,9 +1027,7 @@ class BatchedCollector:
         # detector records - including records a caller restored with mpc_set_env_state before building the collector
         # (resume).  A graph collector and an eager one with the same seeds therefore produce the same rollouts
         # (tests/test_predict_gpu.py::test_graph_and_eager_collectors_produce_the_same_rollout).
-        names = [n for n in ("ego", "opos", "ospeed", "ohead", "oactive", "oroute", "oprog", "otarget", "t", "rng_counter")
-                 if hasattr(env, n)]
-        snap = {n: getattr(env, n).clone() for n in names}
+        snap = {n: t.clone() for n, t in env.state_tensors().items()}
         snap_obs, snap_starts = self._last_obs.clone(), self._last_episode_starts.clone()
         gen_states = [self.gen.get_state(), env.gen.get_state()]
         snap_step = self._fg["step"].clone() if self.fused_glue else None
@@ -1047,20 +1050,20 @@ class BatchedCollector:
             # the capture FAILED: put the collector back as if it had never tried, and should the restore itself fail
             # (a synchronize or a state load after an invalidated capture), chain it so that the capture's error stays visible
             try:
-                self._restore_after_capture(names, snap, snap_obs, snap_starts, gen_states, snap_step, records)
+                self._restore_after_capture(snap, snap_obs, snap_starts, gen_states, snap_step, records)
             except Exception as restore_error:      # noqa: BLE001
                 raise restore_error from capture_error
             raise
         else:
-            self._restore_after_capture(names, snap, snap_obs, snap_starts, gen_states, snap_step, records)
+            self._restore_after_capture(snap, snap_obs, snap_starts, gen_states, snap_step, records)
 
-    def _restore_after_capture(self, names, snap, snap_obs, snap_starts, gen_states, snap_step, records):
+    def _restore_after_capture(self, snap, snap_obs, snap_starts, gen_states, snap_step, records):
         """Put back what the warm-up / capture steps of _capture() touched (in place: a graph replays against these addresses)."""
         env = self.env
         torch.cuda.synchronize(env.device)
         self.buffer.reset()
-        for n in names:
-            getattr(env, n).copy_(snap[n])
+        for n, t in env.state_tensors().items():
+            t.copy_(snap[n])
         self._last_obs.copy_(snap_obs)
         self._last_episode_starts.copy_(snap_starts)
         self.gen.set_state(gen_states[0])
@@ -1091,20 +1094,16 @@ class BatchedCollector:
             self.buffer.compute_returns_and_advantage(last_values, self._roll["dones"])
             return
         # the same arithmetic in one launch (mpc_rollout_finish) instead of 11 torch kernels per step of the rollout
-        import ctypes
         buf, dev, B = self.buffer, self.env.device, self.env.num_envs
         T = buf.n_steps
         tv = None
         if buf.terminal_obs is not None:
             tv = self.policy.predict_values(buf.terminal_obs.reshape((T * B,) + buf.terminal_obs.shape[2:])).contiguous()
-        last_values = last_values.contiguous()
-        p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        rc = self.engine._lib.mpc_rollout_finish(dev.index, T, B, self.policy.action_dim, buf._cols,
-                                                 1 if buf.terminal_obs is not None else 0, p(buf._row), p(last_values),
-                                                 p(self._roll["dones"]), p(tv), buf.gamma, buf.gae_lambda, p(buf.advantages),
-                                                 p(buf.returns), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"mpc_rollout_finish failed ({rc}): {self.engine._lib.mpc_last_error().decode()}")
+        _engine.call("mpc_rollout_finish", lib=self.engine._lib, device=dev.index, T=T, B=B, A=self.policy.action_dim,
+                     cols=buf._cols, keep_terminal=1 if buf.terminal_obs is not None else 0, row=buf._row,
+                     last_values=last_values.contiguous(), dones=self._roll["dones"], terminal_values=tv, gamma=buf.gamma,
+                     gae_lambda=buf.gae_lambda, advantages=buf.advantages, returns=buf.returns,
+                     stream=_engine.current_stream(dev))
 
     def _rollout_stats(self, n):
         r = self._roll
@@ -1291,113 +1290,60 @@ class OnPolicyTrainer:
         return log
 
 
-class MPCRLAgent:
-    """The reference's `trainer.predict(obs)` (trainers/trainer.py:342-368) for a batch of observations: the policy forward,
-    then the MPC with its output - version "v0" hands action 0 to the MPC as the reference speed, "v1" actions 0..2 as the
-    cost weights.  Like the reference the policy output is stochastic and NOT clipped (SURVEY 3.3), whatever the algorithm.
+class _PolicyAgent:
+    """What MPCRLAgent and PPOAgent share: an ActorCritic policy and an engine, SB3 checkpoints, the policy's output, and the
+    closed-loop evaluation's contract (evaluate.evaluate_agent) - `act_batch_torch` with the state it keeps between calls and
+    `restart_actions`.  A subclass says whether the fused policy step can run (`_fusable`) and in which mode (`_mode`), which
+    buffers its state needs besides (`_act_buffers`), and how the action becomes what the environment gets (`_act`)."""
 
-    gSDE policies: the reference draws ONE exploration matrix when it loads a checkpoint (agents/ppo_mpc.py:627-628) and
-    predict never resamples, so every later prediction explores with that same matrix.  reset_noise() draws it per
-    environment (one matrix per row of the batch, kept until the next reset_noise()); without it the policy's single matrix
-    serves every row, as in the reference."""
-
-    def __init__(self, policy: ActorCritic, engine, version: str = "v0", algorithm: str = "ppo",
-                 default_weights=(1.0, 1.0, 1.0), collision_cost: bool = False):
-        if version not in ("v0", "v1") or algorithm not in ("ppo", "a2c"):
-            raise ValueError("version must be v0|v1 and algorithm ppo|a2c")
-        if version == "v1" and policy.action_dim < 3:
-            raise ValueError("v1 needs an action of at least 3 components (speed, control, input_diff weights)")
-        self.policy, self.engine, self.version, self.algorithm = policy, engine, version, algorithm
-        self.default_weights = tuple(float(w) for w in default_weights)
-        self.collision_cost = bool(collision_cost)
+    DETERMINISTIC = False          # policy_output's default, the one of the reference's predict
 
     @classmethod
-    def from_sb3(cls, path, engine, device="cpu", **kw):
-        """Load an SB3 checkpoint (ActorCritic.load_sb3) and wrap it; version / algorithm from the checkpoint unless given."""
+    def from_sb3(cls, path, engine=None, device="cpu", **kw):
+        """Load an SB3 checkpoint (ActorCritic.load_sb3; what ActorCritic.save_sb3 writes) and wrap it -> (agent, meta)."""
         pol, meta = ActorCritic.load_sb3(path, device=device)
-        kw.setdefault("version", meta["version"] or "v0")
-        kw.setdefault("algorithm", meta["algorithm"] or "ppo")
-        return cls(pol, engine, **kw), meta
+        return cls(pol, engine, **cls._sb3_settings(meta, kw)), meta
+
+    @staticmethod
+    def _sb3_settings(meta, kw):
+        return kw
 
     @torch.no_grad()
-    def reset_noise(self, n: int, generator=None):
-        self.policy.reset_noise(n, generator=generator)
-
-    @torch.no_grad()
-    def policy_output(self, obs, deterministic: bool = False, generator=None):
+    def policy_output(self, obs, deterministic: bool | None = None, generator=None):
         self.policy.eval()
         obs = torch.as_tensor(obs, dtype=torch.float32, device=self.policy.log_std.device)
+        deterministic = self.DETERMINISTIC if deterministic is None else deterministic
         actions, _, _ = self.policy(obs, deterministic=deterministic, generator=generator)
         return actions
 
-    def mpc_inputs(self, actions):
-        B, dev = actions.shape[0], actions.device
-        if self.version == "v0":
-            w = torch.tensor(self.default_weights, dtype=torch.float64, device=dev).repeat(B, 1).contiguous()
-            return w, actions[:, 0].to(torch.float64).contiguous()
-        return actions[:, :3].to(torch.float64).contiguous(), None
-
-    @torch.no_grad()
-    def predict_batch(self, obs_batch, deterministic: bool = False, generator=None):
-        """obs_batch [B, 10, 8] -> dict(act [B, 2], status, iters, rl_action [B, A]).  A torch tensor on a GPU goes through
-        engine.predict_batch_torch (zero-copy, synchronised before returning); anything else through engine.predict_batch."""
-        actions = self.policy_output(obs_batch, deterministic, generator)
-        weights, ref_speed = self.mpc_inputs(actions)
-        if actions.is_cuda and hasattr(self.engine, "predict_batch_torch"):
-            obs = torch.as_tensor(obs_batch, dtype=torch.float32, device=actions.device).contiguous()
-            out = self.engine.predict_batch_torch(obs, weights, ref_speed, collision_cost=self.collision_cost, sync=True)
-        else:
-            out = self.engine.predict_batch(np.asarray(torch.as_tensor(obs_batch, dtype=torch.float32).cpu()),
-                                            weights.cpu().numpy(), None if ref_speed is None else ref_speed.cpu().numpy(),
-                                            collision_cost=self.collision_cost)
-        return dict(out, rl_action=actions)
-
-    # ---- closed-loop evaluation (evaluate.evaluate_agent) ---------------------------------------------------------------
     @torch.no_grad()
     def act_batch_torch(self, obs, deterministic: bool = False, seed: int = 0, env_offset: int = 0):
         """obs float32 device tensor [B, 10, 8] -> dict(act [B, 2] f64, status, iters, step, generator): the policy, then the
-        MPC through engine.predict_batch_torch, mapped like mpc_inputs and unclipped (trainer.predict).  Enqueue-only, the same
-        output tensors every call.  On a GPU with the real engine the policy is one launch (mpc_policy_act / _sde, the
-        collector's kernels), otherwise ActorCritic.act.
-          deterministic  the mean
+        subclass's `_act`.  Enqueue-only, the same output tensors every call.  With `_fusable` and the observation on a GPU
+        the policy is one launch (FusedPolicy, the collector's kernels), otherwise ActorCritic.act.
+          deterministic  the mean: the fused kernel reads all-zero noise, `step` is None and no generator is returned
           stochastic     fused: noise keyed by (seed, env_offset + b, step), `step` the int64 [1] counter the caller
                          advances once per step (mpc_episode_stats does); torch: drawn from `generator` (seeded by seed)
           gSDE           one exploration matrix per environment for the whole evaluation (what reset_noise(B) draws, never
                          resampled, agents/ppo_mpc.py:627-628): fused, keyed by (seed, env_offset + b, epoch 0); torch, drawn
                          once from a generator seeded by seed
         restart_actions() puts the counters / matrices back to their start."""
-        import ctypes
-        B, dev = int(obs.shape[0]), obs.device
-        key = (B, dev, bool(deterministic), int(seed), int(env_offset))
+        key = (int(obs.shape[0]), obs.device, bool(deterministic), int(seed), int(env_offset))
         st = getattr(self, "_act_state", None)
         if st is None or st["key"] != key:
             st = self._act_init(key)
-        pol, v1 = self.policy, self.version == "v1"
+        actions = None
         if st["fused"]:
-            f, fg, A = pol._fz, st["fg"], pol.action_dim
-            lib = self.engine._lib
-            p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            seed64 = int(seed) & 0xFFFFFFFFFFFFFFFF
-            common = (p(fg["act"]), p(fg["val"]), p(fg["logp"]), p(fg["w"]) if v1 else None, None if v1 else p(fg["rs"]), stream)
-            if pol.use_sde:
-                rc = lib.mpc_policy_act_sde(dev.index, B, A, f["b1"].numel(), p(obs), p(f["w1"]), p(f["b1"]), p(f["w2"]),
-                                            p(f["b2"]), p(f["wh"]), p(f["bh"]), p(f["std"]), p(st["noise"]), seed64,
-                                            int(env_offset), p(fg.get("sde_epoch")), None, -1, 1 if v1 else 0, 0, *common)
-            else:
-                rc = lib.mpc_policy_act(dev.index, B, A, f["b1"].numel(), p(obs), p(f["w1"]), p(f["b1"]), p(f["w2"]), p(f["b2"]),
-                                        p(f["wh"]), p(f["bh"]), p(f["std"]), p(f["c0"]), p(fg["noise"]), seed64, int(env_offset),
-                                        p(st["step"]), 1 if v1 else 0, 0, *common)
-            if rc != 0:
-                raise RuntimeError(f"mpc_policy_act failed ({rc}): {lib.mpc_last_error().decode()}")
-            weights, ref_speed = (fg["w"], None) if v1 else (st["w"], fg["rs"])
+            st["policy_step"].launch(obs)
         else:
-            actions, _, _ = pol.act(obs, generator=st["gen"], noise=st["noise"])
-            weights, ref_speed = (actions[:, :3].to(torch.float64).contiguous(), None) if v1 else \
-                (st["w"], actions[:, 0].to(torch.float64).contiguous())
-        st["out"] = self.engine.predict_batch_torch(obs, weights, ref_speed, collision_cost=self.collision_cost, out=st["out"])
-        draws = not st["fused"] and not deterministic and not pol.use_sde
-        return dict(st["out"], step=st["step"], generator=st["gen"] if draws else None)
+            actions, _, _ = self.policy.act(obs, generator=st["gen"], noise=st["noise"])
+        draws = not st["fused"] and not deterministic and not self.policy.use_sde
+        return dict(self._act(st, obs, actions), step=st["step"], generator=st["gen"] if draws else None)
+
+    def _fused_policy(self, key):
+        B, dev, deterministic, seed, env_offset = key
+        return FusedPolicy(self.policy, B, dev, self.engine._lib, self._mode, seed=seed, env_offset=env_offset,
+                           deterministic=deterministic)
 
     def _act_init(self, key):
         B, dev, deterministic, seed, _ = key
@@ -1406,28 +1352,20 @@ class MPCRLAgent:
         pol.refresh_fused()
         A, H = pol.action_dim, pol.pi[0].out_features
         z = lambda *sh, dt=torch.float32: torch.zeros(sh, dtype=dt, device=dev)
-        fused = (dev.type == "cuda" and hasattr(self.engine, "_lib") and hasattr(self.engine, "predict_batch_torch") and
-                 pol.pi[0].in_features == VEHICLES_COUNT * 8 and 2 * H <= 256 and A <= 8 and pol.log_std.dtype == torch.float32)
-        st = dict(key=key, fused=fused, out=None, step=None, gen=None, noise=None,
-                  w=torch.tensor(self.default_weights, dtype=torch.float64, device=dev).repeat(B, 1).contiguous())
-        if fused:
-            st["fg"] = dict(act=z(B, A), val=z(B), logp=z(B), w=z(B, 3, dt=torch.float64), rs=z(B, dt=torch.float64),
-                            noise=z(B, A))
-            if pol.use_sde:
-                if deterministic:
-                    st["noise"] = z(B, H, A)               # read by the kernel: latent @ (std * 0) = 0
-                else:
-                    st["fg"]["sde_epoch"] = z(1, dt=torch.int64)
-            elif not deterministic:
-                st["step"] = z(1, dt=torch.int64)
+        st = dict(key=key, fused=dev.type == "cuda" and self._fusable(), out=None, step=None, gen=None, noise=None)
+        if st["fused"]:
+            st["policy_step"] = self._fused_policy(key)
+            st["fg"] = st["policy_step"].tensors
+            if not pol.use_sde:                # None when deterministic: the kernel reads the all-zero noise instead
+                st["step"] = st["fg"]["step"]
+        elif deterministic:
+            st["noise"] = z(B, H, A) if pol.use_sde else z(B, A)
         else:
-            if deterministic:
-                st["noise"] = z(B, H, A) if pol.use_sde else z(B, A)
-            else:
-                st["gen"] = torch.Generator(device=dev)
-                st["gen"].manual_seed(seed)
-                if pol.use_sde:
-                    st["noise"] = z(B, H, A, dt=pol.log_std.dtype).normal_(generator=st["gen"])
+            st["gen"] = torch.Generator(device=dev)
+            st["gen"].manual_seed(seed)
+            if pol.use_sde:
+                st["noise"] = z(B, H, A, dt=pol.log_std.dtype).normal_(generator=st["gen"])
+        self._act_buffers(st, B, dev)
         self._act_state = st
         return st
 
@@ -1446,6 +1384,72 @@ class MPCRLAgent:
             if self.policy.use_sde:
                 st["noise"].normal_(generator=st["gen"])
 
+
+class MPCRLAgent(_PolicyAgent):
+    """The reference's `trainer.predict(obs)` (trainers/trainer.py:342-368) for a batch of observations: the policy forward,
+    then the MPC with its output - version "v0" hands action 0 to the MPC as the reference speed, "v1" actions 0..2 as the
+    cost weights.  Like the reference the policy output is stochastic and NOT clipped (SURVEY 3.3), whatever the algorithm.
+
+    gSDE policies: the reference draws ONE exploration matrix when it loads a checkpoint (agents/ppo_mpc.py:627-628) and
+    predict never resamples, so every later prediction explores with that same matrix.  reset_noise() draws it per
+    environment (one matrix per row of the batch, kept until the next reset_noise()); without it the policy's single matrix
+    serves every row, as in the reference."""
+
+    def __init__(self, policy: ActorCritic, engine, version: str = "v0", algorithm: str = "ppo",
+                 default_weights=(1.0, 1.0, 1.0), collision_cost: bool = False):
+        if version not in ("v0", "v1") or algorithm not in ("ppo", "a2c"):
+            raise ValueError("version must be v0|v1 and algorithm ppo|a2c")
+        if version == "v1" and policy.action_dim < 3:
+            raise ValueError("v1 needs an action of at least 3 components (speed, control, input_diff weights)")
+        self.policy, self.engine, self.version, self.algorithm = policy, engine, version, algorithm
+        self._mode = version
+        self.default_weights = tuple(float(w) for w in default_weights)
+        self.collision_cost = bool(collision_cost)
+
+    @staticmethod
+    def _sb3_settings(meta, kw):
+        """version / algorithm from the checkpoint unless given"""
+        return dict(dict(version=meta["version"] or "v0", algorithm=meta["algorithm"] or "ppo"), **kw)
+
+    @torch.no_grad()
+    def reset_noise(self, n: int, generator=None):
+        self.policy.reset_noise(n, generator=generator)
+
+    def _weights(self, B, dev):
+        return torch.tensor(self.default_weights, dtype=torch.float64, device=dev).repeat(B, 1).contiguous()
+
+    @torch.no_grad()
+    def predict_batch(self, obs_batch, deterministic: bool = False, generator=None):
+        """obs_batch [B, 10, 8] -> dict(act [B, 2], status, iters, rl_action [B, A]).  A torch tensor on a GPU goes through
+        engine.predict_batch_torch (zero-copy, synchronised before returning); anything else through engine.predict_batch."""
+        actions = self.policy_output(obs_batch, deterministic, generator)
+        weights, ref_speed = mpc_inputs(actions, self.version, self._weights(actions.shape[0], actions.device))
+        if actions.is_cuda and hasattr(self.engine, "predict_batch_torch"):
+            obs = torch.as_tensor(obs_batch, dtype=torch.float32, device=actions.device).contiguous()
+            out = self.engine.predict_batch_torch(obs, weights, ref_speed, collision_cost=self.collision_cost, sync=True)
+        else:
+            out = self.engine.predict_batch(np.asarray(torch.as_tensor(obs_batch, dtype=torch.float32).cpu()),
+                                            weights.cpu().numpy(), None if ref_speed is None else ref_speed.cpu().numpy(),
+                                            collision_cost=self.collision_cost)
+        return dict(out, rl_action=actions)
+
+    # ---- closed-loop evaluation (_PolicyAgent.act_batch_torch): the MPC through engine.predict_batch_torch with the policy's
+    #      action mapped like mpc_inputs and unclipped (trainer.predict)
+    def _fusable(self):
+        return fits_fused_policy(self.policy, self.engine) and hasattr(self.engine, "predict_batch_torch")
+
+    def _act_buffers(self, st, B, dev):
+        st["w"] = self._weights(B, dev)
+
+    def _act(self, st, obs, actions):
+        if actions is None:                    # the fused launch left the MPC's inputs in its buffers
+            fg = st["fg"]
+            weights, ref_speed = (fg["w"], None) if self.version == "v1" else (st["w"], fg["rs"])
+        else:
+            weights, ref_speed = mpc_inputs(actions, self.version, st["w"])
+        st["out"] = self.engine.predict_batch_torch(obs, weights, ref_speed, collision_cost=self.collision_cost, out=st["out"])
+        return st["out"]
+
     def predict(self, obs, deterministic: bool = False, generator=None):
         """One observation [10, 8] -> the MPC action [2] (trainer.predict)."""
         out = self.predict_batch(torch.as_tensor(obs, dtype=torch.float32)[None], deterministic, generator)
@@ -1453,7 +1457,7 @@ class MPCRLAgent:
         return act.cpu().numpy() if isinstance(act, torch.Tensor) else act
 
 
-class PPOAgent:
+class PPOAgent(_PolicyAgent):
     """The reference's end-to-end baseline (agents/ppo_agent.py `PPOAgent`, the `ppo` model of main/model_comparison.py): an SB3
     MlpPolicy whose two outputs are the vehicle's controls, with no MPC in between.  The environment's action type
     (highway-env's ContinuousAction) clips the action to [-1, 1] and scales it onto the acceleration / steering ranges
@@ -1461,22 +1465,12 @@ class PPOAgent:
     Gaussian policies with action_dim 2 only.  `engine` (an MPCEngine) is used for its library alone - the fused policy step
     mpc_policy_control on a GPU; None runs the policy in torch, on any device."""
 
+    DETERMINISTIC = True           # agents/ppo_agent.py's default
+    _mode = "direct"
+
     def __init__(self, policy: ActorCritic, engine=None):
         _check_direct_policy(policy)
         self.policy, self.engine = policy, engine
-
-    @classmethod
-    def from_sb3(cls, path, engine=None, device="cpu"):
-        """Load a checkpoint (ActorCritic.load_sb3; what ActorCritic.save_sb3 writes) and wrap it -> (agent, meta)."""
-        pol, meta = ActorCritic.load_sb3(path, device=device)
-        return cls(pol, engine), meta
-
-    @torch.no_grad()
-    def policy_output(self, obs, deterministic: bool = True, generator=None):
-        self.policy.eval()
-        obs = torch.as_tensor(obs, dtype=torch.float32, device=self.policy.log_std.device)
-        actions, _, _ = self.policy(obs, deterministic=deterministic, generator=generator)
-        return actions
 
     def predict(self, obs, deterministic: bool = True, generator=None):
         """One observation [10, 8] -> the normalised action [2] float32 clipped to [-1, 1], what SB3's `model.predict`
@@ -1492,65 +1486,18 @@ class PPOAgent:
         zi = lambda: torch.zeros(actions.shape[0], dtype=torch.int32, device=actions.device)
         return dict(act=map_control(actions), rl_action=actions, status=zi(), iters=zi())
 
-    # ---- closed-loop evaluation (evaluate.evaluate_agent): the contract of MPCRLAgent.act_batch_torch ---------------------
-    @torch.no_grad()
-    def act_batch_torch(self, obs, deterministic: bool = False, seed: int = 0, env_offset: int = 0):
-        """obs float32 device tensor [B, 10, 8] -> dict(act [B, 2] f64 controls, status, iters (zeros), step, generator).
-        Enqueue-only, the same output tensors every call.  On a GPU with an engine one mpc_policy_control launch, its noise
-        keyed by (seed, env_offset + b, step) - `step` the int64 [1] counter the caller advances once per step
-        (mpc_episode_stats does); otherwise ActorCritic.act, drawing from `generator` (seeded by seed), and map_control.
-        deterministic: the mean.  restart_actions() puts the counter / generator back to the start."""
-        import ctypes
-        B, dev = int(obs.shape[0]), obs.device
-        key = (B, dev, bool(deterministic), int(seed), int(env_offset))
-        st = getattr(self, "_act_state", None)
-        if st is None or st["key"] != key:
-            st = self._act_init(key)
-        pol = self.policy
-        if st["fused"]:
-            f, lib = pol._fz, self.engine._lib
-            p = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-            rc = lib.mpc_policy_control(dev.index, B, f["b1"].numel(), p(obs), p(f["w1"]), p(f["b1"]), p(f["w2"]), p(f["b2"]),
-                                        p(f["wh"]), p(f["bh"]), p(f["std"]), p(f["c0"]), p(st["noise"]),
-                                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(env_offset), p(st["step"]), p(st["actions"]),
-                                        p(st["val"]), p(st["logp"]), p(st["out"]["act"]),
-                                        ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if rc != 0:
-                raise RuntimeError(f"mpc_policy_control failed ({rc}): {lib.mpc_last_error().decode()}")
-        else:
-            actions, _, _ = pol.act(obs, generator=st["gen"], noise=st["noise"] if deterministic else None)
+    # ---- closed-loop evaluation (_PolicyAgent.act_batch_torch): act = the controls, written by the fused launch itself or by
+    #      map_control; status and iters stay zero
+    def _fusable(self):
+        return fits_fused_policy(self.policy, self.engine)
+
+    def _act_buffers(self, st, B, dev):
+        zi = lambda: torch.zeros(B, dtype=torch.int32, device=dev)
+        st["scale"] = control_scale(dev)
+        st["out"] = dict(act=st["fg"]["ctrl"] if st["fused"] else torch.zeros((B, 2), dtype=torch.float64, device=dev),
+                         status=zi(), iters=zi())
+
+    def _act(self, st, obs, actions):
+        if actions is not None:
             map_control(actions, out=st["out"]["act"], scale=st["scale"])
-        return dict(st["out"], step=st["step"], generator=st["gen"])
-
-    def _act_init(self, key):
-        B, dev, deterministic, seed, _ = key
-        pol = self.policy
-        pol.eval()
-        pol.refresh_fused()
-        z = lambda *sh, dt=torch.float32: torch.zeros(sh, dtype=dt, device=dev)
-        fused = (dev.type == "cuda" and hasattr(self.engine, "_lib") and pol.pi[0].in_features == VEHICLES_COUNT * 8 and
-                 2 * pol.pi[0].out_features <= 256 and pol.log_std.dtype == torch.float32)
-        st = dict(key=key, fused=fused, step=None, gen=None, noise=z(B, 2), scale=control_scale(dev),
-                  out=dict(act=z(B, 2, dt=torch.float64), status=z(B, dt=torch.int32), iters=z(B, dt=torch.int32)))
-        if fused:
-            st.update(actions=z(B, 2), val=z(B), logp=z(B))
-            if not deterministic:              # drawn by the kernel; deterministic reads the all-zero noise instead
-                st["step"] = z(1, dt=torch.int64)
-        elif not deterministic:
-            st["gen"] = torch.Generator(device=dev)
-            st["gen"].manual_seed(seed)
-        self._act_state = st
-        return st
-
-    @torch.no_grad()
-    def restart_actions(self):
-        """Put the evaluation's noise counter / generator back to where act_batch_torch started them (in place: a captured
-        graph reads them at their addresses)."""
-        st = getattr(self, "_act_state", None)
-        if st is None:
-            return
-        self.policy.refresh_fused()
-        if st["step"] is not None:
-            st["step"].zero_()
-        if st["gen"] is not None:
-            st["gen"].manual_seed(st["key"][3])
+        return st["out"]

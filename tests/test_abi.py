@@ -9,10 +9,145 @@ import pytest
 from conftest import ROOT
 
 
-def _declared_symbols():
+def _header_text():
+    """include/mpc_mi355x.h without its comments"""
     text = open(os.path.join(ROOT, "include", "mpc_mi355x.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(mpc_[a-z_]+)\s*\(", text)))
+    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+
+
+def _declared_symbols():
+    return sorted(set(re.findall(r"\b(mpc_[a-z_]+)\s*\(", _header_text())))
+
+
+def _prototype(name):
+    """[(parameter name, kind)] of `name`'s prototype in the header, kinds as engine.SIGNATURES spells them."""
+    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, _header_text())
+    assert m, f"{name}: no prototype in include/mpc_mi355x.h"
+    out = []
+    for decl in m.group(1).split(","):
+        ctype, pname = re.fullmatch(r"\s*(.*?)(\w+)\s*", decl, flags=re.S).groups()
+        ctype = " ".join(ctype.replace("*", " * ").split())
+        if ctype.endswith("*"):
+            kind = "perception" if ctype == "const mpc_perception *" else "ptr"
+        else:
+            kind = {"int32_t": "i32", "uint64_t": "u64", "double": "f64"}[ctype]      # any other type: the table has no kind for it
+        out.append((pname, kind))
+    return out
+
+
+I32, U64, F64, VP = ctypes.c_int32, ctypes.c_uint64, ctypes.c_double, ctypes.c_void_p
+_SYNTH_HEAD = [I32, I32, I32, F64, F64, U64, I32, VP, I32]
+
+
+def _argtypes_before_the_table():
+    """The argtypes lists load_library wrote out by hand (as counts) before SIGNATURES, element for element."""
+    from mpc_rl_for_avs_amd.engine import PerceptionParams
+    control = [I32] * 3 + [VP] * 10 + [U64, I32, VP] + [VP] * 5
+    return dict(
+        mpc_synth_env_step=_SYNTH_HEAD + [VP] * 15 + [I32, VP],
+        mpc_synth_env_step_idm=_SYNTH_HEAD + [VP] * 18 + [I32, VP],
+        mpc_policy_act=[I32] * 4 + [VP] * 10 + [U64, I32, VP] + [I32] * 2 + [VP] * 6,
+        mpc_policy_act_sde=[I32] * 4 + [VP] * 9 + [U64, I32, VP, VP] + [I32] * 3 + [VP] * 6,
+        mpc_policy_control=control,
+        mpc_policy_control_tile=[I32] + control,
+        mpc_rollout_record=[I32] * 6 + [VP] * 22,
+        mpc_rollout_finish=[I32] * 6 + [VP] * 4 + [F64] * 2 + [VP] * 3,
+        mpc_episode_stats=[I32] * 4 + [VP] * 14 + [VP],
+        mpc_drive_metrics=[I32] * 6 + [F64] + [VP] * 9 + [VP],
+        mpc_interaction_metrics=[I32] * 6 + [F64] + [VP] * 15 + [VP],
+        mpc_perceive=[I32] * 5 + [ctypes.POINTER(PerceptionParams)] + [VP] * 6 + [VP])
+
+
+def test_signature_table_is_the_header():
+    """engine.SIGNATURES, which orders engine.call's named arguments, against the prototypes: the same parameter names in the
+    same order, every kind the C type's, and the argtypes built from it the lists the binding had before the table."""
+    from mpc_rl_for_avs_amd import engine
+    before = _argtypes_before_the_table()
+    assert sorted(engine.SIGNATURES) == sorted(before) and len(before) == 12
+    lib = engine.load_library()
+    for name, sig in engine.SIGNATURES.items():
+        assert list(sig) == _prototype(name), name
+        assert len({n for n, _ in sig}) == len(sig), name
+        assert list(getattr(lib, name).argtypes) == before[name], name
+        assert getattr(lib, name).restype is ctypes.c_int, name
+
+
+class RecordingLib:
+    """Stands in for the shared library: every mpc_* attribute records its positional arguments and returns `rc`."""
+
+    def __init__(self, rc=0, error=b"the stub's text"):
+        self.rc, self.error, self.calls = rc, error, []
+
+    def mpc_last_error(self):
+        return self.error
+
+    def __getattr__(self, name):
+        if not name.startswith("mpc_"):
+            raise AttributeError(name)
+
+        def entry(*args):
+            self.calls.append((name, args))
+            return self.rc
+        return entry
+
+    def named(self, i=-1):
+        """(entry point, {parameter name: argument}) of call i, by the header's order - not by engine.SIGNATURES."""
+        name, args = self.calls[i]
+        names = [n for n, _ in _prototype(name)]
+        assert len(args) == len(names), name
+        return name, dict(zip(names, args))
+
+
+def address(a):
+    return None if a is None else a.value
+
+
+def test_call_marshals_by_name():
+    import torch
+    from mpc_rl_for_avs_amd import engine
+    lib = RecordingLib()
+    T, B = 2, 3
+    row, last = torch.zeros(T * B * 85), torch.zeros(B)
+    dones = torch.zeros(B, dtype=torch.bool)
+    adv, ret = torch.zeros(T, B), torch.zeros(T, B)
+    kw = dict(stream=None, returns=ret, advantages=adv, gae_lambda=0.95, gamma=0.99, terminal_values=None, dones=dones,
+              last_values=last, row=row, keep_terminal=0, cols=85, A=1, B=B, T=T, device=0)      # in reverse on purpose
+    engine.call("mpc_rollout_finish", lib=lib, **kw)
+    (name, args), = lib.calls
+    assert name == "mpc_rollout_finish" and args[:6] == (0, T, B, 1, 85, 0) and args[10:12] == (0.99, 0.95)
+    assert [address(a) for a in args[6:10]] == [row.data_ptr(), last.data_ptr(), dones.view(torch.uint8).data_ptr(), None]
+    assert args[9] is None and args[14] is None                     # None stays None, the stream's included
+    assert [address(a) for a in args[12:14]] == [adv.data_ptr(), ret.data_ptr()]
+    assert all(isinstance(a, ctypes.c_void_p) for a in args[6:9] + args[12:14])
+    # a stream (a torch stream by its handle, or the handle itself) and the perception struct
+    class Stream:
+        cuda_stream = 0x1234
+    p = engine.PerceptionParams(struct_size=ctypes.sizeof(engine.PerceptionParams), p_drop=0.25)
+    engine.call("mpc_perceive", lib=lib, device=0, B=B, R=10, S=0, reset=1, params=p, obs_true=ret, occluders=None,
+                obs_seen=row, row_class=dones, counts=last, ctr=adv, stream=Stream())
+    _, d = lib.named()
+    assert address(d["obs_true"]) == ret.data_ptr() and address(d["stream"]) == 0x1234 and d["occluders"] is None
+    engine.call("mpc_rollout_finish", lib=lib, **dict(kw, stream=0x5678))
+    assert address(lib.calls[-1][1][14]) == 0x5678
+    assert ctypes.cast(d["params"], ctypes.POINTER(engine.PerceptionParams)).contents.p_drop == 0.25
+    # a missing and an unknown keyword: TypeError naming the entry point and the parameter, nothing called
+    lib.calls.clear()
+    short = {k: v for k, v in kw.items() if k != "gamma"}
+    with pytest.raises(TypeError, match=r"mpc_rollout_finish.*missing.*'gamma'"):
+        engine.call("mpc_rollout_finish", lib=lib, **short)
+    with pytest.raises(TypeError, match=r"mpc_rollout_finish.*unexpected.*'lam'"):
+        engine.call("mpc_rollout_finish", lib=lib, lam=1.0, **kw)
+    with pytest.raises(TypeError, match=r"mpc_rollout_finish.*('gamma'|'lam')"):
+        engine.call("mpc_rollout_finish", lib=lib, lam=1.0, **short)
+    assert lib.calls == []
+    # a refusal: EngineError (a RuntimeError) with the entry point called and the library's text
+    bad = RecordingLib(rc=-1, error=b"sde_epoch and sde_noise both given")
+    sde = {n: None if k == "ptr" else 0 for n, k in engine.SIGNATURES["mpc_policy_act_sde"]}
+    with pytest.raises(engine.EngineError, match=r"^mpc_policy_act_sde failed \(-1\): sde_epoch and sde_noise both given$"):
+        engine.call("mpc_policy_act_sde", lib=bad, **sde)
+    assert issubclass(engine.EngineError, RuntimeError) and [c[0] for c in bad.calls] == ["mpc_policy_act_sde"]
+    with pytest.raises(engine.EngineError, match=r"^mpc_rollout_finish failed \(-1\): "):
+        engine.call("mpc_rollout_finish", lib=bad, **kw)
 
 
 def test_library_exports_every_declared_symbol():

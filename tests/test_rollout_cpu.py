@@ -181,7 +181,7 @@ def test_fused_rollout_forward_is_the_policy():
 @pytest.mark.parametrize("A,version,clip", [(1, "v0", True), (3, "v1", True), (4, "v1", False), (2, "v0", False)])
 def test_rollout_glue_code_is_the_policy_and_the_buffer_row(A, version, clip):
     """csrc/mpc_rollout_glue.hpp (what mpc_policy_act / mpc_rollout_record run per thread), compiled for the host, against the
-    torch ops it replaces: ActorCritic.act + BatchedCollector.mpc_inputs, and RolloutBuffer.add with the collector's
+    torch ops it replaces: ActorCritic.act + rollout.mpc_inputs, and RolloutBuffer.add with the collector's
     carry-over and counters."""
     import ctypes
     import glue_host
@@ -430,3 +430,144 @@ def test_a_step_past_the_buffer_is_never_silent():
     col._roll["counts"][4] = 2
     with pytest.raises(IndexError, match="past the end of the buffer"):
         col._rollout_stats(3)
+
+
+# ---- which tensor goes where: the fused step on CPU tensors against a library that only records -------------------------------
+class _RecordingEngine:
+    """An engine whose library records (tests/test_abi.py: RecordingLib) and whose solve returns fixed tensors."""
+
+    def __init__(self, B):
+        from test_abi import RecordingLib
+        self._lib = RecordingLib()
+        self.out = dict(act=torch.zeros((B, 2), dtype=torch.float64), status=torch.zeros(B, dtype=torch.int32),
+                        iters=torch.zeros(B, dtype=torch.int32))
+        self.solves = []
+
+    def predict_batch_torch(self, obs, weights, ref_speed=None, collision_cost=False, out=None, sync=False, warm_start=False):
+        self.solves.append((obs, weights, ref_speed))
+        return self.out
+
+
+class _HipEnvOnTheCPU:
+    """What the collector's fused step touches of SyntheticIntersectionEnv(backend="hip"): outputs at fixed addresses and a
+    step that computes nothing."""
+    backend, env_offset = "hip", 7
+
+    def __init__(self, B):
+        self.num_envs, self.device, self.stepped = B, torch.device("cpu"), []
+        u8 = lambda: torch.zeros(B, dtype=torch.uint8)
+        self._out = dict(obs=torch.zeros(B, 10, 8), terminal_obs=torch.zeros(B, 10, 8), reward=torch.zeros(B), done=u8(),
+                         truncated=u8(), crashed=u8(), arrived=u8())
+
+    def reset(self):
+        return self._out["obs"]
+
+    def step(self, action):
+        self.stepped.append(action)
+
+
+def _arrived(got: dict, want: dict):
+    """Every parameter of the call accounted for: a tensor by its address, anything else by value."""
+    import ctypes
+    assert set(got) == set(want)
+    for n, w in want.items():
+        if torch.is_tensor(w):
+            assert isinstance(got[n], ctypes.c_void_p) and got[n].value == w.data_ptr(), n
+        else:
+            assert got[n] is None if w is None else got[n] == w and type(got[n]) is type(w), n
+
+
+def _policy_args(pol, step, obs, seed, **rest):
+    f, t = pol._fz, step.tensors
+    want = dict(device=None, B=3, H2=16, obs=obs, w1=f["w1"], b1=f["b1"], w2=f["w2"], b2=f["b2"], wh=f["wh"], bh=f["bh"],
+                noise_seed=seed, env_offset=7, actions=t["act"], values=t["val"], log_probs=t["logp"], stream=None)
+    if step.mode != "direct":
+        v1 = step.mode == "v1"
+        want.update(A=pol.action_dim, version_v1=int(v1), mpc_weights=t["w"] if v1 else None,
+                    mpc_ref_speed=None if v1 else t["rs"])
+    if pol.use_sde:
+        want.update(sde_std=f["std"])
+    else:
+        want.update(std_=f["std"], c0=f["c0"], noise=t["noise"])
+    return dict(want, **rest)
+
+
+@pytest.mark.parametrize("version, algorithm, A, sde", [("v0", "ppo", 1, False), ("v1", "ppo", 3, False), ("v0", "a2c", 1, False),
+                                                        ("v1", "a2c", 4, False), ("v0", "ppo", 1, True), ("direct", "ppo", 2, False),
+                                                        ("direct", "a2c", 2, False)])
+def test_fused_collector_step_names_every_tensor(version, algorithm, A, sde):
+    """The collector's fused step (policy launch, solve, environment, record) with B = 3, hidden 8, n_steps = 2: each
+    parameter of the two glue calls, by the header's name, is the tensor the step means."""
+    torch.manual_seed(0)
+    B, ppo, direct = 3, algorithm == "ppo", version == "direct"
+    env, eng = _HipEnvOnTheCPU(B), _RecordingEngine(B)
+    pol = rollout.ActorCritic(A, hidden=8, use_sde=sde)
+    col = rollout.BatchedCollector(env, pol, eng, version=version, algorithm=algorithm, n_steps=2, seed=5, use_graph=False,
+                                   sde_sample_freq=2 if sde else -1)
+    assert col.fused_glue and col._graph is None and eng._lib.calls == []
+    fg, buf, o = col._fg, col.buffer, env._out
+    col._rollout_step()
+    assert [c[0] for c in eng._lib.calls] == [("mpc_policy_control" if direct else "mpc_policy_act_sde" if sde else "mpc_policy_act"),
+                                              "mpc_rollout_record"]
+    if direct:
+        more = dict(control=fg["ctrl"], noise_step=fg["step"])
+    elif sde:
+        more = dict(clip=int(ppo), sde_noise=None, sde_epoch=fg["sde_epoch"], sde_step=buf.pos_dev, sde_sample_freq=2)
+    else:
+        more = dict(clip=int(ppo), noise_step=fg["step"])
+    _arrived(eng._lib.named(0)[1], _policy_args(pol, col._policy_step, col._last_obs, 5, **more))
+    if direct:
+        assert eng.solves == [] and col.last_mpc["act"] is fg["ctrl"] and not col.last_mpc["status"].any()
+        mpc_act, status = fg["ctrl"], col._direct["status"]
+    else:
+        (obs, weights, ref_speed), = eng.solves
+        assert obs is col._last_obs
+        assert (weights is fg["w"] and ref_speed is None) if version == "v1" else \
+            (weights is col.default_weights and ref_speed is fg["rs"])
+        mpc_act, status = eng.out["act"], eng.out["status"]
+    assert len(env.stepped) == 1 and env.stepped[0] is mpc_act
+    assert (buf.terminal_obs is not None) == ppo
+    _arrived(eng._lib.named(1)[1], dict(
+        device=None, T=2, B=B, A=A, cols=buf._cols, keep_terminal=int(ppo), row=buf._row, mpc_actions_buf=buf.mpc_actions,
+        pos_dev=buf.pos_dev, ticket=col._ticket, last_obs=col._last_obs, last_starts=col._last_episode_starts,
+        actions=fg["act"], values=fg["val"], log_probs=fg["logp"], mpc_act=mpc_act, mpc_status=status, new_obs=o["obs"],
+        reward=o["reward"], done=o["done"], terminal_obs=o["terminal_obs"] if ppo else None,
+        truncated=o["truncated"] if ppo else None, crashed=o["crashed"], arrived=o["arrived"], counts=col._roll["counts"],
+        dones_out=col._roll["dones"], step_counter=fg["step"], stream=None))
+    # the rollout's end: mpc_rollout_finish by name
+    col._finish_rollout()
+    name, d = eng._lib.named()
+    assert name == "mpc_rollout_finish"
+    assert d["terminal_values"] is None if not ppo else d["terminal_values"] is not None
+    for n in ("last_values", "terminal_values"):           # temporaries of the call: checked above, not by address
+        d.pop(n)
+    _arrived(d, dict(device=None, T=2, B=B, A=A, cols=buf._cols, keep_terminal=int(ppo), row=buf._row, dones=col._roll["dones"],
+                     gamma=0.99, gae_lambda=0.95, advantages=buf.advantages, returns=buf.returns, stream=None))
+
+
+@pytest.mark.parametrize("deterministic", [False, True])
+@pytest.mark.parametrize("kind, A, sde", [("v0", 1, False), ("v1", 3, False), ("v0", 1, True), ("v1", 3, True), ("direct", 2, False)])
+def test_fused_agent_step_names_every_tensor(kind, A, sde, deterministic):
+    """The agents' fused policy launch (the FusedPolicy their act_batch_torch builds), stochastic and deterministic: never
+    clipped; gSDE one matrix for the whole evaluation (epoch counter, no step, sde_sample_freq -1); deterministic the
+    all-zero noise with no counter."""
+    torch.manual_seed(0)
+    B, eng = 3, _RecordingEngine(3)
+    pol = rollout.ActorCritic(A, hidden=8, use_sde=sde)
+    agent = rollout.PPOAgent(pol, eng) if kind == "direct" else rollout.MPCRLAgent(pol, eng, version=kind)
+    assert agent._fusable()
+    pol.refresh_fused()
+    step = agent._fused_policy((B, torch.device("cpu"), deterministic, 11, 7))
+    t, obs = step.tensors, torch.zeros(B, 10, 8)
+    step.launch(obs)
+    name, d = eng._lib.named()
+    assert name == ("mpc_policy_control" if kind == "direct" else "mpc_policy_act_sde" if sde else "mpc_policy_act")
+    assert (t["step"] is None) == deterministic and (t["sde_epoch"] is not None) == (sde and not deterministic)
+    if sde:
+        more = dict(clip=0, sde_noise=t["noise"], sde_epoch=t["sde_epoch"], sde_step=None, sde_sample_freq=-1)
+        assert (t["noise"] is None) != deterministic
+        assert t["noise"] is None or (tuple(t["noise"].shape) == (B, 8, A) and not t["noise"].any())
+    else:
+        more = dict(noise_step=t["step"], **(dict(control=t["ctrl"]) if kind == "direct" else dict(clip=0)))
+        assert tuple(t["noise"].shape) == (B, A) and not t["noise"].any()
+    _arrived(d, _policy_args(pol, step, obs, 11, **more))
