@@ -192,15 +192,19 @@ def _certify_chunk(p, X, U, eps_c, wall_tol, relax, slack_max):
             unit = np.where(free, scale[b] / cn, np.minimum(ubv, 1e300))
             hi = np.where(free, np.inf, 1.0)
             Gs = G * unit[None, :] / scale[b]
-            sol = lsq_linear(Gs, -rb / scale[b], bounds=(np.zeros(len(ub)), hi), method="bvls", tol=1e-15, max_iter=1000)
-            xs = sol.x
-            if np.abs(Gs @ xs + rb / scale[b]).max() > 1e-10:
+            try:
+                xs = lsq_linear(Gs, -rb / scale[b], bounds=(np.zeros(len(ub)), hi), method="bvls", tol=1e-15, max_iter=1000).x
+            except np.linalg.LinAlgError:
+                # BVLS's inner unbounded least squares can fail outright (LAPACK's SVD not converging; seen at N = 63 with
+                # 400+ candidate bounds on a warm-started answer of the oracle): the two other methods below decide
+                xs = None
+            if xs is None or np.abs(Gs @ xs + rb / scale[b]).max() > 1e-10:
                 # BVLS can stop early on these badly conditioned 40 x ~120 systems (cond ~ 1e11) with a set of variables parked at
                 # their upper bounds (round 5: instance 2791 of config 3, seed 0, ended at 1.4e-8 where the optimum is 2e-16 - the
                 # reason two gates had been loosened).  Two other exact methods for the same convex problem, best of the three:
                 # non-negative least squares (Lawson-Hanson; optimal for the boxed problem whenever its solution respects the
                 # boxes, which it does unless a complementarity box really binds) and the trust-region reflective method.
-                cand = [xs]
+                cand = [] if xs is None else [xs]
                 xn, _ = nnls(Gs, -rb / scale[b])
                 if np.all(xn <= hi):
                     cand.append(xn)
