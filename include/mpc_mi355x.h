@@ -498,6 +498,53 @@ int mpc_interaction_metrics(int32_t device, int32_t B, int32_t K, int32_t Q, int
                             double *state_f64, int32_t *rec_i32, double *rec_f64, void *stream);
 
 /*
+ * mpc_episode_trace (an addition within ABI 8: old clients never call it, nothing else changes) - the step-by-step record of
+ * the episodes of a closed-loop evaluation of B environments that someone will look at, beside mpc_episode_stats: every
+ * environment keeps the last W steps of its current episode in rings, and an episode that ends and is selected by its outcome
+ * is copied in chronological order to the next free slot of a store with capacity C (the model, the layouts and the
+ * per-environment append and commit in csrc/mpc_episode_trace.hpp).  Device pointers, enqueue only on `stream`, never
+ * synchronises (capturable in a hipGraph); two launches per call - the claim, one workgroup that ranks the environments whose
+ * episode ends with a wave ballot and hands out the slots in environment order, then one workgroup of four waves per
+ * environment for the append and the copy, 16 bytes per lane; no atomics, no scratch.  One call per policy step, after the
+ * environment's step and before the buffer the agent acted on is overwritten.
+ *
+ * Inputs of a step: terminal_obs [B][R][8] f32 (the scene after the step, before the auto-reset), obs [B][R][8] f32 (what the
+ * next step starts from), seen [B][R][8] f32 or NULL (what the agent acted on at this step, with a perception model), action
+ * [B][2] f64 as commanded, reward [B] f32, done, truncated, crashed, arrived [B] u8, status and iters [B] i32 (the step's
+ * solve).  Q: the quota of mpc_episode_stats; only episodes of ordinal j < Q are traced.  keep: the outcomes that are kept, a
+ * bit set of 1 collision (crashed on any step), 2 truncated, 4 success (arrived), 8 unsolved (a solve that is not
+ * MPC_STATUS_IS_SOLVED), 16 all; an episode is selected when keep & 16 or outcome & keep & 15.
+ * Running state: state_i32 [4][B] = steps of the current episode, crashed so far, unsolved so far, episode ordinal j.
+ * Rings: ring_scene [B][W + 1][R][8] f32 (scene t of the episode at index t mod (W + 1)), ring_seen [B][W][R][8] f32 or NULL,
+ * ring_act [B][W][2] f64, ring_reward [B][W] f32, ring_i32 [B][W][3] = status, iters, flags (bit 0 done, 1 truncated, 2
+ * crashed, 3 arrived); frame t at index t mod W.  slot [B] i32: work array between the two launches (the slot of an episode
+ * that ends on this step, else -1).
+ * Store: kept_scene [C][W + 1][R][8], kept_seen [C][W][R][8] or NULL, kept_act [C][W][2], kept_reward [C][W], kept_i32
+ * [C][W][3]: of a kept episode of T steps the last L = min(T, W), first = T - L: kept frame i is step first + i (i < L), kept
+ * scene i is s_{first + i} (i <= L); entries past L are not written.  index [C][6] i32 = environment b, ordinal j, steps T,
+ * first, outcome, the launch the episode ended on (1-based since the reset launch).  counts [4] i64 = matched, kept, dropped
+ * (selected, but the store was full), launches; matched = kept + dropped.  Selected episodes take slots 0, 1, .. ordered by
+ * the launch on which they ended, then by environment index.
+ *
+ * reset != 0 (issue it after the environments' reset; only obs is required): clear the running state and the counts, write
+ * obs as s_0 of every environment; the store is not touched.  Otherwise, for every environment with j < Q: append the frame
+ * and the scene terminal_obs; when done[b]: if the episode is selected and has a slot, copy the rings out and write its index
+ * row; then clear the running state, j += 1, and write obs[b] as s_0 of the next episode.  An environment with j == Q writes
+ * nothing.  Every scene plane (terminal_obs, obs, seen, ring_scene, ring_seen, kept_scene, kept_seen) must be 16-byte aligned.
+ * Errors (MPC_ERR_INVALID_ARG): B < 0, R outside 1 .. MPC_MAX_OTHERS + 1, Q < 1, W outside 1 .. 4096, C < 1, keep outside
+ * 1 .. 31, a NULL state / ring / slot / store / index / counts pointer, a NULL obs, a NULL step input of a non-reset launch,
+ * seen, ring_seen and kept_seen not all given or all NULL (a reset launch needs no seen), a misaligned scene plane.  B == 0
+ * is a no-op.
+ */
+int mpc_episode_trace(int32_t device, int32_t B, int32_t R, int32_t Q, int32_t W, int32_t C, int32_t keep, int32_t reset,
+                      const float *terminal_obs, const float *obs, const float *seen, const double *action,
+                      const float *reward, const uint8_t *done, const uint8_t *truncated, const uint8_t *crashed,
+                      const uint8_t *arrived, const int32_t *status, const int32_t *iters, int32_t *state_i32,
+                      float *ring_scene, float *ring_seen, double *ring_act, float *ring_reward, int32_t *ring_i32,
+                      int32_t *slot, float *kept_scene, float *kept_seen, double *kept_act, float *kept_reward,
+                      int32_t *kept_i32, int32_t *index, int64_t *counts, void *stream);
+
+/*
  * mpc_perceive (an addition within ABI 8: old clients never call it, nothing else changes) - a perception model between the
  * environment and the agent of a closed-loop evaluation: obs_seen is what the ego sees of the true scene obs_true under a
  * limited range, occlusion by the other vehicles' 5 m x 2 m rectangles and by static convex quadrilaterals, random dropout

@@ -33,6 +33,7 @@
 #include "mpc_perception.hpp"
 #include "mpc_interaction.hpp"
 #include "mpc_episode_stats.hpp"
+#include "mpc_episode_trace.hpp"
 
 namespace {
 
@@ -930,6 +931,62 @@ __global__ __launch_bounds__(64) void mpc_interaction_kernel(mpc::interact::Acco
         sf[(ia::kCarryProg + q) * B] = sprog;
         si[(ia::kCarryRoute + q) * B] = sroute;
     }
+}
+
+// episode trace recorder of a closed-loop evaluation (mpc_episode_trace.hpp), launch 1 of 2 - the claim: which of the episodes
+// that end on this step get which slot of the store.  ONE workgroup of sixteen waves walks the B environments in index order
+// in passes of 1024: each lane asks the header's ends_selected() of its environment (the running state is the one before the
+// step: the frame kernel changes it afterwards, in stream order), a wave ranks its lanes with a 64-bit ballot and a popcount
+// of the bits below the lane, the waves' totals go through LDS and every lane adds up the waves before its own; the matched
+// so far is carried in a register that every lane keeps alike.  Slots are therefore handed out in environment order, with no
+// atomics, and the order is part of the result.  Lane 0 advances the counts after the last pass; every lane read the kept
+// count before the first barrier.  A reset launch clears the counts.  Ballot and barriers sit in uniform control flow.
+constexpr int kTraceClaimThreads = 1024, kTraceFrameThreads = 256;
+__global__ __launch_bounds__(kTraceClaimThreads) void mpc_episode_trace_claim_kernel(mpc::trace::Recorder rec,
+                                                                                      mpc::trace::StepInputs in, int reset) {
+    namespace tr = mpc::trace;
+    __shared__ int s_total[kTraceClaimThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (reset) {
+        if (tid < tr::kCounts) rec.counts[tid] = 0;
+        return;
+    }
+    const long long kept_before = rec.counts[tr::kKept];
+    long long matched = 0;
+    for (int base = 0; base < rec.B; base += kTraceClaimThreads) {
+        const int b = base + tid;
+        const bool sel = b < rec.B && tr::ends_selected(rec, in, b);
+        const unsigned long long mask = __ballot(sel);
+        const int below = __popcll(mask & ((1ull << lane) - 1ull));
+        if (lane == 0) s_total[wave] = __popcll(mask);
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int w = 0; w < kTraceClaimThreads / 64; ++w) {
+            const int c = s_total[w];
+            total += c;
+            before += w < wave ? c : 0;
+        }
+        if (b < rec.B) rec.slot[b] = sel ? tr::slot_of(kept_before, matched + before + below, rec.C) : -1;
+        matched += total;
+        __syncthreads();                                   // the next pass overwrites s_total
+    }
+    if (tid == 0) tr::advance_counts(rec.counts, matched, rec.C);
+}
+
+// launch 2 of 2 - frame and commit: one workgroup per environment, FOUR waves.  The append is small (a scene is 2 R <= 34
+// chunks of 16 bytes, one per lane, and lane 0 writes the scalars), so one wave would do for it; the four are there for the
+// copy of an episode that ends with a slot, up to (2 W + 1) scenes of the rings to the store, as lane-strided 16-byte loads
+// and stores with 256 of them in flight per pass instead of 64.  The frame appended in this launch is read back by other
+// lanes during that copy: there is a WORKGROUP BARRIER between append and copy (the copy reads the rings only, one code
+// path), and a second one before s_0 of the next episode overwrites ring entry 0, which the copy may have read, and before
+// lane 0 writes the running state that every lane read at the start.  Both barriers sit in uniform control flow: every
+// condition before them depends on the environment alone.  No atomics, no LDS.
+struct TraceBarrier {
+    __device__ __forceinline__ void operator()(int) const { __syncthreads(); }
+};
+__global__ __launch_bounds__(kTraceFrameThreads) void mpc_episode_trace_frame_kernel(mpc::trace::Recorder rec,
+                                                                                      mpc::trace::StepInputs in, int reset) {
+    mpc::trace::step_env(rec, in, (int)blockIdx.x, reset != 0, (int)threadIdx.x, kTraceFrameThreads, TraceBarrier{});
 }
 
 // perception model of a closed-loop evaluation (mpc_perception.hpp): sixteen lanes per environment, four environments per
@@ -2043,6 +2100,43 @@ int mpc_interaction_metrics(int32_t device, int32_t B, int32_t K, int32_t Q, int
                                        ref_xy, conflict};
     hipLaunchKernelGGL(mpc_interaction_kernel, dim3((unsigned)((B + 3) / 4)), dim3(64), 0,
                        reinterpret_cast<hipStream_t>(stream_), acc, in, (int)reset);
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_episode_trace(int32_t device, int32_t B, int32_t R, int32_t Q, int32_t W, int32_t C, int32_t keep, int32_t reset,
+                      const float *terminal_obs, const float *obs, const float *seen, const double *action,
+                      const float *reward, const uint8_t *done, const uint8_t *truncated, const uint8_t *crashed,
+                      const uint8_t *arrived, const int32_t *status, const int32_t *iters, int32_t *state_i32,
+                      float *ring_scene, float *ring_seen, double *ring_act, float *ring_reward, int32_t *ring_i32,
+                      int32_t *slot, float *kept_scene, float *kept_seen, double *kept_act, float *kept_reward,
+                      int32_t *kept_i32, int32_t *index, int64_t *counts, void *stream_) {
+    namespace tr = mpc::trace;
+    if (B < 0 || R < 1 || R > MPC_MAX_OTHERS + 1 || Q < 1 || W < 1 || W > tr::kMaxWindow || C < 1 || keep < 1 || keep > 31)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_episode_trace: bad size (B >= 0, 1 <= R <= 17, Q >= 1, 1 <= W <= 4096, C >= 1, "
+                                         "1 <= keep <= 31)");
+    if (!state_i32 || !ring_scene || !ring_act || !ring_reward || !ring_i32 || !slot || !kept_scene || !kept_act ||
+        !kept_reward || !kept_i32 || !index || !counts)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_episode_trace: null state / ring / slot / store / index / counts pointer");
+    if (!obs) return fail(MPC_ERR_INVALID_ARG, "mpc_episode_trace: null obs");
+    if (!reset && (!terminal_obs || !action || !reward || !done || !truncated || !crashed || !arrived || !status || !iters))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_episode_trace: null step-input pointer of a non-reset launch");
+    if ((ring_seen != nullptr) != (kept_seen != nullptr) || (!reset && (seen != nullptr) != (ring_seen != nullptr)))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_episode_trace: seen, ring_seen and kept_seen must all be given or all be NULL");
+    for (const void *p : {(const void *)terminal_obs, (const void *)obs, (const void *)seen, (const void *)ring_scene,
+                          (const void *)ring_seen, (const void *)kept_scene, (const void *)kept_seen})
+        if (((uintptr_t)p & 15) != 0)
+            return fail(MPC_ERR_INVALID_ARG, "mpc_episode_trace: the observation, ring and store planes of scenes must be "
+                                             "16-byte aligned");
+    if (B == 0) return MPC_OK;
+    HIP_TRY(hipSetDevice(device));
+    const tr::Recorder rec{(int)B, (int)R, (int)Q, (int)W, (int)C, (int)keep, state_i32, ring_scene, ring_seen, ring_act,
+                           ring_reward, ring_i32, slot, kept_scene, kept_seen, kept_act, kept_reward, kept_i32, index, counts};
+    const tr::StepInputs in{terminal_obs, obs, seen, action, reward, done, truncated, crashed, arrived, status, iters};
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    hipLaunchKernelGGL(mpc_episode_trace_claim_kernel, dim3(1), dim3(kTraceClaimThreads), 0, stream, rec, in, (int)reset);
+    hipLaunchKernelGGL(mpc_episode_trace_frame_kernel, dim3((unsigned)B), dim3(kTraceFrameThreads), 0, stream, rec, in,
+                       (int)reset);
     HIP_TRY(hipGetLastError());
     return MPC_OK;
 }

@@ -1,6 +1,7 @@
 """ctypes binding of the C ABI (include/mpc_mi355x.h) - the only way Python reaches the HIP kernels: the entry points that
 take an engine handle through `MPCEngine`'s methods, the handle-less ones (environment step, policy step, rollout glue,
-evaluation accounting, perception) through `call` / `caller`, by parameter name, in the order of `SIGNATURES`.
+evaluation accounting, perception, episode traces) through `call` / `caller`, by parameter name, in the order of `SIGNATURES`
+and `EVALUATION_SIGNATURES`.
 
 There is no CPU fallback: if the shared library is missing, or no MI355X is visible, construction fails
 loudly (`EngineError`).  Host numpy arrays are copied by the library; torch device tensors are passed
@@ -100,13 +101,21 @@ SIGNATURES = {name: tuple(tuple(word.split(":")) for word in text.split()) for n
                             "stream:ptr",
     mpc_perceive="device:i32 B:i32 R:i32 S:i32 reset:i32 params:perception obs_true:ptr occluders:ptr obs_seen:ptr "
                  "row_class:ptr counts:ptr ctr:ptr stream:ptr").items()}
+# The entry points of the evaluation that came after that table: the same spelling, the same service through `caller` /
+# `call`; tests/test_episode_trace_cpu.py holds this one against the header.
+EVALUATION_SIGNATURES = {name: tuple(tuple(word.split(":")) for word in text.split()) for name, text in dict(
+    mpc_episode_trace="device:i32 B:i32 R:i32 Q:i32 W:i32 C:i32 keep:i32 reset:i32 terminal_obs:ptr obs:ptr seen:ptr "
+                      "action:ptr reward:ptr done:ptr truncated:ptr crashed:ptr arrived:ptr status:ptr iters:ptr "
+                      "state_i32:ptr ring_scene:ptr ring_seen:ptr ring_act:ptr ring_reward:ptr ring_i32:ptr slot:ptr "
+                      "kept_scene:ptr kept_seen:ptr kept_act:ptr kept_reward:ptr kept_i32:ptr index:ptr counts:ptr "
+                      "stream:ptr").items()}
 
 
 _EXPORTS = ["mpc_version", "mpc_last_error", "mpc_default_config", "mpc_default_config_sized", "mpc_create", "mpc_destroy",
             "mpc_set_reference", "mpc_solve_batch", "mpc_workspace_bytes", "mpc_predict_batch",
             "mpc_reset_env_state", "mpc_reset_env_mask", "mpc_get_env_state", "mpc_get_last_inputs",
             "mpc_ltv_solve_batch", "mpc_ltv_predict_batch", "mpc_env_state_bytes", "mpc_save_env_state",
-            "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_policy_control", "mpc_policy_control_tile", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_interaction_metrics", "mpc_perceive", "mpc_eval_nlp", "mpc_streams_overlap"]
+            "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_policy_control", "mpc_policy_control_tile", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_interaction_metrics", "mpc_episode_trace", "mpc_perceive", "mpc_eval_nlp", "mpc_streams_overlap"]
 ABI_VERSION = 8          # MPC_ABI_VERSION of include/mpc_mi355x.h this binding is written for
 MAX_OTHERS = 16
 _lib = None
@@ -185,7 +194,7 @@ def load_library(path: str | None = None):
     lib.mpc_set_diagnostics.restype = ctypes.c_int
     lib.mpc_get_last_paths.argtypes = [vp, ctypes.c_int32, dp, ip, vp]
     lib.mpc_get_last_paths.restype = ctypes.c_int
-    for name, sig in SIGNATURES.items():
+    for name, sig in list(SIGNATURES.items()) + list(EVALUATION_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = [_KINDS[kind] for _, kind in sig], ctypes.c_int
     lib.mpc_eval_nlp.argtypes = [vp, ctypes.c_int32] + [vp] * 5 + [ctypes.c_int32, ctypes.c_uint32] + [vp] * 4
@@ -219,11 +228,12 @@ def _caller(name, sig):
     return scope[name]
 
 
-_CALLERS = {name: _caller(name, sig) for name, sig in SIGNATURES.items()}
+_CALLERS = {name: _caller(name, sig) for name, sig in list(SIGNATURES.items()) + list(EVALUATION_SIGNATURES.items())}
 
 
 def caller(name: str):
-    """The handle-less entry point `name` as a function of keywords alone: every one of SIGNATURES[name] and no other (TypeError
+    """The handle-less entry point `name` as a function of keywords alone: every one of SIGNATURES[name] (or
+    EVALUATION_SIGNATURES[name]) and no other (TypeError
     naming the entry point and the parameter otherwise, before anything is called).  Python ints and floats pass through;
     a pointer is a torch tensor (its address; a bool tensor's bytes are the uint8 the kernels read) or None; `stream` is a
     torch stream, its raw handle or None; `params` of mpc_perceive a PerceptionParams.  Enqueue only; EngineError with the

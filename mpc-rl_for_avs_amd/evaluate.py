@@ -28,6 +28,11 @@ seen; the accounting and the drive metrics keep reading the true scene.
 (`InteractionMetrics`: how often another vehicle yields to the ego, how hard the ego makes it brake, the speed that costs the
 traffic, post-encroachment times where a traffic route crosses the ego's), computed per step from the simulator's own slots
 inside the same captured step (mpc_interaction_metrics), or by the same update in numpy on the CPU path.
+
+`trace=` keeps the step-by-step record of the episodes someone will look at (csrc/mpc_episode_trace.hpp, `EpisodeTrace`): the
+last `window` steps - scenes, actions, rewards, the solve's status, the flags, and with a perception model what the agent saw - of
+the episodes that ended with one of the outcomes in `keep`, in a store of `capacity` episodes on the device, filled inside the
+same captured step (mpc_episode_trace) in an order that does not depend on timing, or by the same update in numpy on the CPU path.
 """
 from __future__ import annotations
 
@@ -63,6 +68,13 @@ INTERACT_I32 = ("steps", "yield_steps", "forced_brake_steps", "forced_brake_even
 INTERACT_F64 = ("max_forced_decel", "speed_deficit", "min_pet")                     # rec_f64 [3][B][Q]
 PET_CRITICAL, ROUTES, SLOTS = 1.5, 12, 9
 INTERACT_STATE_I32, INTERACT_STATE_F64 = 9 + SLOTS, 4 + ROUTES + 2 * SLOTS
+# csrc/mpc_episode_trace.hpp: the outcome bits an EpisodeTrace keeps by name, the columns of its index, its counts, the flag
+# bits of a frame, the largest window
+TRACE_KEEP = dict(collision=1, truncated=2, success=4, unsolved=8, all=16, failed=3)
+TRACE_INDEX = ("env", "ordinal", "steps", "first", "outcome", "launch")             # mpc_episode_trace index [C][6]
+TRACE_COUNTS = ("matched", "kept", "dropped", "launches")                           # counts [4]
+TRACE_FLAGS = dict(done=1, truncated=2, crashed=4, arrived=8)
+TRACE_MAX_WINDOW = 4096
 
 
 def records_from_planes(rec_i32, rec_f64) -> dict:
@@ -840,6 +852,225 @@ class Perception:
         return {k: int(c[i]) for i, k in enumerate(PERCEPTION_COUNTS)}
 
 
+def _keep_bits(keep) -> int:
+    names = (keep,) if isinstance(keep, str) else tuple(keep)
+    bits = 0
+    for name in names:
+        if name not in TRACE_KEEP:
+            raise ValueError(f"keep: {name!r} is not one of {sorted(TRACE_KEEP)}")
+        bits |= TRACE_KEEP[name]
+    if bits == 0:
+        raise ValueError("keep names no outcome")
+    return bits
+
+
+class EpisodeTraces:
+    """The episodes an `EpisodeTrace` kept, on the host: `index` (dict of int arrays [n]: env - the global id, env_offset +
+    b -, ordinal, steps, first, outcome, launch), `counts` (dict: matched, kept, dropped, launches), the store's planes cut to
+    the n kept episodes (scene [n, W + 1, R, 8], seen [n, W, R, 8] or None, action [n, W, 2], reward [n, W], frame_i32
+    [n, W, 3]; entries past an episode's L = min(steps, W) are whatever the store held) and `nbytes`, the memory the recorder
+    took (running state, rings, work array and store).  `keep` is the bit set the recorder ran with."""
+
+    def __init__(self, index, counts, scene, seen, action, reward, frame_i32, keep, nbytes):
+        self.index, self.counts, self.keep, self.nbytes = index, counts, int(keep), int(nbytes)
+        self.scene, self.seen, self.action, self.reward, self.frame_i32 = scene, seen, action, reward, frame_i32
+
+    def __len__(self):
+        return int(self.index["env"].shape[0])
+
+    @property
+    def window(self) -> int:
+        return int(self.action.shape[1])
+
+    def episode(self, i: int) -> dict:
+        """Kept episode i in chronological order: its index fields as ints (env, ordinal, steps, first, outcome, launch),
+        and of its last L = min(steps, W) steps action [L, 2], reward [L], status, iters, flags [L] (TRACE_FLAGS), scene
+        [L + 1, R, 8] (scene k is the one step first + k started from; the last is the scene the episode ended in) and,
+        when it was recorded, seen [L, R, 8]."""
+        if not 0 <= int(i) < len(self):
+            raise IndexError(f"episode {i} of {len(self)}")
+        out = {k: int(v[i]) for k, v in self.index.items()}
+        L = min(out["steps"], self.window)
+        out.update(action=self.action[i, :L].copy(), reward=self.reward[i, :L].copy(), status=self.frame_i32[i, :L, 0].copy(),
+                   iters=self.frame_i32[i, :L, 1].copy(), flags=self.frame_i32[i, :L, 2].copy(),
+                   scene=self.scene[i, :L + 1].copy())
+        if self.seen is not None:
+            out["seen"] = self.seen[i, :L].copy()
+        return out
+
+    def save(self, path) -> None:
+        """One .npz with everything `load` needs."""
+        arrays = {f"index_{k}": v for k, v in self.index.items()}
+        arrays.update(counts=np.array([self.counts[k] for k in TRACE_COUNTS], np.int64), scene=self.scene, action=self.action,
+                      reward=self.reward, frame_i32=self.frame_i32, keep=np.int64(self.keep), nbytes=np.int64(self.nbytes))
+        if self.seen is not None:
+            arrays["seen"] = self.seen
+        np.savez_compressed(path, **arrays)
+
+    @classmethod
+    def load(cls, path) -> "EpisodeTraces":
+        with np.load(path) as z:
+            return cls({k: z[f"index_{k}"] for k in TRACE_INDEX}, {k: int(v) for k, v in zip(TRACE_COUNTS, z["counts"])},
+                       z["scene"], z["seen"] if "seen" in z.files else None, z["action"], z["reward"], z["frame_i32"],
+                       int(z["keep"]), int(z["nbytes"]))
+
+
+class EpisodeTrace:
+    """The step-by-step record of the episodes someone will look at (csrc/mpc_episode_trace.hpp has the model; layouts in
+    include/mpc_mi355x.h, mpc_episode_trace): every environment keeps the last `window` steps of its current episode in
+    rings on the device, and an episode of ordinal j < Q that ends with one of the outcomes in `keep` is copied, in
+    chronological order, to the next free of `capacity` slots, ordered by (launch on which it ended, environment); one that
+    finds the store full is counted as dropped.  keep: a name or an iterable of names from collision, truncated, success,
+    unsolved, all; "failed" is collision | truncated.  seen=True also records what the agent acted on (with a perception
+    model).  `update` after the environment's step is the kernel (backend "hip": enqueue only, capturable) or the same update
+    in numpy (backend "torch", for the CPU environment); both give the same bytes.  Memory is bounded by B, window and
+    capacity alone (`nbytes`)."""
+
+    def __init__(self, B: int, Q: int, device, backend: str = "torch", R: int = VEHICLES_COUNT, keep="failed",
+                 capacity: int = 64, window: int = EPISODE_STEPS, seen: bool = False, env_offset: int = 0):
+        if backend not in ("hip", "torch"):
+            raise ValueError("backend must be 'hip' or 'torch'")
+        if int(B) < 0 or int(Q) < 1:
+            raise ValueError("B must be >= 0 and episodes_per_env >= 1")
+        if not 1 <= int(R) <= MAX_ROWS:
+            raise ValueError(f"R must be 1..{MAX_ROWS}")
+        if not 1 <= int(window) <= TRACE_MAX_WINDOW:
+            raise ValueError(f"window must be 1..{TRACE_MAX_WINDOW}")
+        if int(capacity) < 1:
+            raise ValueError("capacity must be >= 1")
+        self.B, self.Q, self.R, self.device, self.backend = int(B), int(Q), int(R), torch.device(device), backend
+        self.W, self.C, self.keep, self.seen, self.env_offset = int(window), int(capacity), _keep_bits(keep), bool(seen), \
+            int(env_offset)
+        B, R, W, C = self.B, self.R, self.W, self.C
+        z = lambda *s, dt: torch.zeros(s, dtype=dt, device=self.device)
+        f32, f64, i32 = torch.float32, torch.float64, torch.int32
+        self.state_i32 = z(4, B, dt=i32)                 # steps, crashed so far, unsolved so far, ordinal
+        self.ring_scene, self.ring_seen = z(B, W + 1, R, 8, dt=f32), z(B, W, R, 8, dt=f32) if self.seen else None
+        self.ring_act, self.ring_reward, self.ring_i32 = z(B, W, 2, dt=f64), z(B, W, dt=f32), z(B, W, 3, dt=i32)
+        self.slot = z(B, dt=i32)
+        self.kept_scene, self.kept_seen = z(C, W + 1, R, 8, dt=f32), z(C, W, R, 8, dt=f32) if self.seen else None
+        self.kept_act, self.kept_reward, self.kept_i32 = z(C, W, 2, dt=f64), z(C, W, dt=f32), z(C, W, 3, dt=i32)
+        self.index, self.counts = z(C, 6, dt=i32), z(4, dt=torch.int64)
+
+    _PLANES = ("state_i32", "ring_scene", "ring_seen", "ring_act", "ring_reward", "ring_i32", "slot", "kept_scene", "kept_seen",
+               "kept_act", "kept_reward", "kept_i32", "index", "counts")
+    _STORE = ("kept_scene", "kept_seen", "kept_act", "kept_reward", "kept_i32", "index")
+
+    @staticmethod
+    def bytes_for(B: int, R: int, W: int, C: int, seen: bool = False) -> int:
+        """The layout formula: running state and work array 20 B, rings ((W + 1) + [W]) 32 R + 32 W per environment; store
+        ((W + 1) + [W]) 32 R + 32 W + 24 per slot; counts 32."""
+        planes = ((W + 1) + (W if seen else 0)) * 32 * R + 32 * W
+        return B * (20 + planes) + C * (planes + 24) + 32
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * t.element_size() for t in (getattr(self, n) for n in self._PLANES) if t is not None)
+
+    def _check(self, t, name, shape, dtype):
+        if t is None or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device:
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+
+    def update(self, terminal_obs, obs, seen, action, reward, done, truncated, crashed, arrived, status, iters, reset=False):
+        """After the reset of the environments (reset=True: only `obs` is read; the store is zeroed as well) and after every
+        step, before the buffer the agent acted on is overwritten.  seen: that buffer when the recorder was built with
+        seen=True, else None."""
+        B, R = self.B, self.R
+        self._check(obs, "obs", (B, R, 8), torch.float32)
+        flags = {}
+        if reset:
+            for n in self._STORE:
+                if getattr(self, n) is not None:
+                    getattr(self, n).zero_()
+            terminal_obs = seen = action = reward = status = iters = None
+            flags = dict(done=None, truncated=None, crashed=None, arrived=None)
+        else:
+            if (seen is not None) != self.seen:
+                raise ValueError("seen must be given exactly when the recorder was built with seen=True")
+            self._check(terminal_obs, "terminal_obs", (B, R, 8), torch.float32)
+            if self.seen:
+                self._check(seen, "seen", (B, R, 8), torch.float32)
+            self._check(action, "action", (B, 2), torch.float64)
+            self._check(reward, "reward", (B,), torch.float32)
+            self._check(status, "status", (B,), torch.int32)
+            self._check(iters, "iters", (B,), torch.int32)
+            for n, t in (("done", done), ("truncated", truncated), ("crashed", crashed), ("arrived", arrived)):
+                flags[n] = _u8(t)
+                self._check(flags[n], n, (B,), torch.uint8)
+        if self.backend == "torch":
+            self._numpy_update(terminal_obs, obs, seen, action, reward, flags, status, iters, reset)
+            return
+        _engine.caller("mpc_episode_trace")(
+            device=self.device.index, B=B, R=R, Q=self.Q, W=self.W, C=self.C, keep=self.keep, reset=1 if reset else 0,
+            terminal_obs=terminal_obs, obs=obs, seen=seen, action=action, reward=reward, **flags, status=status, iters=iters,
+            **{n: getattr(self, n) for n in self._PLANES}, stream=_engine.current_stream(self.device))
+
+    def _numpy_update(self, terminal_obs, obs, seen, action, reward, flags, status, iters, reset):
+        """csrc/mpc_episode_trace.hpp over the batch: the claim is a cumulative sum in environment order."""
+        B, Q, W, C = self.B, self.Q, self.W, self.C
+        host = {n: None if getattr(self, n) is None else getattr(self, n).cpu().numpy() for n in self._PLANES}
+        si, counts, slot = host["state_i32"], host["counts"], host["slot"]
+        n_ = lambda t: t.cpu().numpy()
+        if reset:
+            si[:], counts[:], slot[:] = 0, 0, -1
+            host["ring_scene"][:, 0] = n_(obs)
+        else:
+            done, truncated, crashed, arrived = (n_(flags[k]) != 0 for k in ("done", "truncated", "crashed", "arrived"))
+            status = n_(status)
+            t, j = si[0].copy(), si[3].copy()
+            live = j < Q
+            crash_ever = (si[1] != 0) | crashed
+            unsolved_ever = (si[2] != 0) | ~_solved(status)
+            outcome = (crash_ever * 1 + truncated * 2 + arrived * 4 + unsolved_ever * 8).astype(np.int32)
+            frame_flags = (done * 1 + truncated * 2 + crashed * 4 + arrived * 8).astype(np.int32)
+            sel = live & done & (np.bool_(self.keep & 16) | ((outcome & self.keep & 15) != 0))
+            place = int(counts[1]) + np.cumsum(sel) - 1
+            slot[:] = np.where(sel & (place < C), place, -1)
+            m = int(sel.sum())
+            k = min(m, max(C - int(counts[1]), 0))
+            counts += np.array([m, k, m - k, 1], np.int64)
+            e = np.nonzero(live)[0]                          # append
+            f = t[e] % W
+            host["ring_scene"][e, (t[e] + 1) % (W + 1)] = n_(terminal_obs)[e]
+            if self.seen:
+                host["ring_seen"][e, f] = n_(seen)[e]
+            host["ring_act"][e, f] = n_(action)[e]
+            host["ring_reward"][e, f] = n_(reward)[e]
+            host["ring_i32"][e, f] = np.stack([status, n_(iters), frame_flags], axis=1)[e]
+            for b in np.nonzero(slot >= 0)[0]:               # commit, chronologically
+                s, T = int(slot[b]), int(t[b]) + 1
+                L = min(T, W)
+                first = T - L
+                frames, scenes = (first + np.arange(L)) % W, (first + np.arange(L + 1)) % (W + 1)
+                host["kept_scene"][s, :L + 1] = host["ring_scene"][b, scenes]
+                for name in ("seen", "act", "reward", "i32"):
+                    if host["ring_" + name] is not None:
+                        host["kept_" + name][s, :L] = host["ring_" + name][b, frames]
+                host["index"][s] = [b, j[b], T, first, outcome[b], counts[3]]
+            ends = live & done
+            go = live & ~done
+            si[0] = np.where(ends, 0, np.where(go, t + 1, si[0]))
+            si[1] = np.where(ends, 0, np.where(go, crash_ever, si[1]))
+            si[2] = np.where(ends, 0, np.where(go, unsolved_ever, si[2]))
+            si[3] = j + ends
+            host["ring_scene"][ends, 0] = n_(obs)[ends]
+        for name, src in host.items():
+            if src is not None:
+                dst, src = getattr(self, name), torch.from_numpy(src)
+                if dst.data_ptr() != src.data_ptr():         # on the CPU the arrays above are the tensors' own memory
+                    dst.copy_(src)
+
+    def traces(self) -> EpisodeTraces:
+        counts = {k: int(v) for k, v in zip(TRACE_COUNTS, self.counts.cpu().numpy())}
+        n = counts["kept"]
+        cut = lambda t: None if t is None else t[:n].cpu().numpy().copy()
+        ix = cut(self.index)
+        index = {k: ix[:, i].copy() for i, k in enumerate(TRACE_INDEX)}
+        index["env"] = index["env"] + np.int32(self.env_offset)
+        return EpisodeTraces(index, counts, cut(self.kept_scene), cut(self.kept_seen), cut(self.kept_act),
+                             cut(self.kept_reward), cut(self.kept_i32), self.keep, self.nbytes)
+
+
 @dataclass
 class EvalResult:
     """records: dict of numpy arrays [B, Q] (steps, success, collision, truncated, avg_speed, return, unsolved, max_iters);
@@ -849,7 +1080,8 @@ class EvalResult:
     the perception model (`Perception.totals()`: rows present, seen, out_of_range, occluded, dropped over the whole
     evaluation, idle steps included) when the evaluation ran with one, else None; interaction: the interaction metrics'
     records (dict of numpy arrays [B, Q], keys INTERACT_I32 + INTERACT_F64, the same slots) when the evaluation ran with
-    interaction=True, else None."""
+    interaction=True, else None; traces: the episodes the trace recorder kept (`EpisodeTraces`) when the evaluation ran with
+    trace=, else None."""
     records: dict
     dt: float
     steps: int
@@ -858,6 +1090,7 @@ class EvalResult:
     drive: dict | None = None
     perception: dict | None = None
     interaction: dict | None = None
+    traces: EpisodeTraces | None = None
 
     @property
     def travel_time(self):
@@ -942,7 +1175,7 @@ def _engine_of(agent):
 @torch.no_grad()
 def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = False, reset_mpc_on_done: bool = False,
                    use_graph: bool | None = None, poll_every: int = 16, seed: int = 0, on_step=None,
-                   metrics: bool = False, perception=None, interaction: bool = False) -> EvalResult:
+                   metrics: bool = False, perception=None, interaction: bool = False, trace=None) -> EvalResult:
     """Run `agent` in closed loop on the B environments of `env` (a SyntheticIntersectionEnv) until each environment has
     finished `episodes_per_env` episodes; returns their records.
 
@@ -966,6 +1199,10 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     interaction=True: also the interaction metrics of every episode (`InteractionMetrics`, EvalResult.interaction), updated
     after the drive metrics inside the step (so inside the captured graph) from the environment's slots; ValueError unless the
     environment has traffic="idm".  on_step's dict is unchanged.
+    trace: an `EpisodeTrace` for this environment's batch and quota, or a dict of its keyword arguments (env_offset defaults to
+    the environment's, seen to whether a perception model is in use): the step-by-step record of the selected episodes
+    (EvalResult.traces), updated after the interaction metrics inside the step (so inside the captured graph) and before the
+    buffer the agent acted on is overwritten.  Everything else, on_step's dict included, is what it is without it.
     Every episode ends by EPISODE_STEPS (200) steps, so Q * 200 steps bound the loop; RuntimeError if the episodes are not
     all recorded by then."""
     Q = int(episodes_per_env)
@@ -998,6 +1235,15 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
         perception = Perception(B, dev, "hip" if hip else "torch", **pkw)
     if perception is not None and (perception.B != B or perception.R != VEHICLES_COUNT or perception.device != dev):
         raise ValueError(f"perception must be built for {B} environments of {VEHICLES_COUNT} rows on {dev}")
+    if isinstance(trace, dict):
+        tkw = dict(env_offset=int(getattr(env, "env_offset", 0)), seen=perception is not None)
+        tkw.update(trace)
+        trace = EpisodeTrace(B, Q, dev, "hip" if hip else "torch", VEHICLES_COUNT, **tkw)
+    if trace is not None:
+        if (trace.B, trace.Q, trace.R, trace.device) != (B, Q, VEHICLES_COUNT, dev):
+            raise ValueError(f"trace must be built for {B} environments, {Q} episodes each, {VEHICLES_COUNT} rows, on {dev}")
+        if trace.seen and perception is None:
+            raise ValueError("trace records seen=True only with a perception model")
     kw = dict(deterministic=bool(deterministic), seed=int(seed), env_offset=int(getattr(env, "env_offset", 0)))
 
     def step():
@@ -1015,6 +1261,9 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
             inputs.update(terminal_obs=info["terminal_obs"], obs=new_obs, act=out["act"])
         if inter is not None:
             inter.update(env, done)
+        if trace is not None:         # `obs` still holds what the agent acted on
+            trace.update(info["terminal_obs"], new_obs, obs if trace.seen else None, out["act"], reward, done,
+                         info["truncated"], info["crashed"], info["arrived"], out["status"], out["iters"])
         if perception is None:
             obs.copy_(new_obs)
         else:
@@ -1068,6 +1317,8 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
         drive.update(None, true0, None, None, reset=True)
     if inter is not None:
         inter.update(env, None, reset=True)
+    if trace is not None:
+        trace.update(None, true0, None, None, None, None, None, None, None, None, None, reset=True)
     if on_step is not None:
         first = dict(reset=True, ego=env.ego, obs=true0) if drive is not None else dict(reset=True, ego=env.ego)
         if perception is not None:
@@ -1098,19 +1349,33 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     return EvalResult(records=stats.records(), dt=float(env.dt), steps=n, env_steps=n * B, seconds=seconds,
                       drive=None if drive is None else drive.records(),
                       perception=None if perception is None else perception.totals(),
-                      interaction=None if inter is None else inter.records())
+                      interaction=None if inter is None else inter.records(),
+                      traces=None if trace is None else trace.traces())
 
 
 def compare(agents: dict, make_env, episodes_per_env: int = 1, metrics: bool = False, perception=None,
-            interaction: bool = False, **kw) -> dict:
+            interaction: bool = False, trace=None, results=None, **kw) -> dict:
     """Evaluate every agent on a fresh environment from make_env() (same seed: the HIP environment keys its draws by seed and
     environment id, so every agent meets the same initial episodes) -> {name: summary}; metrics=True adds the drive metrics'
     keys to every summary.  perception (a dict of `Perception`'s keyword arguments, or a Perception whose configuration is
     copied): every agent gets a fresh Perception with the same seed, hence the same draws on the same steps.
-    interaction=True adds the interaction metrics' keys (the environments must have traffic="idm")."""
+    interaction=True adds the interaction metrics' keys (the environments must have traffic="idm").  trace (a dict of
+    `EpisodeTrace`'s keyword arguments, or an EpisodeTrace whose settings are copied): every agent gets a fresh recorder with
+    the same settings.  results: a dict that receives every agent's EvalResult by name (its traces, its records)."""
     if isinstance(perception, Perception):
         perception = perception.config
+    if isinstance(trace, EpisodeTrace):
+        trace = dict(keep=[k for k, bit in TRACE_KEEP.items() if k != "failed" and trace.keep & bit], capacity=trace.C,
+                     window=trace.W, seen=trace.seen, env_offset=trace.env_offset)
     extra = dict(interaction=True) if interaction else {}
-    return {name: evaluate_agent(agent, make_env(), episodes_per_env, metrics=metrics,
-                                 perception=None if perception is None else dict(perception), **extra, **kw).summary()
-            for name, agent in agents.items()}
+    if trace is not None:
+        extra["trace"] = trace
+    out = {}
+    for name, agent in agents.items():
+        res = evaluate_agent(agent, make_env(), episodes_per_env, metrics=metrics,
+                             perception=None if perception is None else dict(perception),
+                             **{k: dict(v) if k == "trace" else v for k, v in extra.items()}, **kw)
+        if results is not None:
+            results[name] = res
+        out[name] = res.summary()
+    return out

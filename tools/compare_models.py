@@ -17,6 +17,12 @@ in the layout ActorCritic.save_sb3 writes; --ppo-random adds it with a seeded un
   python tools/compare_models.py --metrics --traffic idm --occlusion buildings --range 60 --sigma-pos 0.2
   python tools/compare_models.py --metrics --traffic idm --interaction --envs 256
   python tools/compare_models.py --envs 256 --fixture --ppo baseline.zip
+  python tools/compare_models.py --traffic idm --trace failed --trace-window 50 --trace-dir out
+
+--trace KEEP keeps the step-by-step record of the episodes that ended as KEEP says (evaluate.EpisodeTrace: the last
+--trace-window steps of at most --trace-capacity episodes per model) and writes one --trace-dir/<model>.npz per model;
+tools/show_episode.py prints an episode of such a file.  The JSON line then also names the file and the episodes matched,
+kept and dropped.
 """
 import argparse
 import json
@@ -52,6 +58,12 @@ def main():
     src = ap.add_mutually_exclusive_group()
     src.add_argument("--mpcrl", help="an SB3 checkpoint (.zip) of the reference's MPC-RL agent")
     src.add_argument("--fixture", action="store_true", help="MPC-RL: the v0 PPO policy of tests/golden/sb3_policies.npz")
+    ap.add_argument("--trace", metavar="KEEP", help="keep the step-by-step record of episodes (evaluate.EpisodeTrace): failed, all, "
+                                                     "or a comma-separated list of collision, truncated, success, unsolved")
+    ap.add_argument("--trace-window", type=int, default=200, metavar="W", help="--trace: the last W steps of each kept episode")
+    ap.add_argument("--trace-capacity", type=int, default=64, metavar="C", help="--trace: at most C episodes per model")
+    ap.add_argument("--trace-dir", default="traces", metavar="DIR", help="--trace: one DIR/<model>.npz per model "
+                                                                         "(tools/show_episode.py prints them)")
     base = ap.add_mutually_exclusive_group()
     base.add_argument("--ppo", metavar="PATH", help="the end-to-end PPO baseline: a checkpoint (.zip) as ActorCritic.save_sb3 writes it")
     base.add_argument("--ppo-random", action="store_true", help="the end-to-end PPO baseline with an untrained policy seeded by --seed")
@@ -100,11 +112,21 @@ def main():
                           occluders=evaluate.corner_buildings() if args.occlusion == "buildings" else None)
     finite = lambda v: None if isinstance(v, float) and not math.isfinite(v) else v
     echo = {} if perception is None else dict(perception={k: finite(v) for k, v in flags.items()})
+    trace = None
+    if args.trace:
+        keep = args.trace.split(",") if "," in args.trace else args.trace
+        trace = dict(keep=keep, window=args.trace_window, capacity=args.trace_capacity)
+        os.makedirs(args.trace_dir, exist_ok=True)
     for name, agent in agents.items():
+        results = {}
         s = evaluate.compare({name: agent}, make_env, args.episodes_per_env, deterministic=args.deterministic,
                              seed=args.seed, metrics=args.metrics, perception=perception,
-                             interaction=args.interaction)[name]
+                             interaction=args.interaction, trace=trace, results=results)[name]
         s = {k: finite(v) for k, v in s.items()}
+        if trace is not None:
+            path = os.path.join(args.trace_dir, f"{name}.npz")
+            results[name].traces.save(path)
+            s.update(trace_file=path, **{f"trace_{k}": v for k, v in results[name].traces.counts.items() if k != "launches"})
         print(json.dumps(dict(agent=name, traffic=args.traffic, envs=args.envs, episodes_per_env=args.episodes_per_env,
                               **echo, **s)), flush=True)
     if tmp is not None:
