@@ -77,11 +77,13 @@ TRACE_FLAGS = dict(done=1, truncated=2, crashed=4, arrived=8)
 TRACE_MAX_WINDOW = 4096
 
 
-def records_from_planes(rec_i32, rec_f64) -> dict:
-    """The record planes of the accounting (include/mpc_mi355x.h layout) -> dict of numpy arrays [B, Q]."""
+def records_from_planes(rec_i32, rec_f64, names_i32=REC_I32, names_f64=REC_F64, bools=_BOOL) -> dict:
+    """Record planes (include/mpc_mi355x.h layout) -> dict of numpy arrays [B, Q]: plane i of rec_i32 under names_i32[i] (as
+    bool for the names in `bools`), plane i of rec_f64 under names_f64[i].  The defaults are the accounting's records; the
+    drive metrics' are (DRIVE_I32, DRIVE_F64), the interaction metrics' (INTERACT_I32, INTERACT_F64)."""
     rec_i32, rec_f64 = np.asarray(rec_i32), np.asarray(rec_f64)
-    out = {k: (rec_i32[i] != 0) if k in _BOOL else rec_i32[i].copy() for i, k in enumerate(REC_I32)}
-    out.update({k: rec_f64[i].copy() for i, k in enumerate(REC_F64)})
+    out = {k: (rec_i32[i] != 0) if k in bools else rec_i32[i].copy() for i, k in enumerate(names_i32)}
+    out.update({k: rec_f64[i].copy() for i, k in enumerate(names_f64)})
     return out
 
 
@@ -93,23 +95,103 @@ def _u8(t):
     return t.view(torch.uint8) if t.dtype == torch.bool else t
 
 
-class EpisodeStats:
+def _check(t, name, shape, dtype, device):
+    """`t` as the kernels read it (a bool tensor's bytes where uint8 is wanted); ValueError unless it is a contiguous tensor
+    of that dtype and shape on that device.  Every `update` / `apply` checks what it is given with this before it
+    dispatches: on the "hip" backend the tensor's address goes to a kernel as it is."""
+    if t is not None and dtype == torch.uint8:
+        t = _u8(t)
+    if t is None or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != device:
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape} on {device}")
+    return t
+
+
+def _write_back(pairs):
+    """Every numpy result `src` of (dst, src) into its tensor `dst`, unless it already is that tensor's memory (on the CPU
+    `dst.cpu().numpy()` is)."""
+    for dst, src in pairs:
+        src = torch.from_numpy(np.ascontiguousarray(src))
+        if dst.data_ptr() != src.data_ptr():
+            dst.copy_(src)
+
+
+def _route(ref_xy):
+    """The ego's route ref_xy [M, 2], 1 <= M <= MAX_ROUTE -> (ref, e0, d), f64 on the CPU: the points, and of its max(M - 1,
+    1) segments the start and end - start (a single point is one segment of length 0)."""
+    if ref_xy is None:
+        raise ValueError("the ego's route ref_xy [M, 2] is needed")
+    ref = torch.as_tensor(ref_xy, dtype=torch.float64).cpu().contiguous()
+    if ref.ndim != 2 or ref.shape[1] != 2 or not 1 <= ref.shape[0] <= MAX_ROUTE:
+        raise ValueError(f"ref_xy must be [M, 2] with 1 <= M <= {MAX_ROUTE}")
+    M = ref.shape[0]
+    nseg = max(M - 1, 1)
+    return ref, ref[:nseg], ref[torch.clamp(torch.arange(nseg) + 1, max=M - 1)] - ref[:nseg]
+
+
+class _EpisodeAccounts:
+    """What the per-episode accounts share (the rule of csrc/mpc_episode_stats.hpp): the running state of every environment
+    (state_i32 [n_i32, B], state_f64 [n_f64, B]) and the records of its first Q episodes (rec_i32 [len(names_i32), B, Q],
+    rec_f64 [len(names_f64), B, Q]) as device tensors in the layout of include/mpc_mi355x.h.  An episode that ends with
+    ordinal j < Q is written to slot [b][j]; `done` clears the running counters and advances the ordinal up to the quota."""
+    _ORDINAL = 4                                         # the plane of state_i32 that `_torch_commit` keeps the ordinal in
+
+    def __init__(self, B: int, Q: int, device, backend: str, n_i32: int, n_f64: int, names_i32, names_f64):
+        if Q < 1:
+            raise ValueError("episodes_per_env must be >= 1")
+        if backend not in ("hip", "torch"):
+            raise ValueError("backend must be 'hip' or 'torch'")
+        self.B, self.Q, self.device, self.backend = int(B), int(Q), torch.device(device), backend
+        self._names = (names_i32, names_f64)
+        z = lambda *s, dt: torch.zeros(s, dtype=dt, device=self.device)
+        self.state_i32, self.state_f64 = z(n_i32, B, dt=torch.int32), z(n_f64, B, dt=torch.float64)
+        self.rec_i32, self.rec_f64 = z(len(names_i32), B, Q, dt=torch.int32), z(len(names_f64), B, Q, dt=torch.float64)
+
+    def _torch_commit(self, done, new_i32, new_f64):
+        """The record commit in torch ops: the rows new_i32 [len(names_i32), B] and new_f64 [len(names_f64), B] go to slot
+        [b][j] where `done` and j < Q, and the ordinal advances there.  Returns (write, keep): where a record was written,
+        and where the episode goes on (the caller clears its running counters elsewhere)."""
+        B, Q = self.B, self.Q
+        j = self.state_i32[self._ORDINAL]
+        done = done.bool()
+        write = done & (j < Q)
+        slot = torch.arange(B, device=self.device) * Q + torch.clamp(j, max=Q - 1).long()
+        for rec, new in ((self.rec_i32, new_i32), (self.rec_f64, new_f64)):
+            rec = rec.view(rec.shape[0], B * Q)
+            rec[:, slot] = torch.where(write, new, rec[:, slot])
+        self.state_i32[self._ORDINAL] = j + write.to(torch.int32)
+        return write, ~done
+
+    def records(self) -> dict:
+        return records_from_planes(self.rec_i32.cpu().numpy(), self.rec_f64.cpu().numpy(), *self._names)
+
+
+class EpisodeStats(_EpisodeAccounts):
     """Running state and records of the accounting, as device tensors in the layout of mpc_episode_stats
     (include/mpc_mi355x.h); `update` is the kernel (backend "hip") or the same update in torch ops (backend "torch")."""
 
     def __init__(self, B: int, Q: int, device, backend: str = "torch"):
-        if Q < 1:
-            raise ValueError("episodes_per_env must be >= 1")
-        self.B, self.Q, self.device, self.backend = int(B), int(Q), torch.device(device), backend
-        z = lambda *s, dt: torch.zeros(s, dtype=dt, device=self.device)
-        self.state_i32 = z(5, B, dt=torch.int32)        # steps, crashed, unsolved, max_iters, ordinal
-        self.state_f64 = z(3, B, dt=torch.float64)      # speed sum, return, carry_speed
-        self.rec_i32 = z(6, B, Q, dt=torch.int32)
-        self.rec_f64 = z(2, B, Q, dt=torch.float64)
-        self.recorded = z(1, dt=torch.int64)
+        # state_i32: steps, crashed, unsolved, max_iters, ordinal; state_f64: speed sum, return, carry_speed
+        super().__init__(B, Q, device, backend, 5, 3, REC_I32, REC_F64)
+        self.recorded = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def observe(self, frame, reset=False):
+        f = frame.get
+        self.update(frame["ego"], f("done"), f("truncated"), f("crashed"), f("arrived"), f("reward"), f("status"), f("iters"),
+                    reset=reset, step_counter=f("step"))
 
     def update(self, ego, done=None, truncated=None, crashed=None, arrived=None, reward=None, status=None, iters=None,
                reset=False, step_counter=None):
+        B, dev = self.B, self.device
+        _check(ego, "ego", (B, 4), torch.float64, dev)
+        if step_counter is not None:
+            _check(step_counter, "step_counter", (1,), torch.int64, dev)
+        if not reset:
+            done, truncated, crashed, arrived = [
+                _check(t, n, (B,), torch.uint8, dev)
+                for n, t in (("done", done), ("truncated", truncated), ("crashed", crashed), ("arrived", arrived))]
+            _check(reward, "reward", (B,), torch.float32, dev)
+            _check(status, "status", (B,), torch.int32, dev)
+            _check(iters, "iters", (B,), torch.int32, dev)
         if self.backend == "torch":
             self._torch_update(ego, done, truncated, crashed, arrived, reward, status, iters, reset)
             if step_counter is not None and not reset:
@@ -123,7 +205,7 @@ class EpisodeStats:
 
     @torch.no_grad()
     def _torch_update(self, ego, done, truncated, crashed, arrived, reward, status, iters, reset):
-        si, sf, B, Q = self.state_i32, self.state_f64, self.B, self.Q
+        si, sf = self.state_i32, self.state_f64
         if reset:
             si.zero_()
             sf[:2].zero_()
@@ -133,37 +215,18 @@ class EpisodeStats:
         steps = si[0] + 1
         crash = (si[1] != 0) | crashed.bool()
         unsolved = si[2] + (~_solved(status)).to(torch.int32)
-        max_iters = torch.maximum(si[3], iters.to(torch.int32))
+        max_iters = torch.maximum(si[3], iters)
         speed_sum = sf[0] + sf[2]
         ret = sf[1] + reward.to(torch.float64)
-        j = si[4]
-        done = done.bool()
-        write = done & (j < Q)
-        slot = torch.arange(B, device=self.device) * Q + torch.clamp(j, max=Q - 1).long()
         i32 = lambda t: t.to(torch.int32)
         new_i = torch.stack([steps, i32(arrived.bool()), i32(crash), i32(truncated.bool()), unsolved, max_iters])
-        new_f = torch.stack([speed_sum / steps, ret])
-        for rec, new in ((self.rec_i32.view(6, B * Q), new_i), (self.rec_f64.view(2, B * Q), new_f)):
-            rec[:, slot] = torch.where(write, new, rec[:, slot])
+        write, keep = self._torch_commit(done, new_i, torch.stack([speed_sum / steps, ret]))
         self.recorded += write.sum()
-        keep = ~done
         for i, t in enumerate((steps, i32(crash), unsolved, max_iters)):
             si[i] = torch.where(keep, t, torch.zeros_like(t))
-        si[4] = j + i32(write)
         sf[0] = torch.where(keep, speed_sum, torch.zeros_like(speed_sum))
         sf[1] = torch.where(keep, ret, torch.zeros_like(ret))
         sf[2] = ego[:, 3]
-
-    def records(self) -> dict:
-        return records_from_planes(self.rec_i32.cpu().numpy(), self.rec_f64.cpu().numpy())
-
-
-def drive_records_from_planes(rec_i32, rec_f64) -> dict:
-    """The record planes of the drive metrics (include/mpc_mi355x.h layout) -> dict of numpy arrays [B, Q]."""
-    rec_i32, rec_f64 = np.asarray(rec_i32), np.asarray(rec_f64)
-    out = {k: rec_i32[i].copy() for i, k in enumerate(DRIVE_I32)}
-    out.update({k: rec_f64[i].copy() for i, k in enumerate(DRIVE_F64)})
-    return out
 
 
 def _sqrt(x):
@@ -228,7 +291,7 @@ def _ttc(rx, ry, ux, uy):
     return torch.where(rr <= d2, torch.zeros_like(t), t)
 
 
-class DriveMetrics:
+class DriveMetrics(_EpisodeAccounts):
     """Running state and records of the safety and comfort metrics, as device tensors in the layout of mpc_drive_metrics
     (include/mpc_mi355x.h; formulas in csrc/mpc_drive_metrics.hpp); `update` is the kernel (backend "hip") or the same update
     in elementwise torch ops (backend "torch": every dot product written a*b + c*d, no reduction but min, so both agree bit
@@ -236,42 +299,27 @@ class DriveMetrics:
 
     def __init__(self, B: int, Q: int, device, backend: str = "torch", ref_xy=None, dt: float = 0.1,
                  rows: int = VEHICLES_COUNT):
-        if Q < 1:
-            raise ValueError("episodes_per_env must be >= 1")
         if not 1 <= int(rows) <= MAX_ROWS:
             raise ValueError(f"rows must be 1..{MAX_ROWS}")
         if not float(dt) > 0:
             raise ValueError("dt must be > 0")
-        if ref_xy is None:
-            raise ValueError("DriveMetrics needs the ego's route ref_xy [M, 2]")
-        self.B, self.Q, self.device, self.backend = int(B), int(Q), torch.device(device), backend
-        self.dt, self.rows = float(dt), int(rows)
-        self.ref_xy = torch.as_tensor(ref_xy, dtype=torch.float64).to(self.device).contiguous()
-        if self.ref_xy.ndim != 2 or self.ref_xy.shape[1] != 2 or not 1 <= self.ref_xy.shape[0] <= MAX_ROUTE:
-            raise ValueError(f"ref_xy must be [M, 2] with 1 <= M <= {MAX_ROUTE}")
-        self.M = int(self.ref_xy.shape[0])
-        z = lambda *s, dt: torch.zeros(s, dtype=dt, device=self.device)
-        self.state_i32 = z(5, B, dt=torch.int32)        # steps, ttc_steps, close_steps, hard_brake_steps, ordinal
-        self.state_f64 = z(17, B, dt=torch.float64)     # ten running values, then the carries vx vy cos sin ax ay steer
-        self.rec_i32 = z(4, B, Q, dt=torch.int32)
-        self.rec_f64 = z(10, B, Q, dt=torch.float64)
-        if backend != "hip":                             # the route's segments: start and end - start
-            nseg = max(self.M - 1, 1)
-            end = self.ref_xy[torch.clamp(torch.arange(nseg, device=self.device) + 1, max=self.M - 1)]
-            self._e0, self._d = self.ref_xy[:nseg], end - self.ref_xy[:nseg]
+        ref, e0, d = _route(ref_xy)
+        # state_i32: steps, ttc_steps, close_steps, hard_brake_steps, ordinal; state_f64: ten running values, then the
+        # carries vx vy cos sin ax ay steer
+        super().__init__(B, Q, device, backend, 5, 17, DRIVE_I32, DRIVE_F64)
+        self.dt, self.rows, self.M = float(dt), int(rows), int(ref.shape[0])
+        self.ref_xy, self._e0, self._d = ref.to(self.device), e0.to(self.device), d.to(self.device)
 
-    def _check(self, t, name, shape, dtype):
-        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape}")
+    def observe(self, frame, reset=False):
+        self.update(frame.get("terminal_obs"), frame["obs"], frame.get("act"), frame.get("done"), reset)
 
     def update(self, terminal_obs, obs, action, done, reset=False):
-        B, R = self.B, self.rows
-        self._check(obs, "obs", (B, R, 8), torch.float32)
+        B, R, dev = self.B, self.rows, self.device
+        _check(obs, "obs", (B, R, 8), torch.float32, dev)
         if not reset:
-            self._check(terminal_obs, "terminal_obs", (B, R, 8), torch.float32)
-            self._check(action, "action", (B, 2), torch.float64)
-            done = _u8(done)
-            self._check(done, "done", (B,), torch.uint8)
+            _check(terminal_obs, "terminal_obs", (B, R, 8), torch.float32, dev)
+            _check(action, "action", (B, 2), torch.float64, dev)
+            done = _check(done, "done", (B,), torch.uint8, dev)
         if self.backend == "torch":
             self._torch_update(terminal_obs, obs, action, done, reset)
             return
@@ -298,7 +346,7 @@ class DriveMetrics:
 
     @torch.no_grad()
     def _torch_update(self, terminal_obs, obs, action, done, reset):
-        si, sf, B, Q, dt = self.state_i32, self.state_f64, self.B, self.Q, self.dt
+        si, sf, dt = self.state_i32, self.state_f64, self.dt
         nxt = obs[:, 0].to(torch.float64)
         carry = lambda ax, ay, steer: [nxt[:, 3], nxt[:, 4], nxt[:, 7], nxt[:, 6], ax, ay, steer]
         if reset:
@@ -334,31 +382,13 @@ class DriveMetrics:
         new_i = torch.stack([steps, ttc_steps, close_steps, brake_steps])
         new_f = torch.stack(run_f[:5] + [torch.where(second, rms, torch.zeros_like(rms)), max_jerk, max_rate,
                                          xte_sum / steps.to(torch.float64), run_f[9]])
-        j = si[4]
-        done = done.bool()
-        write = done & (j < Q)
-        slot = torch.arange(B, device=self.device) * Q + torch.clamp(j, max=Q - 1).long()
-        for rec, new in ((self.rec_i32.view(4, B * Q), new_i), (self.rec_f64.view(10, B * Q), new_f)):
-            rec[:, slot] = torch.where(write, new, rec[:, slot])
-        keep = ~done
+        _, keep = self._torch_commit(done, new_i, new_f)
         for i in range(4):
             si[i] = torch.where(keep, new_i[i], torch.zeros_like(new_i[i]))
-        si[4] = j + i32(write)
         for i, v in enumerate(run_f):
             sf[i] = torch.where(keep, v, torch.full_like(v, float("inf") if i < 3 else 0.0))
         for i, v in enumerate(carry(ax, ay, steer)):
             sf[10 + i] = v
-
-    def records(self) -> dict:
-        return drive_records_from_planes(self.rec_i32.cpu().numpy(), self.rec_f64.cpu().numpy())
-
-
-def interaction_records_from_planes(rec_i32, rec_f64) -> dict:
-    """The record planes of the interaction metrics (include/mpc_mi355x.h layout) -> dict of numpy arrays [B, Q]."""
-    rec_i32, rec_f64 = np.asarray(rec_i32), np.asarray(rec_f64)
-    out = {k: rec_i32[i].copy() for i, k in enumerate(INTERACT_I32)}
-    out.update({k: rec_f64[i].copy() for i, k in enumerate(INTERACT_F64)})
-    return out
 
 
 def _wrap_pi(a):
@@ -487,7 +517,7 @@ def _drives_free(j, first, who):
     return closed & (lowest == j)
 
 
-class InteractionMetrics:
+class InteractionMetrics(_EpisodeAccounts):
     """Running state and records of the interaction metrics, as device tensors in the layout of mpc_interaction_metrics
     (include/mpc_mi355x.h; formulas in csrc/mpc_interaction.hpp); `update(env, done)` after the environment's step is the
     kernel (backend "hip") or the same update in numpy on the CPU (backend "torch": the feature works wherever the environment
@@ -495,61 +525,42 @@ class InteractionMetrics:
     SyntheticIntersectionEnv with traffic="idm".  ref_xy [M, 2]: the ego's route; dt: the step length; K: the other vehicles."""
 
     def __init__(self, B: int, Q: int, device, backend: str = "torch", ref_xy=None, dt: float = 0.1, K: int = 4):
-        if Q < 1:
-            raise ValueError("episodes_per_env must be >= 1")
-        if backend not in ("hip", "torch"):
-            raise ValueError("backend must be 'hip' or 'torch'")
         if not 1 <= int(K) <= SLOTS:
             raise ValueError(f"K must be 1..{SLOTS}")
         if not float(dt) > 0:
             raise ValueError("dt must be > 0")
-        if ref_xy is None:
-            raise ValueError("InteractionMetrics needs the ego's route ref_xy [M, 2]")
-        self.B, self.Q, self.K, self.device, self.backend = int(B), int(Q), int(K), torch.device(device), backend
-        self.dt = float(dt)
-        ref = torch.as_tensor(ref_xy, dtype=torch.float64).cpu().contiguous()
-        if ref.ndim != 2 or ref.shape[1] != 2 or not 1 <= ref.shape[0] <= MAX_ROUTE:
-            raise ValueError(f"ref_xy must be [M, 2] with 1 <= M <= {MAX_ROUTE}")
-        self.M = int(ref.shape[0])
-        self.ref_xy = ref.to(self.device)
-        self.conflict = torch.from_numpy(conflict_points(ref.numpy())).to(self.device)
-        z = lambda *s, dt: torch.zeros(s, dtype=dt, device=self.device)
-        self.state_i32 = z(INTERACT_STATE_I32, B, dt=torch.int32)
-        self.state_f64 = z(INTERACT_STATE_F64, B, dt=torch.float64)
-        self.rec_i32 = z(len(INTERACT_I32), B, Q, dt=torch.int32)
-        self.rec_f64 = z(len(INTERACT_F64), B, Q, dt=torch.float64)
+        ref, e0, d = _route(ref_xy)
+        super().__init__(B, Q, device, backend, INTERACT_STATE_I32, INTERACT_STATE_F64, INTERACT_I32, INTERACT_F64)
+        self.K, self.dt, self.M = int(K), float(dt), int(ref.shape[0])
+        # the route, its segments and the conflict table stay on the host for the numpy path
+        self._e0, self._d, self._conflict = e0.numpy(), d.numpy(), conflict_points(ref.numpy())
+        self.ref_xy, self.conflict = ref.to(self.device), torch.from_numpy(self._conflict).to(self.device)
+        B, K, f64 = self.B, self.K, torch.float64
+        self._slots = dict(ego=((B, 4), f64), opos=((B, K, 2), f64), ospeed=((B, K), f64), ohead=((B, K), f64),
+                           oactive=((B, K), torch.uint8), oroute=((B, K), torch.int32), oprog=((B, K), f64),
+                           otarget=((B, K), f64))            # what `update` reads of the environment
+
+    def observe(self, frame, reset=False):
+        self.update(frame["env"], frame.get("done"), reset)
 
     def update(self, env, done, reset=False):
-        B, K = self.B, self.K
         if getattr(env, "traffic", None) != "idm":
             raise ValueError("the interaction metrics need an environment with traffic='idm'")
-        shapes = dict(ego=((B, 4), torch.float64), opos=((B, K, 2), torch.float64), ospeed=((B, K), torch.float64),
-                      ohead=((B, K), torch.float64), oactive=((B, K), torch.bool), oroute=((B, K), torch.int32),
-                      oprog=((B, K), torch.float64), otarget=((B, K), torch.float64))
-        arrays = {}
-        for name, (shape, dtype) in shapes.items():
-            t = getattr(env, name)
-            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != self.device:
-                raise ValueError(f"env.{name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
-            arrays[name] = _u8(t)
+        arrays = {name: _check(getattr(env, name), "env." + name, shape, dtype, self.device)
+                  for name, (shape, dtype) in self._slots.items()}
         if not reset:
-            done = _u8(done)
-            if done.dtype != torch.uint8 or tuple(done.shape) != (B,) or not done.is_contiguous():
-                raise ValueError(f"done must be a contiguous bool / uint8 tensor of shape {(B,)}")
+            done = _check(done, "done", (self.B,), torch.uint8, self.device)
         if self.backend == "torch":
             self._numpy_update({k: v.cpu().numpy() for k, v in arrays.items()}, None if reset else done.cpu().numpy(), reset)
             return
         _engine.caller("mpc_interaction_metrics")(
-            device=self.device.index, B=B, K=K, Q=self.Q, M=self.M, reset=1 if reset else 0, dt=self.dt, **arrays,
+            device=self.device.index, B=self.B, K=self.K, Q=self.Q, M=self.M, reset=1 if reset else 0, dt=self.dt, **arrays,
             done=None if reset else done, ref_xy=self.ref_xy, conflict=self.conflict, state_i32=self.state_i32,
             state_f64=self.state_f64, rec_i32=self.rec_i32, rec_f64=self.rec_f64, stream=_engine.current_stream(self.device))
 
     def _sigma(self, x, y):
         """The ego's arc length along ref_xy [B] (csrc/mpc_interaction.hpp: sigma)."""
-        ref, M = self.ref_xy.cpu().numpy(), self.M
-        nseg = max(M - 1, 1)
-        e0 = ref[:nseg]
-        d = ref[np.minimum(np.arange(nseg) + 1, M - 1)] - e0
+        e0, d = self._e0, self._d
         sx, sy = x[:, None] - e0[None, :, 0], y[:, None] - e0[None, :, 1]
         dx, dy = d[None, :, 0], d[None, :, 1]
         dd = dx * dx + dy * dy
@@ -613,8 +624,7 @@ class InteractionMetrics:
             hard_mask |= (yields & (a_with < -HARD_BRAKE)).astype(np.int32) << j
             imposed_sum = imposed_sum + imposed
         # ---- (b) post-encroachment time
-        conflict = self.conflict.cpu().numpy()
-        sigma_c, s_c = conflict[:, 0], conflict[:, 1]
+        sigma_c, s_c = self._conflict[:, 0], self._conflict[:, 1]
         sigma, sigma_prev = self._sigma(x, y), sf[3]
         with np.errstate(divide="ignore", invalid="ignore"):
             te_old = np.where(fresh[None], -1.0, sf[4:4 + ROUTES])
@@ -656,13 +666,7 @@ class InteractionMetrics:
         sf[1] = run_f[1] + imposed_sum * dt
         sf[2] = np.where(min_pet < run_f[2], min_pet, run_f[2])
         sf[3] = sigma
-        for dst, src in ((self.state_i32, si), (self.state_f64, sf), (self.rec_i32, rec_i), (self.rec_f64, rec_f)):
-            src = torch.from_numpy(src)
-            if dst.data_ptr() != src.data_ptr():         # on the CPU the arrays above are the tensors' own memory
-                dst.copy_(src)
-
-    def records(self) -> dict:
-        return interaction_records_from_planes(self.rec_i32.cpu().numpy(), self.rec_f64.cpu().numpy())
+        _write_back(((self.state_i32, si), (self.state_f64, sf), (self.rec_i32, rec_i), (self.rec_f64, rec_f)))
 
 
 def corner_buildings(setback: float = 6.0, size: float = 30.0, road_half_width: float = 4.0) -> np.ndarray:
@@ -754,10 +758,8 @@ class Perception:
                     occluders=self.occluders.cpu().numpy().copy(), seed=self.seed, env_offset=self.env_offset)
 
     def apply(self, obs_true, out, reset: bool = False):
-        shape = (self.B, self.R, 8)
-        for name, t in (("obs_true", obs_true), ("out", out)):
-            if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device:
-                raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape} on {self.device}")
+        _check(obs_true, "obs_true", (self.B, self.R, 8), torch.float32, self.device)
+        _check(out, "out", (self.B, self.R, 8), torch.float32, self.device)
         if out.data_ptr() == obs_true.data_ptr() and self.B > 0:
             raise ValueError("out must not be obs_true")
         if self.backend == "torch":
@@ -842,8 +844,7 @@ class Perception:
             counts[f] += (cls != ROW_ABSENT).sum(axis=1) if f == 0 else (cls == c).sum(axis=1)
         ctr += 1
         row_class = np.concatenate([np.full((B, 1), ROW_SEEN, np.uint8), cls], axis=1)
-        for dst, src in ((self.counts, counts), (self.ctr, ctr), (self.row_class, row_class)):
-            dst.copy_(torch.from_numpy(np.ascontiguousarray(src)))
+        _write_back(((self.counts, counts), (self.ctr, ctr), (self.row_class, row_class)))
         return out
 
     def totals(self) -> dict:
@@ -967,16 +968,23 @@ class EpisodeTrace:
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in (getattr(self, n) for n in self._PLANES) if t is not None)
 
-    def _check(self, t, name, shape, dtype):
-        if t is None or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != self.device:
-            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+    @property
+    def config(self) -> dict:
+        """The keyword arguments that make an EpisodeTrace with the same settings."""
+        return dict(R=self.R, keep=[k for k, bit in TRACE_KEEP.items() if k != "failed" and self.keep & bit],
+                    capacity=self.C, window=self.W, seen=self.seen, env_offset=self.env_offset)
+
+    def observe(self, frame, reset=False):
+        f = frame.get
+        self.update(f("terminal_obs"), frame["obs"], f("seen") if self.seen else None, f("act"), f("reward"), f("done"),
+                    f("truncated"), f("crashed"), f("arrived"), f("status"), f("iters"), reset)
 
     def update(self, terminal_obs, obs, seen, action, reward, done, truncated, crashed, arrived, status, iters, reset=False):
         """After the reset of the environments (reset=True: only `obs` is read; the store is zeroed as well) and after every
         step, before the buffer the agent acted on is overwritten.  seen: that buffer when the recorder was built with
         seen=True, else None."""
-        B, R = self.B, self.R
-        self._check(obs, "obs", (B, R, 8), torch.float32)
+        B, R, dev = self.B, self.R, self.device
+        _check(obs, "obs", (B, R, 8), torch.float32, dev)
         flags = {}
         if reset:
             for n in self._STORE:
@@ -987,16 +995,15 @@ class EpisodeTrace:
         else:
             if (seen is not None) != self.seen:
                 raise ValueError("seen must be given exactly when the recorder was built with seen=True")
-            self._check(terminal_obs, "terminal_obs", (B, R, 8), torch.float32)
+            _check(terminal_obs, "terminal_obs", (B, R, 8), torch.float32, dev)
             if self.seen:
-                self._check(seen, "seen", (B, R, 8), torch.float32)
-            self._check(action, "action", (B, 2), torch.float64)
-            self._check(reward, "reward", (B,), torch.float32)
-            self._check(status, "status", (B,), torch.int32)
-            self._check(iters, "iters", (B,), torch.int32)
+                _check(seen, "seen", (B, R, 8), torch.float32, dev)
+            _check(action, "action", (B, 2), torch.float64, dev)
+            _check(reward, "reward", (B,), torch.float32, dev)
+            _check(status, "status", (B,), torch.int32, dev)
+            _check(iters, "iters", (B,), torch.int32, dev)
             for n, t in (("done", done), ("truncated", truncated), ("crashed", crashed), ("arrived", arrived)):
-                flags[n] = _u8(t)
-                self._check(flags[n], n, (B,), torch.uint8)
+                flags[n] = _check(t, n, (B,), torch.uint8, dev)
         if self.backend == "torch":
             self._numpy_update(terminal_obs, obs, seen, action, reward, flags, status, iters, reset)
             return
@@ -1054,11 +1061,7 @@ class EpisodeTrace:
             si[2] = np.where(ends, 0, np.where(go, unsolved_ever, si[2]))
             si[3] = j + ends
             host["ring_scene"][ends, 0] = n_(obs)[ends]
-        for name, src in host.items():
-            if src is not None:
-                dst, src = getattr(self, name), torch.from_numpy(src)
-                if dst.data_ptr() != src.data_ptr():         # on the CPU the arrays above are the tensors' own memory
-                    dst.copy_(src)
+        _write_back((getattr(self, name), src) for name, src in host.items() if src is not None)
 
     def traces(self) -> EpisodeTraces:
         counts = {k: int(v) for k, v in zip(TRACE_COUNTS, self.counts.cpu().numpy())}
@@ -1172,6 +1175,12 @@ def _engine_of(agent):
     return e if e is not None else getattr(agent, "engine", None)
 
 
+def _instance(cls, given, defaults: dict, *args):
+    """`given` itself (an instance of cls, or None), or for a dict of cls's keyword arguments cls(*args, **them) with
+    `defaults` for those it leaves out."""
+    return cls(*args, **{**defaults, **given}) if isinstance(given, dict) else given
+
+
 @torch.no_grad()
 def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = False, reset_mpc_on_done: bool = False,
                    use_graph: bool | None = None, poll_every: int = 16, seed: int = 0, on_step=None,
@@ -1223,28 +1232,38 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     if use_graph and on_step is not None:
         raise ValueError("on_step needs the eager path (use_graph=False)")
     warm = bool(getattr(agent, "warm_start", False))
-    stats = EpisodeStats(B, Q, dev, "hip" if hip else "torch")
+    backend, offset = "hip" if hip else "torch", int(getattr(env, "env_offset", 0))
     obs = torch.zeros((B, VEHICLES_COUNT, 8), dtype=torch.float32, device=dev)     # the observation the agent acts on
-    drive = DriveMetrics(B, Q, dev, "hip" if hip else "torch", env.ref_xy, env.dt, VEHICLES_COUNT) if metrics else None
     if interaction and getattr(env, "traffic", None) != "idm":
         raise ValueError("interaction=True needs an environment with traffic='idm'")
-    inter = InteractionMetrics(B, Q, dev, "hip" if hip else "torch", env.ref_xy, env.dt, env.K) if interaction else None
-    if isinstance(perception, dict):
-        pkw = dict(env_offset=int(getattr(env, "env_offset", 0)))
-        pkw.update(perception)
-        perception = Perception(B, dev, "hip" if hip else "torch", **pkw)
+    perception = _instance(Perception, perception, dict(env_offset=offset), B, dev, backend)
     if perception is not None and (perception.B != B or perception.R != VEHICLES_COUNT or perception.device != dev):
         raise ValueError(f"perception must be built for {B} environments of {VEHICLES_COUNT} rows on {dev}")
-    if isinstance(trace, dict):
-        tkw = dict(env_offset=int(getattr(env, "env_offset", 0)), seen=perception is not None)
-        tkw.update(trace)
-        trace = EpisodeTrace(B, Q, dev, "hip" if hip else "torch", VEHICLES_COUNT, **tkw)
+    trace = _instance(EpisodeTrace, trace, dict(R=VEHICLES_COUNT, env_offset=offset, seen=perception is not None),
+                      B, Q, dev, backend)
     if trace is not None:
         if (trace.B, trace.Q, trace.R, trace.device) != (B, Q, VEHICLES_COUNT, dev):
             raise ValueError(f"trace must be built for {B} environments, {Q} episodes each, {VEHICLES_COUNT} rows, on {dev}")
         if trace.seen and perception is None:
             raise ValueError("trace records seen=True only with a perception model")
-    kw = dict(deterministic=bool(deterministic), seed=int(seed), env_offset=int(getattr(env, "env_offset", 0)))
+    stats = EpisodeStats(B, Q, dev, backend)
+    drive = DriveMetrics(B, Q, dev, backend, env.ref_xy, env.dt, VEHICLES_COUNT) if metrics else None
+    inter = InteractionMetrics(B, Q, dev, backend, env.ref_xy, env.dt, env.K) if interaction else None
+    # The order of a step's launches, after the agent's and the environment's: the accounting, the drive metrics, the
+    # interaction metrics, the trace recorder - each `observe` of the step's frame - and then perception.apply (or the
+    # plain copy), which overwrites the buffer the agent acted on: the recorder has to have read it by then.
+    observers = [o for o in (stats, drive, inter, trace) if o is not None]
+    kw = dict(deterministic=bool(deterministic), seed=int(seed), env_offset=offset)
+    # what on_step is shown of a frame: the accounting's inputs; with metrics=True also the scenes and the action; with a
+    # perception model also the true observation, what the agent gets next and (below) the class of every row
+    shown = ("ego", "done", "truncated", "crashed", "arrived", "reward", "status", "iters") + \
+        (("terminal_obs", "obs", "act") if metrics else ()) + (("obs", "seen") if perception is not None else ())
+
+    def show(frame, **first):
+        first.update((k, frame[k]) for k in shown if k in frame)
+        if perception is not None:
+            first["row_class"] = perception.row_class
+        on_step(first)
 
     def step():
         out = agent.act_batch_torch(obs, **kw)
@@ -1253,23 +1272,18 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
             eng.reset_env_mask_torch(_u8(done))
         elif warm:                    # a new episode must not start from the old one's plan
             eng.reset_env_mask_torch(_u8(done), warm_only=True)
-        inputs = dict(ego=env.ego, done=done, truncated=info["truncated"], crashed=info["crashed"], arrived=info["arrived"],
-                      reward=reward, status=out["status"], iters=out["iters"])
-        stats.update(**inputs, step_counter=out.get("step"))
-        if drive is not None:
-            drive.update(info["terminal_obs"], new_obs, out["act"], done)
-            inputs.update(terminal_obs=info["terminal_obs"], obs=new_obs, act=out["act"])
-        if inter is not None:
-            inter.update(env, done)
-        if trace is not None:         # `obs` still holds what the agent acted on
-            trace.update(info["terminal_obs"], new_obs, obs if trace.seen else None, out["act"], reward, done,
-                         info["truncated"], info["crashed"], info["arrived"], out["status"], out["iters"])
+        frame = dict(env=env, ego=env.ego, terminal_obs=info["terminal_obs"], obs=new_obs, act=out["act"], reward=reward,
+                     done=done, truncated=info["truncated"], crashed=info["crashed"], arrived=info["arrived"],
+                     status=out["status"], iters=out["iters"], step=out.get("step"))
+        if perception is not None:
+            frame["seen"] = obs       # still what the agent acted on while the observers run; what it gets next after them
+        for o in observers:
+            o.observe(frame)
         if perception is None:
             obs.copy_(new_obs)
         else:
             perception.apply(new_obs, obs)
-            inputs.update(obs=new_obs, seen=obs, row_class=perception.row_class)
-        return out, inputs
+        return out, frame
 
     def first_obs(reset):
         true = env.reset()
@@ -1312,18 +1326,13 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
         eng.reset_env_state()
     if hasattr(agent, "restart_actions"):
         agent.restart_actions()
-    stats.update(env.ego, reset=True)
-    if drive is not None:
-        drive.update(None, true0, None, None, reset=True)
-    if inter is not None:
-        inter.update(env, None, reset=True)
-    if trace is not None:
-        trace.update(None, true0, None, None, None, None, None, None, None, None, None, reset=True)
+    frame = dict(env=env, ego=env.ego, obs=true0)
+    if perception is not None:
+        frame["seen"] = obs
+    for o in observers:
+        o.observe(frame, reset=True)
     if on_step is not None:
-        first = dict(reset=True, ego=env.ego, obs=true0) if drive is not None else dict(reset=True, ego=env.ego)
-        if perception is not None:
-            first.update(obs=true0, seen=obs, row_class=perception.row_class)
-        on_step(first)
+        show(frame, reset=True)
     target, max_steps = B * Q, Q * EPISODE_STEPS
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
@@ -1333,9 +1342,9 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
         if graph is not None:
             graph.replay()
         else:
-            _, inputs = step()
+            _, frame = step()
             if on_step is not None:
-                on_step(inputs)
+                show(frame)
         n += 1
         if n % int(poll_every) == 0 or n == max_steps:
             recorded = int(stats.recorded.item())          # one small copy to the host (synchronises)
@@ -1362,19 +1371,12 @@ def compare(agents: dict, make_env, episodes_per_env: int = 1, metrics: bool = F
     interaction=True adds the interaction metrics' keys (the environments must have traffic="idm").  trace (a dict of
     `EpisodeTrace`'s keyword arguments, or an EpisodeTrace whose settings are copied): every agent gets a fresh recorder with
     the same settings.  results: a dict that receives every agent's EvalResult by name (its traces, its records)."""
-    if isinstance(perception, Perception):
-        perception = perception.config
-    if isinstance(trace, EpisodeTrace):
-        trace = dict(keep=[k for k, bit in TRACE_KEEP.items() if k != "failed" and trace.keep & bit], capacity=trace.C,
-                     window=trace.W, seen=trace.seen, env_offset=trace.env_offset)
-    extra = dict(interaction=True) if interaction else {}
-    if trace is not None:
-        extra["trace"] = trace
+    perception, trace = (x.config if isinstance(x, (Perception, EpisodeTrace)) else x for x in (perception, trace))
+    fresh = lambda settings: None if settings is None else dict(settings)
     out = {}
     for name, agent in agents.items():
-        res = evaluate_agent(agent, make_env(), episodes_per_env, metrics=metrics,
-                             perception=None if perception is None else dict(perception),
-                             **{k: dict(v) if k == "trace" else v for k, v in extra.items()}, **kw)
+        res = evaluate_agent(agent, make_env(), episodes_per_env, metrics=metrics, perception=fresh(perception),
+                             interaction=interaction, trace=fresh(trace), **kw)
         if results is not None:
             results[name] = res
         out[name] = res.summary()

@@ -76,8 +76,8 @@ class HostDrive:
         assert rc == 0
 
     def records(self):
-        from mpc_rl_for_avs_amd.evaluate import drive_records_from_planes
-        return drive_records_from_planes(self.rec_i32, self.rec_f64)
+        from mpc_rl_for_avs_amd.evaluate import DRIVE_F64, DRIVE_I32, records_from_planes
+        return records_from_planes(self.rec_i32, self.rec_f64, DRIVE_I32, DRIVE_F64)
 
 
 # ---- the plain-Python restatement ---------------------------------------------------------------------------------------

@@ -97,8 +97,8 @@ class HostInteraction:
         return {n: getattr(self, n) for n in PLANES}
 
     def records(self):
-        from mpc_rl_for_avs_amd.evaluate import interaction_records_from_planes
-        return interaction_records_from_planes(self.rec_i32, self.rec_f64)
+        from mpc_rl_for_avs_amd.evaluate import INTERACT_F64, INTERACT_I32, records_from_planes
+        return records_from_planes(self.rec_i32, self.rec_f64, INTERACT_I32, INTERACT_F64)
 
 
 def run_host(states, B, Q, K, ref_xy, conflict):

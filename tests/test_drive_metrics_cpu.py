@@ -287,7 +287,7 @@ def test_evaluate_agent_without_metrics_is_what_it_was():
 def test_drive_metrics_refuses_invalid_arguments():
     ref = np.zeros((3, 2))
     for kw in (dict(Q=0), dict(rows=0), dict(rows=18), dict(dt=0.0), dict(ref_xy=None), dict(ref_xy=np.zeros((129, 2))),
-               dict(ref_xy=np.zeros((0, 2)))):
+               dict(ref_xy=np.zeros((0, 2))), dict(backend="foo")):
         args = dict(B=2, Q=1, device="cpu", backend="torch", ref_xy=ref, dt=DT, rows=10)
         args.update(kw)
         with pytest.raises(ValueError):
@@ -295,3 +295,34 @@ def test_drive_metrics_refuses_invalid_arguments():
     d = evaluate.DriveMetrics(2, 1, "cpu", "torch", ref, DT, 10)
     with pytest.raises(ValueError):
         d.update(None, torch.zeros(2, 9, 8), None, None, reset=True)
+
+
+def test_kernel_backed_drive_metrics_refuse_a_bad_tensor_before_any_library_call(monkeypatch):
+    """backend "hip" built on the CPU: the constructor loads no library, and every bad tensor is a ValueError before the
+    entry point is even looked up"""
+    from mpc_rl_for_avs_amd import engine
+
+    def caller(name):
+        raise AssertionError(f"{name} reached the library")
+
+    monkeypatch.setattr(engine, "caller", caller)
+    d = evaluate.DriveMetrics(2, 1, "cpu", "hip", np.zeros((3, 2)), DT, 10)
+    good = dict(terminal_obs=torch.zeros(2, 10, 8), obs=torch.zeros(2, 10, 8), action=torch.zeros(2, 2, dtype=torch.float64),
+                done=torch.zeros(2, dtype=torch.bool))
+    bad = dict(terminal_obs=[torch.zeros(2, 10, 8, device="meta"), torch.zeros(2, 10, 8, dtype=torch.float64),
+                             torch.zeros(2, 9, 8), torch.zeros(2, 10, 16)[:, :, ::2]],
+               obs=[torch.zeros(2, 10, 8, device="meta"), torch.zeros(2, 10, 8, dtype=torch.float16), torch.zeros(1, 10, 8),
+                    torch.zeros(2, 8, 10).transpose(1, 2)],
+               action=[torch.zeros(2, 2, dtype=torch.float64, device="meta"), torch.zeros(2, 2),
+                       torch.zeros(2, 3, dtype=torch.float64), torch.zeros(2, 4, dtype=torch.float64)[:, ::2]],
+               done=[torch.zeros(2, dtype=torch.bool, device="meta"), torch.zeros(2, dtype=torch.int32),
+                     torch.zeros(3, dtype=torch.bool), torch.zeros(4, dtype=torch.uint8)[::2]])
+    for name, tensors in bad.items():
+        for t in tensors:
+            with pytest.raises(ValueError, match=name):
+                d.update(**dict(good, **{name: t}))
+    for t in bad["obs"]:
+        with pytest.raises(ValueError, match="obs"):
+            d.update(None, t, None, None, reset=True)
+    with pytest.raises(AssertionError, match="mpc_drive_metrics reached the library"):
+        d.update(**good)                                     # the checks above were the only thing in the way

@@ -104,5 +104,6 @@ def test_eager_evaluation_is_reproduced_by_the_plain_python_restatement(traffic)
     take = lambda d: {k: (v.cpu().numpy().copy() if isinstance(v, torch.Tensor) else v) for k, v in d.items()}
     res, env = _eval(_pure(), B, traffic, use_graph=False, on_step=lambda d: seen.append(take(d)))
     want = dmh.replay(seen, B, 1, env.ref_xy.cpu().numpy(), env.dt, rollout.VEHICLES_COUNT)
-    _assert_drive_equal(res.drive, evaluate.drive_records_from_planes(want["rec_i32"], want["rec_f64"]))
+    _assert_drive_equal(res.drive, evaluate.records_from_planes(want["rec_i32"], want["rec_f64"], evaluate.DRIVE_I32,
+                                                                  evaluate.DRIVE_F64))
     assert np.array_equal(res.drive["steps"], res.records["steps"])

@@ -251,3 +251,91 @@ def test_invalid_arguments_raise_value_error():
         evaluate.evaluate_agent(agent, env, poll_every=0)
     with pytest.raises(ValueError):
         evaluate.evaluate_agent(agent, env, use_graph=True)          # the graph needs the HIP environment
+    with pytest.raises(ValueError):
+        evaluate.EpisodeStats(2, 1, "cpu", "foo")
+    with pytest.raises(ValueError):
+        evaluate.EpisodeStats(2, 0, "cpu", "torch")
+
+
+@pytest.mark.parametrize("backend", ["hip", "torch"])
+def test_accounting_refuses_a_bad_tensor_before_any_library_call(backend, monkeypatch):
+    """backend "hip" built on the CPU: the constructor loads no library, and every bad tensor is a ValueError before the
+    entry point is even looked up; the torch backend refuses the same tensors"""
+    from mpc_rl_for_avs_amd import engine
+
+    def caller(name):
+        raise AssertionError(f"{name} reached the library")
+
+    monkeypatch.setattr(engine, "caller", caller)
+    s = evaluate.EpisodeStats(2, 1, "cpu", backend)
+    z = lambda *shape, dt, **kw: torch.zeros(shape, dtype=dt, **kw)
+    flag = [z(2, dt=torch.bool, device="meta"), z(2, dt=torch.int32), z(3, dt=torch.bool), z(4, dt=torch.uint8)[::2]]
+    i32 = [z(2, dt=torch.int32, device="meta"), z(2, dt=torch.int64), z(1, dt=torch.int32), z(4, dt=torch.int32)[::2]]
+    bad = dict(ego=[z(2, 4, dt=torch.float64, device="meta"), z(2, 4, dt=torch.float32), z(2, 3, dt=torch.float64),
+                    z(2, 8, dt=torch.float64)[:, ::2]],
+               done=flag, truncated=flag, crashed=flag, arrived=flag, status=i32, iters=i32,
+               reward=[z(2, dt=torch.float32, device="meta"), z(2, dt=torch.float64), z(2, 1, dt=torch.float32),
+                       z(4, dt=torch.float32)[::2]],
+               # a tensor of one element is always contiguous
+               step_counter=[z(1, dt=torch.int64, device="meta"), z(1, dt=torch.int32), z(2, dt=torch.int64)])
+    good = dict(ego=z(2, 4, dt=torch.float64), reward=z(2, dt=torch.float32), status=z(2, dt=torch.int32),
+                iters=z(2, dt=torch.int32), step_counter=z(1, dt=torch.int64),
+                **{k: z(2, dt=torch.bool) for k in ("done", "truncated", "crashed", "arrived")})
+    for name, tensors in bad.items():
+        for t in tensors:
+            with pytest.raises(ValueError, match=name):
+                s.update(**dict(good, **{name: t}))
+    for name in ("ego", "step_counter"):                      # what a reset launch reads
+        for t in bad[name]:
+            with pytest.raises(ValueError, match=name):
+                s.update(**{"ego": good["ego"], name: t}, reset=True)
+    if backend == "hip":
+        with pytest.raises(AssertionError, match="mpc_episode_stats reached the library"):
+            s.update(**good)                                 # the checks above were the only thing in the way
+    else:
+        s.update(**good)
+        assert int(good["step_counter"][0]) == 1 and int(s.state_i32[0, 0]) == 1
+
+
+ALL_FEATURES = dict(metrics=True, interaction=True, trace=dict(keep="all", capacity=4, window=8))
+ALL_B, ALL_Q = 6, 2                                  # B no multiple of a wave's four environments; Q: environments idle
+
+
+def all_features_perception():
+    return dict(range=30.0, occlusion=True, occluders=evaluate.corner_buildings(), seed=7)
+
+
+def assert_features_do_not_disturb_one_another(run):
+    """run(**features) -> EvalResult of one evaluation with the perception model and those features: each of the four
+    results of the evaluation with every feature equals, bit for bit, that of the evaluation with this feature alone."""
+    from episode_trace_host import same_bits
+    full = run(**ALL_FEATURES)
+    tr = full.traces
+    # every episode inside the quota ends and keep="all" selects it: 12 match, the store holds 4
+    assert tr.counts == dict(matched=ALL_B * ALL_Q, kept=4, dropped=ALL_B * ALL_Q - 4, launches=full.steps)
+    planes = lambda t: dict(t.index, scene=t.scene, seen=t.seen, action=t.action, reward=t.reward, frame_i32=t.frame_i32)
+    singles = dict(records=({}, lambda r: r.records), drive=(dict(metrics=True), lambda r: r.drive),
+                   interaction=(dict(interaction=True), lambda r: r.interaction),
+                   traces=(dict(trace=ALL_FEATURES["trace"]), lambda r: planes(r.traces)))
+    for name, (features, pick) in singles.items():
+        alone = run(**features)
+        assert alone.steps == full.steps, name
+        got, want = pick(full), pick(alone)
+        assert list(got) == list(want), name
+        for k in want:
+            assert same_bits(got[k], want[k]), (name, k)
+        if name == "traces":
+            assert alone.traces.counts == tr.counts and alone.traces.keep == tr.keep and tr.seen is not None
+    return full
+
+
+def test_all_features_in_one_evaluation_are_the_single_feature_evaluations():
+    agent = PureMPC_Agent(Env(), dict(CFG), engine=StubEngine())
+
+    def run(**features):
+        env = rollout.SyntheticIntersectionEnv(ALL_B, device="cpu", seed=1, n_others=4, traffic="idm")
+        features = {k: dict(v) if isinstance(v, dict) else v for k, v in features.items()}
+        return evaluate.evaluate_agent(agent, env, episodes_per_env=ALL_Q, use_graph=False,
+                                       perception=all_features_perception(), **features)
+
+    assert_features_do_not_disturb_one_another(run)

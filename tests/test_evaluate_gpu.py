@@ -9,6 +9,7 @@ import pytest
 
 import episode_stats_host as esh
 import sde_host
+import test_evaluate_cpu as tec
 from test_evaluate_cpu import CFG, Env, _assert_records_equal, _expected_recorded, random_stream
 
 pytestmark = pytest.mark.gpu
@@ -100,6 +101,28 @@ def test_graph_and_eager_evaluations_record_the_same_episodes():
     e = _eval(agent, 256, 2, use_graph=False)
     _assert_records_equal(g.records, e.records)
     assert g.steps == e.steps
+
+
+def test_all_features_in_one_evaluation_graph_eager_and_single_feature_runs_agree():
+    from mpc_rl_for_avs_amd import evaluate, rollout
+    from episode_trace_host import same_bits
+    agent = _pure(collision_cost=False)
+
+    def run(use_graph=True, **features):
+        env = rollout.SyntheticIntersectionEnv(tec.ALL_B, device=_dev(), seed=1, n_others=4, traffic="idm")
+        features = {k: dict(v) if isinstance(v, dict) else v for k, v in features.items()}
+        return evaluate.evaluate_agent(agent, env, episodes_per_env=tec.ALL_Q, seed=1, use_graph=use_graph,
+                                       perception=tec.all_features_perception(), **features)
+
+    g = tec.assert_features_do_not_disturb_one_another(run)          # the graph run against four single-feature graph runs
+    e = run(use_graph=False, **tec.ALL_FEATURES)
+    assert g.steps == e.steps <= 400 and g.traces.counts == e.traces.counts and g.perception == e.perception
+    planes = lambda t: dict(t.index, scene=t.scene, seen=t.seen, action=t.action, reward=t.reward, frame_i32=t.frame_i32)
+    for name, a, b in (("records", g.records, e.records), ("drive", g.drive, e.drive),
+                       ("interaction", g.interaction, e.interaction), ("traces", planes(g.traces), planes(e.traces))):
+        assert list(a) == list(b), name
+        for k in a:
+            assert same_bits(a[k], b[k]), (name, k)
 
 
 def _shards(make_agent, Q=1, **kw):
