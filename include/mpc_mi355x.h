@@ -581,6 +581,35 @@ int mpc_perceive(int32_t device, int32_t B, int32_t R, int32_t S, int32_t reset,
                  int64_t *ctr, void *stream);
 
 /*
+ * mpc_track_rows (an addition within ABI 8: old clients never call it, nothing else changes) - a tracker between the
+ * perception model (or the true observation) and the agent of a closed-loop evaluation: a vehicle that vanishes from the
+ * observation for up to `coast` launches stays in obs_out, moved on with its last velocity; measurements are smoothed by the
+ * gains alpha_pos and alpha_vel; every output row gets an identity, the track slot behind it (every formula, in evaluation
+ * order, in csrc/mpc_tracker.hpp).  Device pointers, enqueue only on `stream`, never synchronises (capturable in a hipGraph);
+ * sixteen lanes per environment, a lane both a row and a slot, no LDS, no atomics, no scratch.  One launch per policy step,
+ * after mpc_perceive where there is one, and one with reset != 0 after the environments' reset.
+ *
+ * obs_meas, obs_out [B][R][8] f32 (presence, x, y, vx, vy, heading, sin_h, cos_h; row 0 the ego, copied; finite); done [B] u8
+ * or NULL: the environments whose episode ended on this step.  State, 16 slots per environment whatever R is: track_f64
+ * [B][16][7] = x, y, vx, vy, heading, sin_h, cos_h; track_i32 [B][16][3] = alive, age, miss.  A launch: reset != 0 or done[b]
+ * clears the slots of b; every alive slot is predicted by dt; the present rows, in row order, each claim the nearest alive
+ * unclaimed slot within `gate` metres (squared distances against gate * gate, a tie to the lowest slot) and update it; an
+ * unclaimed slot coasts (miss += 1) and expires when miss > coast; an unassociated row is born into the next free slot, or,
+ * when none is free, evicts the lowest coasting one.  obs_out: the alive slots ordered by their squared distance to the ego
+ * (ties to the lowest slot), the first R - 1 of them as rows 1, 2, ... with presence 1.0f, the rest +0.0f.  row_slot [B][R]
+ * u8 or NULL: the slot behind each output row, 255 for row 0 and for empty rows; row_miss [B][R] u8 or NULL: that slot's miss
+ * (0: measured in this launch).  counts [7][B] i64 += measured, matched, born, coasted, expired, evicted, cut; reset != 0
+ * zeroes them first.  With coast 0 and both gains 1 obs_out is the present rows of obs_meas bit for bit, in that order.
+ * Errors (MPC_ERR_INVALID_ARG): B < 0, R outside 1 .. MPC_MAX_OTHERS + 1, dt NaN or <= 0, gate NaN or < 0 (+inf is allowed),
+ * coast outside 0 .. 200, alpha_pos or alpha_vel outside (0, 1], a NULL obs_meas / obs_out / track_f64 / track_i32 / counts,
+ * obs_out == obs_meas.  B == 0 is a no-op.
+ */
+int mpc_track_rows(int32_t device, int32_t B, int32_t R, int32_t reset, double dt, double gate, int32_t coast,
+                   double alpha_pos, double alpha_vel, const float *obs_meas, const uint8_t *done, float *obs_out,
+                   uint8_t *row_slot, uint8_t *row_miss, double *track_f64, int32_t *track_i32, int64_t *counts,
+                   void *stream);
+
+/*
  * Diagnostics: the NLP's functions at GIVEN points, evaluated by the solve kernel's own code (csrc/mpc_wave.hpp:
  * Solver::evaluate - stage_terms / track / dist, which judge every line-search trial, and the model step of the rollouts),
  * so that f(z) and g(z) computed by the reference's statements (agents/pure_mpc.py:128-283; tests/golden/

@@ -31,6 +31,7 @@
 #include "mpc_rollout_glue.hpp"
 #include "mpc_drive_metrics.hpp"
 #include "mpc_perception.hpp"
+#include "mpc_tracker.hpp"
 #include "mpc_interaction.hpp"
 #include "mpc_episode_stats.hpp"
 #include "mpc_episode_trace.hpp"
@@ -1064,6 +1065,127 @@ __global__ __launch_bounds__(64) void mpc_perceive_kernel(mpc::sense::Params P, 
 #pragma unroll
         for (int f = 0; f < sense::kCounts; ++f) buf.counts[f * B + b] = (reset ? 0 : buf.counts[f * B + b]) + n[f];
         buf.ctr[b] = c + 1;
+    }
+}
+
+// tracker of a closed-loop evaluation (mpc_tracker.hpp): the mapping of mpc_perceive_kernel, sixteen lanes per environment,
+// four environments per wave.  Lane l of a group is BOTH measurement row l + 1 (R <= 17) and track slot l.  The association
+// is a loop over the rows (R is wave-uniform): the row's position is broadcast inside the group, every lane forms the
+// distance of its slot, and the group takes the lexicographic minimum of (d, slot) by four xor-shuffles - that order is
+// total, so the tree gives the serial loop's answer, ties to the lowest slot - and the winning lane marks itself claimed.  A
+// slot then fetches the row it was updated or born from with one lane-indexed shuffle per column.  Birth slots come from
+// popcounts of the group's slices of the ballots (free slots, then coasting ones, against the unassociated rows), the output
+// rank of a slot from a count of smaller (key, slot) over sixteen broadcasts: no LDS, no atomics, no serial scan.  Every
+// shuffle and ballot sits in wave-uniform control flow: a lane without a row counts as absent, a group past the end reads
+// the last environment; only stores are predicated.  Each slot's state is read and written by its own lane alone; the
+// counts by lane 0.
+__global__ __launch_bounds__(64) void mpc_track_kernel(mpc::track::Params P, mpc::track::Buffers buf, int reset) {
+    namespace track = mpc::track;
+    const int l = threadIdx.x & 15, g = threadIdx.x >> 4;
+    const int b_ = blockIdx.x * 4 + g;
+    const bool live = b_ < buf.B;
+    const int b = live ? b_ : buf.B - 1;
+    const int R = buf.R, i = l + 1;
+    const bool has = i < R;
+    const int shift = g * 16;
+    const unsigned below = (1u << l) - 1u;
+    const float *in = buf.meas + (size_t)b * R * track::kCols;
+    float row[track::kCols];
+#pragma unroll
+    for (int c = 0; c < track::kCols; ++c) row[c] = in[(has ? i : 0) * track::kCols + c];
+    const float ex = in[1], ey = in[2];
+    const bool present = has && row[0] != 0.0f;              // no row: absent
+    const bool clear = reset != 0 || (buf.done != nullptr && buf.done[b] != 0);
+    track::Slot t = clear ? track::empty_slot() : track::load_slot(buf, b, l);          // 1
+    track::predict(P, t);                                                                // 2
+    bool claimed = false, associated = false;
+    int source = l;                                          // the lane whose row this slot is updated or born from
+    for (int j = 0; j < R - 1; ++j) {                        // 3
+        const float mx = __shfl(row[1], j, 16), my = __shfl(row[2], j, 16);
+        const int there = __shfl((int)present, j, 16);
+        const double d = track::dist2(t, mx, my);
+        const bool eligible = there != 0 && t.alive != 0 && !claimed && d <= P.gate2;
+        double best_d = eligible ? d : __builtin_huge_val();                             // d is finite: inputs are
+        int best = eligible ? l : track::kSlots;
+#pragma unroll
+        for (int m = 1; m < 16; m <<= 1) {
+            const double od = __shfl_xor(best_d, m, 16);
+            const int os = __shfl_xor(best, m, 16);
+            const bool take = track::before(od, os, best_d, best);
+            best_d = take ? od : best_d;
+            best = take ? os : best;
+        }
+        if (best == l) claimed = true, source = j;
+        if (j == l) associated = best < track::kSlots;
+    }
+    const bool was_alive = t.alive != 0;
+    bool expired = false;
+    if (was_alive && !claimed) expired = track::coast(P, t);                             // 5 (4 follows with 6)
+    const unsigned measured_mask = (unsigned)(__ballot(present) >> shift) & 0xFFFFu;
+    const unsigned claimed_mask = (unsigned)(__ballot(claimed) >> shift) & 0xFFFFu;
+    const unsigned expired_mask = (unsigned)(__ballot(expired) >> shift) & 0xFFFFu;
+    const unsigned unassoc_mask = (unsigned)(__ballot(present && !associated) >> shift) & 0xFFFFu;
+    const unsigned free_mask = (unsigned)(__ballot(t.alive == 0) >> shift) & 0xFFFFu;
+    const unsigned coasting_mask = (unsigned)(__ballot(t.alive != 0 && !claimed) >> shift) & 0xFFFFu;
+    const int n_unassoc = (int)__popc(unassoc_mask);
+    const int candidate = t.alive == 0 ? (int)__popc(free_mask & below)                  // 6: this slot's place in the queue
+                          : !claimed   ? (int)__popc(free_mask) + (int)__popc(coasting_mask & below)
+                                       : track::kSlots;
+    const bool birth = candidate < n_unassoc;
+    const bool evicted = birth && t.alive != 0;
+    if (birth) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r)                         // the candidate-th unassociated row
+            if ((unassoc_mask >> r & 1u) != 0 && (int)__popc(unassoc_mask & ((1u << r) - 1u)) == candidate) source = r;
+    }
+    float m[track::kCols];
+#pragma unroll
+    for (int c = 1; c < track::kCols; ++c) m[c] = __shfl(row[c], source, 16);
+    if (claimed) track::update(P, t, m[1], m[2], m[3], m[4], m[5], m[6], m[7]);          // 4
+    if (birth) t = track::born(m[1], m[2], m[3], m[4], m[5], m[6], m[7]);
+    const unsigned evicted_mask = (unsigned)(__ballot(evicted) >> shift) & 0xFFFFu;
+    const unsigned alive_mask = (unsigned)(__ballot(t.alive != 0) >> shift) & 0xFFFFu;
+    const double key = track::order_key(t, ex, ey);                                      // 7
+    int rank = 0;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        const double other = __shfl(key, s, 16);
+        rank += ((alive_mask >> s & 1u) != 0 && track::before(other, s, key, l)) ? 1 : 0;
+    }
+    const bool shown = t.alive != 0 && rank < R - 1;
+    const unsigned coasted_mask = (unsigned)(__ballot(shown && t.miss > 0) >> shift) & 0xFFFFu;
+    const int n_alive = (int)__popc(alive_mask);
+    const int n_shown = n_alive < R - 1 ? n_alive : R - 1;
+    if (!live) return;                                        // nothing but stores below
+    float *out = buf.out + (size_t)b * R * track::kCols;
+    uint8_t *row_slot = buf.row_slot ? buf.row_slot + (size_t)b * R : nullptr;
+    uint8_t *row_miss = buf.row_miss ? buf.row_miss + (size_t)b * R : nullptr;
+    if (shown) {
+        float o[track::kCols];
+        track::write_row(o, t);
+#pragma unroll
+        for (int c = 0; c < track::kCols; ++c) out[(1 + rank) * track::kCols + c] = o[c];
+        if (row_slot) row_slot[1 + rank] = (uint8_t)l;
+        if (row_miss) row_miss[1 + rank] = (uint8_t)t.miss;
+    }
+    if (has && l >= n_shown) {
+#pragma unroll
+        for (int c = 0; c < track::kCols; ++c) out[i * track::kCols + c] = 0.0f;
+        if (row_slot) row_slot[i] = (uint8_t)track::kNoSlot;
+        if (row_miss) row_miss[i] = 0;
+    }
+    track::store_slot(buf, b, l, t);
+    if (l == 0) {
+#pragma unroll
+        for (int c = 0; c < track::kCols; ++c) out[c] = in[c];
+        if (row_slot) row_slot[0] = (uint8_t)track::kNoSlot;
+        if (row_miss) row_miss[0] = 0;
+        const size_t B = (size_t)buf.B;
+        const int n[track::kCounts] = {(int)__popc(measured_mask), (int)__popc(claimed_mask), n_unassoc,
+                                       (int)__popc(coasted_mask), (int)__popc(expired_mask), (int)__popc(evicted_mask),
+                                       n_alive - n_shown};
+#pragma unroll
+        for (int f = 0; f < track::kCounts; ++f) buf.counts[f * B + b] = (reset ? 0 : buf.counts[f * B + b]) + n[f];
     }
 }
 
@@ -2163,6 +2285,31 @@ int mpc_perceive(int32_t device, int32_t B, int32_t R, int32_t S, int32_t reset,
     const mpc::sense::Buffers buf{(int)B, (int)R, (int)S, obs_true, occluders, obs_seen, row_class, counts, ctr};
     hipLaunchKernelGGL(mpc_perceive_kernel, dim3((unsigned)((B + 3) / 4)), dim3(64), 0,
                        reinterpret_cast<hipStream_t>(stream_), P, buf, (int)reset);
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_track_rows(int32_t device, int32_t B, int32_t R, int32_t reset, double dt, double gate, int32_t coast,
+                   double alpha_pos, double alpha_vel, const float *obs_meas, const uint8_t *done, float *obs_out,
+                   uint8_t *row_slot, uint8_t *row_miss, double *track_f64, int32_t *track_i32, int64_t *counts,
+                   void *stream_) {
+    if (B < 0 || R < 1 || R > mpc::track::kMaxRows)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_track_rows: bad size (B >= 0, 1 <= R <= 17)");
+    if (!(dt > 0.0) || !(gate >= 0.0))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_track_rows: bad parameter (dt > 0, gate >= 0; neither NaN)");
+    if (coast < 0 || coast > mpc::track::kMaxCoast)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_track_rows: bad parameter (0 <= coast <= 200)");
+    if (!(alpha_pos > 0.0 && alpha_pos <= 1.0) || !(alpha_vel > 0.0 && alpha_vel <= 1.0))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_track_rows: bad parameter (0 < alpha_pos <= 1, 0 < alpha_vel <= 1; neither NaN)");
+    if (!obs_meas || !obs_out || !track_f64 || !track_i32 || !counts)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_track_rows: null obs_meas / obs_out / track_f64 / track_i32 / counts pointer");
+    if (obs_out == obs_meas) return fail(MPC_ERR_INVALID_ARG, "mpc_track_rows: obs_out must not be obs_meas");
+    if (B == 0) return MPC_OK;
+    HIP_TRY(hipSetDevice(device));
+    const mpc::track::Params P{dt, gate * gate, alpha_pos, alpha_vel, coast};
+    const mpc::track::Buffers buf{(int)B, (int)R, obs_meas, done, obs_out, row_slot, row_miss, track_f64, track_i32, counts};
+    hipLaunchKernelGGL(mpc_track_kernel, dim3((unsigned)((B + 3) / 4)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream_),
+                       P, buf, (int)reset);
     HIP_TRY(hipGetLastError());
     return MPC_OK;
 }

@@ -1,7 +1,7 @@
 """ctypes binding of the C ABI (include/mpc_mi355x.h) - the only way Python reaches the HIP kernels: the entry points that
 take an engine handle through `MPCEngine`'s methods, the handle-less ones (environment step, policy step, rollout glue,
-evaluation accounting, perception, episode traces) through `call` / `caller`, by parameter name, in the order of `SIGNATURES`
-and `EVALUATION_SIGNATURES`.
+evaluation accounting, perception, episode traces, tracker) through `call` / `caller`, by parameter name, in the order of
+`SIGNATURES`, `EVALUATION_SIGNATURES` and `TRACKER_SIGNATURES`.
 
 There is no CPU fallback: if the shared library is missing, or no MI355X is visible, construction fails
 loudly (`EngineError`).  Host numpy arrays are copied by the library; torch device tensors are passed
@@ -109,13 +109,17 @@ EVALUATION_SIGNATURES = {name: tuple(tuple(word.split(":")) for word in text.spl
                       "state_i32:ptr ring_scene:ptr ring_seen:ptr ring_act:ptr ring_reward:ptr ring_i32:ptr slot:ptr "
                       "kept_scene:ptr kept_seen:ptr kept_act:ptr kept_reward:ptr kept_i32:ptr index:ptr counts:ptr "
                       "stream:ptr").items()}
-
+# The tracker of the evaluation (csrc/mpc_tracker.hpp), likewise; tests/test_tracker_cpu.py holds this one against the header.
+TRACKER_SIGNATURES = {name: tuple(tuple(word.split(":")) for word in text.split()) for name, text in dict(
+    mpc_track_rows="device:i32 B:i32 R:i32 reset:i32 dt:f64 gate:f64 coast:i32 alpha_pos:f64 alpha_vel:f64 obs_meas:ptr "
+                   "done:ptr obs_out:ptr row_slot:ptr row_miss:ptr track_f64:ptr track_i32:ptr counts:ptr stream:ptr").items()}
+_TABLES = (SIGNATURES, EVALUATION_SIGNATURES, TRACKER_SIGNATURES)
 
 _EXPORTS = ["mpc_version", "mpc_last_error", "mpc_default_config", "mpc_default_config_sized", "mpc_create", "mpc_destroy",
             "mpc_set_reference", "mpc_solve_batch", "mpc_workspace_bytes", "mpc_predict_batch",
             "mpc_reset_env_state", "mpc_reset_env_mask", "mpc_get_env_state", "mpc_get_last_inputs",
             "mpc_ltv_solve_batch", "mpc_ltv_predict_batch", "mpc_env_state_bytes", "mpc_save_env_state",
-            "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_policy_control", "mpc_policy_control_tile", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_interaction_metrics", "mpc_episode_trace", "mpc_perceive", "mpc_eval_nlp", "mpc_streams_overlap"]
+            "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_policy_control", "mpc_policy_control_tile", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_interaction_metrics", "mpc_episode_trace", "mpc_perceive", "mpc_track_rows", "mpc_eval_nlp", "mpc_streams_overlap"]
 ABI_VERSION = 8          # MPC_ABI_VERSION of include/mpc_mi355x.h this binding is written for
 MAX_OTHERS = 16
 _lib = None
@@ -194,7 +198,7 @@ def load_library(path: str | None = None):
     lib.mpc_set_diagnostics.restype = ctypes.c_int
     lib.mpc_get_last_paths.argtypes = [vp, ctypes.c_int32, dp, ip, vp]
     lib.mpc_get_last_paths.restype = ctypes.c_int
-    for name, sig in list(SIGNATURES.items()) + list(EVALUATION_SIGNATURES.items()):
+    for name, sig in [item for table in _TABLES for item in table.items()]:
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = [_KINDS[kind] for _, kind in sig], ctypes.c_int
     lib.mpc_eval_nlp.argtypes = [vp, ctypes.c_int32] + [vp] * 5 + [ctypes.c_int32, ctypes.c_uint32] + [vp] * 4
@@ -228,12 +232,12 @@ def _caller(name, sig):
     return scope[name]
 
 
-_CALLERS = {name: _caller(name, sig) for name, sig in list(SIGNATURES.items()) + list(EVALUATION_SIGNATURES.items())}
+_CALLERS = {name: _caller(name, sig) for table in _TABLES for name, sig in table.items()}
 
 
 def caller(name: str):
     """The handle-less entry point `name` as a function of keywords alone: every one of SIGNATURES[name] (or
-    EVALUATION_SIGNATURES[name]) and no other (TypeError
+    EVALUATION_SIGNATURES[name], TRACKER_SIGNATURES[name]) and no other (TypeError
     naming the entry point and the parameter otherwise, before anything is called).  Python ints and floats pass through;
     a pointer is a torch tensor (its address; a bool tensor's bytes are the uint8 the kernels read) or None; `stream` is a
     torch stream, its raw handle or None; `params` of mpc_perceive a PerceptionParams.  Enqueue only; EngineError with the

@@ -33,6 +33,11 @@ inside the same captured step (mpc_interaction_metrics), or by the same update i
 last `window` steps - scenes, actions, rewards, the solve's status, the flags, and with a perception model what the agent saw - of
 the episodes that ended with one of the outcomes in `keep`, in a store of `capacity` episodes on the device, filled inside the
 same captured step (mpc_episode_trace) in an order that does not depend on timing, or by the same update in numpy on the CPU path.
+
+`tracker=` puts a tracker (csrc/mpc_tracker.hpp, `Tracker`) behind the perception model, or behind the true observation: a
+vehicle that vanishes for a few steps stays in the agent's observation, moved on with its last velocity, the noise is smoothed,
+and every row the agent gets has an identity (`row_slot`), inside the same captured step (mpc_track_rows), or by the same update
+in numpy on the CPU path.
 """
 from __future__ import annotations
 
@@ -75,6 +80,9 @@ TRACE_INDEX = ("env", "ordinal", "steps", "first", "outcome", "launch")         
 TRACE_COUNTS = ("matched", "kept", "dropped", "launches")                           # counts [4]
 TRACE_FLAGS = dict(done=1, truncated=2, crashed=4, arrived=8)
 TRACE_MAX_WINDOW = 4096
+# csrc/mpc_tracker.hpp: the planes of `counts`, the slots per environment, the longest coast, row_slot of a row without a slot
+TRACKER_COUNTS = ("measured", "matched", "born", "coasted", "expired", "evicted", "cut")   # mpc_track_rows counts [7][B]
+TRACK_SLOTS, TRACK_MAX_COAST, TRACK_NO_SLOT = 16, 200, 255
 
 
 def records_from_planes(rec_i32, rec_f64, names_i32=REC_I32, names_f64=REC_F64, bools=_BOOL) -> dict:
@@ -853,6 +861,150 @@ class Perception:
         return {k: int(c[i]) for i, k in enumerate(PERCEPTION_COUNTS)}
 
 
+class Tracker:
+    """Tracks the vehicles of an observation across frames (csrc/mpc_tracker.hpp states the model step by step): every
+    measured row is associated with the nearest of 16 track slots within `gate` metres of its predicted position (greedy, in
+    row order), smoothed by the gains alpha_pos and alpha_vel (1: the measurement itself), a slot that is not measured is moved
+    on with its last velocity for up to `coast` launches, and the output rows are the alive slots ordered by their distance to
+    the ego.  With coast=0 and both gains 1 the output is the input's present rows, bit for bit, in that order.
+
+    `apply(obs_meas, out, done=None, reset=False)` fills `out` [B, R, 8] f32 and returns it; done [B]: the environments whose
+    episode ended on this step (their tracks are dropped before the frame is read).  `row_slot` [B, R] u8 holds the slot behind
+    every output row of the last launch (255: none), `row_miss` [B, R] u8 the launches since that slot was measured,
+    `track_f64` [B, 16, 7] and `track_i32` [B, 16, 3] the slots (x, y, vx, vy, heading, sin_h, cos_h; alive, age, miss),
+    `counts` [7, B] i64 the events of each of TRACKER_COUNTS since the reset.  Backend "hip" is the kernel (mpc_track_rows,
+    enqueue only, capturable); backend "torch" is the same update in numpy for the CPU environment, the same bits."""
+
+    def __init__(self, B: int, device, backend: str = "torch", R: int = VEHICLES_COUNT, dt: float = 0.1, gate: float = 3.0,
+                 coast: int = 0, alpha_pos: float = 1.0, alpha_vel: float = 1.0):
+        if backend not in ("hip", "torch"):
+            raise ValueError("backend must be 'hip' or 'torch'")
+        if int(B) < 0 or not 1 <= int(R) <= MAX_ROWS:
+            raise ValueError(f"B must be >= 0 and R 1..{MAX_ROWS}")
+        if not float(dt) > 0.0:
+            raise ValueError("dt must be > 0")
+        if not float(gate) >= 0.0:
+            raise ValueError("gate must be >= 0")
+        if int(coast) != coast or not 0 <= int(coast) <= TRACK_MAX_COAST:
+            raise ValueError(f"coast must be an integer 0..{TRACK_MAX_COAST}")
+        for name, v in (("alpha_pos", alpha_pos), ("alpha_vel", alpha_vel)):
+            if not 0.0 < float(v) <= 1.0:
+                raise ValueError(f"{name} must be in (0, 1]")
+        self.B, self.R, self.device, self.backend = int(B), int(R), torch.device(device), backend
+        self.dt, self.gate, self.coast = float(dt), float(gate), int(coast)
+        self.alpha_pos, self.alpha_vel = float(alpha_pos), float(alpha_vel)
+        z = lambda *s, dt: torch.zeros(s, dtype=dt, device=self.device)
+        self.row_slot, self.row_miss = z(self.B, self.R, dt=torch.uint8), z(self.B, self.R, dt=torch.uint8)
+        self.track_f64, self.track_i32 = z(self.B, TRACK_SLOTS, 7, dt=torch.float64), z(self.B, TRACK_SLOTS, 3, dt=torch.int32)
+        self.counts = z(len(TRACKER_COUNTS), self.B, dt=torch.int64)
+
+    @property
+    def config(self) -> dict:
+        """The keyword arguments that make a Tracker with the same model."""
+        return dict(R=self.R, dt=self.dt, gate=self.gate, coast=self.coast, alpha_pos=self.alpha_pos, alpha_vel=self.alpha_vel)
+
+    def apply(self, obs_meas, out, done=None, reset: bool = False):
+        B, R, dev = self.B, self.R, self.device
+        _check(obs_meas, "obs_meas", (B, R, 8), torch.float32, dev)
+        _check(out, "out", (B, R, 8), torch.float32, dev)
+        if out.data_ptr() == obs_meas.data_ptr() and B > 0:
+            raise ValueError("out must not be obs_meas")
+        if done is not None:
+            done = _check(done, "done", (B,), torch.uint8, dev)
+        if self.backend == "torch":
+            rows = self._numpy_apply(obs_meas.cpu().numpy(), None if done is None else done.cpu().numpy(), bool(reset))
+            out.copy_(torch.from_numpy(rows))
+            return out
+        _engine.caller("mpc_track_rows")(
+            device=dev.index, B=B, R=R, reset=1 if reset else 0, dt=self.dt, gate=self.gate, coast=self.coast,
+            alpha_pos=self.alpha_pos, alpha_vel=self.alpha_vel, obs_meas=obs_meas, done=done, obs_out=out,
+            row_slot=self.row_slot, row_miss=self.row_miss, track_f64=self.track_f64, track_i32=self.track_i32,
+            counts=self.counts, stream=_engine.current_stream(dev))
+        return out
+
+    def _numpy_apply(self, meas, done, reset):
+        """csrc/mpc_tracker.hpp over the batch: the loops over rows stay, every statement acts on all environments."""
+        B, R, S = self.B, self.R, TRACK_SLOTS
+        tf, ti, counts = self.track_f64.cpu().numpy().copy(), self.track_i32.cpu().numpy().copy(), self.counts.cpu().numpy().copy()
+        env = np.arange(B)
+        clear = np.ones(B, bool) if reset else (np.zeros(B, bool) if done is None else done != 0)
+        if reset:
+            counts[:] = 0
+        tf[clear], ti[clear] = 0.0, 0                                              # 1
+        f = [tf[:, :, c].copy() for c in range(7)]                                 # x, y, vx, vy, heading, sin_h, cos_h [B, S]
+        alive, age, miss = ti[:, :, 0] != 0, ti[:, :, 1].copy(), ti[:, :, 2].copy()
+        f[0] = np.where(alive, f[0] + f[2] * self.dt, f[0])                        # 2
+        f[1] = np.where(alive, f[1] + f[3] * self.dt, f[1])
+        m = meas.astype(np.float64)
+        present = meas[:, :, 0] != 0
+        present[:, 0] = False
+        claimed, unassociated = np.zeros((B, S), bool), np.zeros((B, R), bool)
+        gate2 = self.gate * self.gate
+        blend = lambda a, alpha, v: v if alpha == 1.0 else a + alpha * (v - a)
+        for i in range(1, R):                                                      # 3, 4
+            dx, dy = m[:, i, 1, None] - f[0], m[:, i, 2, None] - f[1]
+            d = dx * dx + dy * dy
+            eligible = present[:, i, None] & alive & ~claimed & (d <= gate2)
+            best = np.argmin(np.where(eligible, d, np.inf), axis=1)                # the first of the smallest: the lowest slot
+            found = eligible[env, best]
+            e, s = env[found], best[found]
+            claimed[e, s] = True
+            f[0][e, s], f[1][e, s] = blend(f[0][e, s], self.alpha_pos, m[e, i, 1]), blend(f[1][e, s], self.alpha_pos, m[e, i, 2])
+            f[2][e, s], f[3][e, s] = blend(f[2][e, s], self.alpha_vel, m[e, i, 3]), blend(f[3][e, s], self.alpha_vel, m[e, i, 4])
+            for c in (4, 5, 6):
+                f[c][e, s] = m[e, i, c + 1]
+            miss[e, s] = 0
+            age[e, s] += 1
+            unassociated[:, i] = present[:, i] & ~found
+        coasting = alive & ~claimed                                                # 5
+        miss = miss + coasting
+        expired = coasting & (miss > self.coast)
+        alive, coasting = alive & ~expired, coasting & ~expired
+        for a in f + [age, miss]:
+            a[expired] = 0
+        queue = np.argsort(np.where(alive, np.where(claimed, 2, 1), 0), axis=1, kind="stable")      # 6: free, then coasting
+        place = np.cumsum(unassociated, axis=1) - 1
+        evicted = np.zeros(B, np.int64)
+        was_alive = alive.copy()
+        for i in range(1, R):
+            e = env[unassociated[:, i]]
+            s = queue[e, place[e, i]]
+            evicted[e] += was_alive[e, s]
+            for c in range(7):
+                f[c][e, s] = m[e, i, c + 1]
+            alive[e, s], age[e, s], miss[e, s] = True, 1, 0
+        out = np.zeros((B, R, 8), np.float32)                                      # 7
+        out[:, 0] = meas[:, 0]
+        row_slot, row_miss = np.full((B, R), TRACK_NO_SLOT, np.uint8), np.zeros((B, R), np.uint8)
+        kx, ky = f[0] - m[:, 0, 1, None], f[1] - m[:, 0, 2, None]
+        key = kx * kx + ky * ky
+        slot = np.arange(S)
+        ahead = alive[:, None, :] & ((key[:, None, :] < key[:, :, None]) |
+                                     ((key[:, None, :] == key[:, :, None]) & (slot[None, None, :] < slot[None, :, None])))
+        rank = ahead.sum(axis=2)                                                   # [B, S]: alive slots ordered before slot s
+        shown = alive & (rank < R - 1)
+        e, s = np.nonzero(shown)
+        out[e, 1 + rank[e, s], 0] = 1.0
+        for c in range(7):
+            out[e, 1 + rank[e, s], c + 1] = f[c][e, s].astype(np.float32)
+        row_slot[e, 1 + rank[e, s]], row_miss[e, 1 + rank[e, s]] = s, miss[e, s]
+        n = (present.sum(axis=1), claimed.sum(axis=1), unassociated.sum(axis=1), (shown & (miss > 0)).sum(axis=1),         # 8
+             expired.sum(axis=1), evicted, (alive & ~shown).sum(axis=1))
+        for k, v in enumerate(n):
+            counts[k] += v
+        tf = np.stack(f, axis=2)
+        ti = np.stack([alive.astype(np.int32), age, miss.astype(np.int32)], axis=2).astype(np.int32)
+        _write_back(((self.track_f64, tf), (self.track_i32, ti), (self.counts, counts), (self.row_slot, row_slot),
+                     (self.row_miss, row_miss)))
+        return out
+
+    def totals(self) -> dict:
+        """Events since the reset, summed over the environments: rows measured, matched to a track, born as a new track;
+        output rows that were coasted; tracks expired, evicted by a birth, cut from the output for want of rows."""
+        c = self.counts.sum(dim=1).cpu().numpy()
+        return {k: int(c[i]) for i, k in enumerate(TRACKER_COUNTS)}
+
+
 def _keep_bits(keep) -> int:
     names = (keep,) if isinstance(keep, str) else tuple(keep)
     bits = 0
@@ -1084,7 +1236,8 @@ class EvalResult:
     evaluation, idle steps included) when the evaluation ran with one, else None; interaction: the interaction metrics'
     records (dict of numpy arrays [B, Q], keys INTERACT_I32 + INTERACT_F64, the same slots) when the evaluation ran with
     interaction=True, else None; traces: the episodes the trace recorder kept (`EpisodeTraces`) when the evaluation ran with
-    trace=, else None."""
+    trace=, else None; tracker: the totals of the tracker (`Tracker.totals()`: measured, matched, born, coasted, expired,
+    evicted, cut over the whole evaluation, idle steps included) when the evaluation ran with one, else None."""
     records: dict
     dt: float
     steps: int
@@ -1094,6 +1247,7 @@ class EvalResult:
     perception: dict | None = None
     interaction: dict | None = None
     traces: EpisodeTraces | None = None
+    tracker: dict | None = None
 
     @property
     def travel_time(self):
@@ -1113,7 +1267,8 @@ class EvalResult:
         HARD_BRAKE, over all folded states), forced_brake_events_per_episode, max_forced_decel_mean and max_forced_decel_max
         over episodes, speed_deficit_per_episode [m/s], conflicts_per_episode, pet_critical_frac and ego_first_frac (of the
         conflicts; 0 when there is none) and min_pet_p05 (the 5th percentile of min_pet over the episodes with a conflict;
-        inf when there is none)."""
+        inf when there is none).  With a tracker also coasted_frac: the output rows that were coasted, as a share of all
+        output rows, coasted / (matched + born + coasted) (0 when there was none)."""
         out = self._base_summary()
         if self.drive is not None:
             out.update(self._drive_summary())
@@ -1122,6 +1277,9 @@ class EvalResult:
             out.update({f"{k}_frac": self.perception[k] / present for k in ("seen", "occluded", "out_of_range", "dropped")})
         if self.interaction is not None:
             out.update(self._interaction_summary())
+        if self.tracker is not None:
+            t = self.tracker
+            out["coasted_frac"] = t["coasted"] / max(t["matched"] + t["born"] + t["coasted"], 1)
         return out
 
     def _interaction_summary(self) -> dict:
@@ -1184,7 +1342,8 @@ def _instance(cls, given, defaults: dict, *args):
 @torch.no_grad()
 def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = False, reset_mpc_on_done: bool = False,
                    use_graph: bool | None = None, poll_every: int = 16, seed: int = 0, on_step=None,
-                   metrics: bool = False, perception=None, interaction: bool = False, trace=None) -> EvalResult:
+                   metrics: bool = False, perception=None, interaction: bool = False, trace=None,
+                   tracker=None) -> EvalResult:
     """Run `agent` in closed loop on the B environments of `env` (a SyntheticIntersectionEnv) until each environment has
     finished `episodes_per_env` episodes; returns their records.
 
@@ -1212,6 +1371,12 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     the environment's, seen to whether a perception model is in use): the step-by-step record of the selected episodes
     (EvalResult.traces), updated after the interaction metrics inside the step (so inside the captured graph) and before the
     buffer the agent acted on is overwritten.  Everything else, on_step's dict included, is what it is without it.
+    tracker: a `Tracker` for this environment's batch, or a dict of its keyword arguments (dt defaults to the environment's):
+    the agent then acts on `tracker.apply(...)` of what the perception model gives (which then writes into a buffer of its
+    own), or of the true observation without one; launched right after perception.apply, after the reset (reset=True) and
+    inside the step with the step's `done` (so inside the captured graph).  on_step's dict then also holds obs, seen (the
+    tracker's output, what the agent gets), row_slot and row_miss; the trace recorder's `seen` is the tracker's output;
+    EvalResult.tracker holds the totals.  The accounting and every metric keep reading the true scene.  None: nothing changes.
     Every episode ends by EPISODE_STEPS (200) steps, so Q * 200 steps bound the loop; RuntimeError if the episodes are not
     all recorded by then."""
     Q = int(episodes_per_env)
@@ -1239,31 +1404,48 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     perception = _instance(Perception, perception, dict(env_offset=offset), B, dev, backend)
     if perception is not None and (perception.B != B or perception.R != VEHICLES_COUNT or perception.device != dev):
         raise ValueError(f"perception must be built for {B} environments of {VEHICLES_COUNT} rows on {dev}")
-    trace = _instance(EpisodeTrace, trace, dict(R=VEHICLES_COUNT, env_offset=offset, seen=perception is not None),
-                      B, Q, dev, backend)
+    tracker = _instance(Tracker, tracker, dict(R=VEHICLES_COUNT, dt=float(env.dt)), B, dev, backend)
+    if tracker is not None and (tracker.B != B or tracker.R != VEHICLES_COUNT or tracker.device != dev):
+        raise ValueError(f"tracker must be built for {B} environments of {VEHICLES_COUNT} rows on {dev}")
+    filtered = perception is not None or tracker is not None       # the agent acts on something other than the true scene
+    sensed = torch.zeros_like(obs) if perception is not None and tracker is not None else None    # between the two
+    trace = _instance(EpisodeTrace, trace, dict(R=VEHICLES_COUNT, env_offset=offset, seen=filtered), B, Q, dev, backend)
     if trace is not None:
         if (trace.B, trace.Q, trace.R, trace.device) != (B, Q, VEHICLES_COUNT, dev):
             raise ValueError(f"trace must be built for {B} environments, {Q} episodes each, {VEHICLES_COUNT} rows, on {dev}")
-        if trace.seen and perception is None:
-            raise ValueError("trace records seen=True only with a perception model")
+        if trace.seen and not filtered:
+            raise ValueError("trace records seen=True only with a perception model or a tracker")
     stats = EpisodeStats(B, Q, dev, backend)
     drive = DriveMetrics(B, Q, dev, backend, env.ref_xy, env.dt, VEHICLES_COUNT) if metrics else None
     inter = InteractionMetrics(B, Q, dev, backend, env.ref_xy, env.dt, env.K) if interaction else None
     # The order of a step's launches, after the agent's and the environment's: the accounting, the drive metrics, the
-    # interaction metrics, the trace recorder - each `observe` of the step's frame - and then perception.apply (or the
-    # plain copy), which overwrites the buffer the agent acted on: the recorder has to have read it by then.
+    # interaction metrics, the trace recorder - each `observe` of the step's frame - and then perception.apply and
+    # tracker.apply (or the plain copy), which overwrite the buffer the agent acted on: the recorder has to have read it by
+    # then.
     observers = [o for o in (stats, drive, inter, trace) if o is not None]
     kw = dict(deterministic=bool(deterministic), seed=int(seed), env_offset=offset)
     # what on_step is shown of a frame: the accounting's inputs; with metrics=True also the scenes and the action; with a
     # perception model also the true observation, what the agent gets next and (below) the class of every row
     shown = ("ego", "done", "truncated", "crashed", "arrived", "reward", "status", "iters") + \
-        (("terminal_obs", "obs", "act") if metrics else ()) + (("obs", "seen") if perception is not None else ())
+        (("terminal_obs", "obs", "act") if metrics else ()) + (("obs", "seen") if filtered else ())
 
     def show(frame, **first):
         first.update((k, frame[k]) for k in shown if k in frame)
         if perception is not None:
             first["row_class"] = perception.row_class
+        if tracker is not None:
+            first["row_slot"], first["row_miss"] = tracker.row_slot, tracker.row_miss
         on_step(first)
+
+    def sense(true, reset=False, done=None):
+        """`obs` <- what the agent gets of the true observation"""
+        if not filtered:
+            obs.copy_(true)
+        elif tracker is None:
+            perception.apply(true, obs, reset=reset)
+        else:
+            meas = true if perception is None else perception.apply(true, sensed, reset=reset)
+            tracker.apply(meas, obs, done=done, reset=reset)
 
     def step():
         out = agent.act_batch_torch(obs, **kw)
@@ -1275,23 +1457,17 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
         frame = dict(env=env, ego=env.ego, terminal_obs=info["terminal_obs"], obs=new_obs, act=out["act"], reward=reward,
                      done=done, truncated=info["truncated"], crashed=info["crashed"], arrived=info["arrived"],
                      status=out["status"], iters=out["iters"], step=out.get("step"))
-        if perception is not None:
+        if filtered:
             frame["seen"] = obs       # still what the agent acted on while the observers run; what it gets next after them
         for o in observers:
             o.observe(frame)
-        if perception is None:
-            obs.copy_(new_obs)
-        else:
-            perception.apply(new_obs, obs)
+        sense(new_obs, done=done)
         return out, frame
 
     def first_obs(reset):
         true = env.reset()
-        if perception is None:
-            obs.copy_(true)
-            return obs
-        perception.apply(true, obs, reset=reset)
-        return true
+        sense(true, reset=reset)
+        return true if filtered else obs
 
     graph = None
     if use_graph:
@@ -1319,7 +1495,7 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
             t.copy_(snap[n])
         env.gen.set_state(gen_state)
 
-    true0 = first_obs(True)                  # `obs` itself without a perception model
+    true0 = first_obs(True)                  # `obs` itself without a perception model or a tracker
     if hasattr(agent, "reset_env_state"):
         agent.reset_env_state()
     elif hasattr(eng, "reset_env_state"):
@@ -1327,7 +1503,7 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     if hasattr(agent, "restart_actions"):
         agent.restart_actions()
     frame = dict(env=env, ego=env.ego, obs=true0)
-    if perception is not None:
+    if filtered:
         frame["seen"] = obs
     for o in observers:
         o.observe(frame, reset=True)
@@ -1359,24 +1535,27 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
                       drive=None if drive is None else drive.records(),
                       perception=None if perception is None else perception.totals(),
                       interaction=None if inter is None else inter.records(),
-                      traces=None if trace is None else trace.traces())
+                      traces=None if trace is None else trace.traces(),
+                      tracker=None if tracker is None else tracker.totals())
 
 
 def compare(agents: dict, make_env, episodes_per_env: int = 1, metrics: bool = False, perception=None,
-            interaction: bool = False, trace=None, results=None, **kw) -> dict:
+            interaction: bool = False, trace=None, results=None, tracker=None, **kw) -> dict:
     """Evaluate every agent on a fresh environment from make_env() (same seed: the HIP environment keys its draws by seed and
     environment id, so every agent meets the same initial episodes) -> {name: summary}; metrics=True adds the drive metrics'
     keys to every summary.  perception (a dict of `Perception`'s keyword arguments, or a Perception whose configuration is
     copied): every agent gets a fresh Perception with the same seed, hence the same draws on the same steps.
     interaction=True adds the interaction metrics' keys (the environments must have traffic="idm").  trace (a dict of
     `EpisodeTrace`'s keyword arguments, or an EpisodeTrace whose settings are copied): every agent gets a fresh recorder with
-    the same settings.  results: a dict that receives every agent's EvalResult by name (its traces, its records)."""
-    perception, trace = (x.config if isinstance(x, (Perception, EpisodeTrace)) else x for x in (perception, trace))
+    the same settings.  tracker (a dict of `Tracker`'s keyword arguments, or a Tracker whose configuration is copied): every
+    agent gets a fresh tracker.  results: a dict that receives every agent's EvalResult by name (its traces, its records)."""
+    perception, trace, tracker = (x.config if isinstance(x, (Perception, EpisodeTrace, Tracker)) else x
+                                  for x in (perception, trace, tracker))
     fresh = lambda settings: None if settings is None else dict(settings)
     out = {}
     for name, agent in agents.items():
         res = evaluate_agent(agent, make_env(), episodes_per_env, metrics=metrics, perception=fresh(perception),
-                             interaction=interaction, trace=fresh(trace), **kw)
+                             interaction=interaction, trace=fresh(trace), tracker=fresh(tracker), **kw)
         if results is not None:
             results[name] = res
         out[name] = res.summary()

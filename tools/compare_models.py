@@ -6,6 +6,10 @@ route keeping; a value that does not exist, such as the closest gap when no vehi
 --range, --occlusion, --dropout and the three --sigma-* flags put a perception model between the environment and every agent
 (evaluate.Perception: the agents act on what the ego sees, the numbers keep describing the true scene); the flags are echoed
 in the JSON line, which then also holds the share of present rows that were seen, occluded, out of range and dropped.
+--track-coast, --track-gate, --track-alpha-pos and --track-alpha-vel put a tracker behind the perception model (or the true
+observation; evaluate.Tracker): a vehicle that vanishes for up to --track-coast steps stays in the observation at its last
+velocity, measurements within --track-gate metres of a track are smoothed by the two gains.  Any of them switches it on; they
+are echoed in the JSON line, which then also holds coasted_frac, the share of the agent's rows that were coasted.
 
 Agents: pure MPC with the collision cost off and on, the iterative-linear (LTV) agent, and MPC-RL - an SB3 `.zip` given with
 --mpcrl, or with --fixture the v0 PPO (gSDE) policy rebuilt from tests/golden/sb3_policies.npz.  --ppo PATH adds the reference's
@@ -15,6 +19,7 @@ in the layout ActorCritic.save_sb3 writes; --ppo-random adds it with a seeded un
   python tools/compare_models.py --envs 256 --episodes-per-env 1 --fixture
   python tools/compare_models.py --metrics --traffic idm --envs 256 --fixture
   python tools/compare_models.py --metrics --traffic idm --occlusion buildings --range 60 --sigma-pos 0.2
+  python tools/compare_models.py --metrics --traffic idm --occlusion buildings --dropout 0.05 --track-coast 10
   python tools/compare_models.py --metrics --traffic idm --interaction --envs 256
   python tools/compare_models.py --envs 256 --fixture --ppo baseline.zip
   python tools/compare_models.py --traffic idm --trace failed --trace-window 50 --trace-dir out
@@ -55,6 +60,10 @@ def main():
     ap.add_argument("--sigma-pos", type=float, default=0.0, help="perception: position noise [m]")
     ap.add_argument("--sigma-vel", type=float, default=0.0, help="perception: velocity noise [m/s]")
     ap.add_argument("--sigma-head", type=float, default=0.0, help="perception: heading noise [rad]")
+    ap.add_argument("--track-coast", type=int, metavar="N", help="tracker: steps a vehicle that is not measured is kept (0..200)")
+    ap.add_argument("--track-gate", type=float, metavar="G", help="tracker: association gate [m] (default 3)")
+    ap.add_argument("--track-alpha-pos", type=float, metavar="A", help="tracker: gain on the measured position, (0, 1]")
+    ap.add_argument("--track-alpha-vel", type=float, metavar="A", help="tracker: gain on the measured velocity, (0, 1]")
     src = ap.add_mutually_exclusive_group()
     src.add_argument("--mpcrl", help="an SB3 checkpoint (.zip) of the reference's MPC-RL agent")
     src.add_argument("--fixture", action="store_true", help="MPC-RL: the v0 PPO policy of tests/golden/sb3_policies.npz")
@@ -112,6 +121,10 @@ def main():
                           occluders=evaluate.corner_buildings() if args.occlusion == "buildings" else None)
     finite = lambda v: None if isinstance(v, float) and not math.isfinite(v) else v
     echo = {} if perception is None else dict(perception={k: finite(v) for k, v in flags.items()})
+    given = dict(coast=args.track_coast, gate=args.track_gate, alpha_pos=args.track_alpha_pos, alpha_vel=args.track_alpha_vel)
+    tracker = {k: v for k, v in given.items() if v is not None} or None        # no flag given: no tracker, the launches of before
+    if tracker is not None:
+        echo["tracker"] = {k: finite(v) for k, v in evaluate.Tracker(0, dev, "hip", **tracker).config.items() if k in given}
     trace = None
     if args.trace:
         keep = args.trace.split(",") if "," in args.trace else args.trace
@@ -121,7 +134,7 @@ def main():
         results = {}
         s = evaluate.compare({name: agent}, make_env, args.episodes_per_env, deterministic=args.deterministic,
                              seed=args.seed, metrics=args.metrics, perception=perception,
-                             interaction=args.interaction, trace=trace, results=results)[name]
+                             interaction=args.interaction, trace=trace, tracker=tracker, results=results)[name]
         s = {k: finite(v) for k, v in s.items()}
         if trace is not None:
             path = os.path.join(args.trace_dir, f"{name}.npz")
