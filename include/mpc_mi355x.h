@@ -610,6 +610,51 @@ int mpc_track_rows(int32_t device, int32_t B, int32_t R, int32_t reset, double d
                    void *stream);
 
 /*
+ * mpc_actuate (an addition within ABI 8: old clients never call it, nothing else changes) - an actuator model between the
+ * agent and the plant of a closed-loop evaluation: `applied` is what the vehicle makes of the agent's `command` under a
+ * transport delay of whole policy steps, lost commands (the previous one is held), calibration gain and offset, bounded noise,
+ * a first-order lag, a rate limit and saturation (every formula, in evaluation order, in csrc/mpc_actuator.hpp).  Device
+ * pointers, enqueue only on `stream`, never synchronises (capturable in a hipGraph); one lane per (environment, channel)
+ * pair, 32 environments per wave, no LDS, no atomics, no scratch.  One launch per policy step between the agent's action and
+ * the environment's step, and one with reset != 0 before the first.
+ *
+ * command, applied [B][2] f64 (acceleration m/s^2, steering rad; applied may be command); done_prev [B] u8 or NULL: the
+ * environments whose episode ended on the previous step, so that this command is the first of a new episode (their delay
+ * line, held command and lag state are cleared first).  State: state_f64 [10][B][2] = the last eight commands, what reached
+ * the actuator last, what was applied last; age [B] i32 the commands of this episode; ctr [B] i64 the launch counter that
+ * keys the draws with (seed, env_offset + b).  counts [5][B] i64 += steps, held, rate_limited, saturated, nonfinite (each at
+ * most one per environment and launch; a NaN or infinite command is applied as 0.0 and counted); sums [2][B][2] f64: the sum
+ * and the maximum of |applied - command|.  reset != 0: state, age, ctr, counts and sums of every environment become 0, no
+ * command is read and no applied written (command, done_prev and applied may be NULL).  With every parameter off (delay 0,
+ * p_hold 0, gain 1, offset 0, sigma 0, alpha 1, rate +inf, lo -inf, hi +inf) applied is command bit for bit for every finite
+ * command.
+ * Errors (MPC_ERR_INVALID_ARG): B < 0, a NULL params / state_f64 / age / ctr / counts / sums, a NULL command / applied with
+ * reset == 0, a wrong struct_size, delay outside 0 .. 7, dt NaN or <= 0, p_hold outside [0, 1], a gain or offset that is
+ * not finite, a sigma that is negative or not finite, alpha outside (0, 1], rate NaN or <= 0 (+inf is allowed), lo > hi or
+ * either NaN.  B == 0 is a no-op.
+ */
+typedef struct mpc_actuator {
+    int32_t struct_size; /* sizeof(mpc_actuator), checked like mpc_config.struct_size */
+    int32_t delay;       /* 0..7 whole policy steps between the command and its arrival at the actuator */
+    int32_t env_offset;  /* global id of environment 0 of this batch (sharding) */
+    int32_t reserved;    /* 0 */
+    double dt;           /* s, the policy step: the rate limit per launch is rate * dt */
+    double p_hold;       /* probability that a step's command is lost and the previous one held, [0, 1] */
+    double gain[2];      /* per channel (0 acceleration, 1 steering); 1 = off */
+    double offset[2];    /* 0 = off */
+    double sigma[2];     /* standard deviation of the noise; 0 = off */
+    double alpha[2];     /* lag: applied = prev + alpha (target - prev), (0, 1]; 1 = off; dt / (tau + dt) */
+    double rate[2];      /* largest change per second; +inf = off */
+    double lo[2];        /* saturation; -inf = off */
+    double hi[2];        /* +inf = off */
+    uint64_t seed;
+} mpc_actuator;
+
+int mpc_actuate(int32_t device, int32_t B, int32_t reset, const mpc_actuator *params, const double *command,
+                const uint8_t *done_prev, double *applied, double *state_f64, int32_t *age, int64_t *ctr, int64_t *counts,
+                double *sums, void *stream);
+
+/*
  * Diagnostics: the NLP's functions at GIVEN points, evaluated by the solve kernel's own code (csrc/mpc_wave.hpp:
  * Solver::evaluate - stage_terms / track / dist, which judge every line-search trial, and the model step of the rollouts),
  * so that f(z) and g(z) computed by the reference's statements (agents/pure_mpc.py:128-283; tests/golden/

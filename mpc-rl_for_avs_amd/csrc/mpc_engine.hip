@@ -32,6 +32,7 @@
 #include "mpc_drive_metrics.hpp"
 #include "mpc_perception.hpp"
 #include "mpc_tracker.hpp"
+#include "mpc_actuator.hpp"
 #include "mpc_interaction.hpp"
 #include "mpc_episode_stats.hpp"
 #include "mpc_episode_trace.hpp"
@@ -1189,6 +1190,82 @@ __global__ __launch_bounds__(64) void mpc_track_kernel(mpc::track::Params P, mpc
     }
 }
 
+// actuator model of a closed-loop evaluation (mpc_actuator.hpp): one lane per (environment, channel) pair, 32 environments
+// per wave - lane l is environment blockIdx.x * 32 + (l >> 1) and channel l & 1, so the loads and stores of command, applied,
+// the sums and every plane of the [.][B][2] state are consecutive addresses across the wave.  The ring stays in memory: a lane
+// stores its command into slot age & 7 and loads slot (age - delay) & 7, which is another slot whenever delay > 0; nothing is
+// indexed in registers.  What both channels of an environment share goes through __shfl_xor(., 1) in wave-uniform control
+// flow: the hold draw (the even lane's) and the OR of the nonfinite, rate_limited and saturated flags.  A lane past the end
+// computes on the last environment; only its stores are predicated.  The even lane writes age, ctr and the counts.  No LDS, no
+// atomics, no scratch.
+__global__ __launch_bounds__(64) void mpc_actuate_kernel(mpc::act::Params P, mpc::act::Buffers buf, int reset) {
+#pragma clang fp contract(off)
+    namespace act = mpc::act;
+    const int l = threadIdx.x, c = l & 1;
+    const int b_ = blockIdx.x * 32 + (l >> 1);
+    const bool live = b_ < buf.B;
+    const int B = buf.B, b = live ? b_ : B - 1;
+    if (reset != 0) {                                        // wave-uniform
+        if (!live) return;
+#pragma unroll
+        for (int p = 0; p < act::kPlanes; ++p) buf.state[act::at(p, B, b, c)] = 0.0;
+#pragma unroll
+        for (int p = 0; p < act::kSums; ++p) buf.sums[act::at(p, B, b, c)] = 0.0;
+        if (c == 0) {
+            buf.age[b] = 0;
+            buf.ctr[b] = 0;
+#pragma unroll
+            for (int f = 0; f < act::kCounts; ++f) buf.counts[(size_t)f * B + b] = 0;
+        }
+        return;
+    }
+    const bool clear = buf.done_prev != nullptr && buf.done_prev[b] != 0;                // 1
+    const int age = clear ? 0 : buf.age[b];
+    const int64_t ctr = buf.ctr[b];
+    double u = buf.command[act::at(0, B, b, c)];                                         // 2
+    const bool nonfinite = !act::is_finite(u);
+    u = nonfinite ? 0.0 : u;
+    const int slot = age & (act::kRing - 1);                                             // 3
+    double delayed = u;
+    if (P.delay > 0) {                                       // wave-uniform; the slot read is not the slot written below
+        const double old = buf.state[act::at((age - P.delay) & (act::kRing - 1), B, b, c)];
+        delayed = age >= P.delay ? old : 0.0;                // after a clear age is 0: nothing stale is used
+    }
+    const double last = clear ? 0.0 : buf.state[act::at(act::kLast, B, b, c)];
+    const double prev = clear ? 0.0 : buf.state[act::at(act::kPrev, B, b, c)];
+    const mpc::env::Rng r(P.seed ^ act::kSalt, P.env_offset + b, ctr);
+    const int drawn = act::hold_draw(P, r) ? 1 : 0;                                      // 4
+    const int partner = __shfl_xor(drawn, 1);
+    const bool held = (c == 0 ? drawn : partner) != 0;       // the even lane's draw, for both channels
+    delayed = held ? last : delayed;
+    bool rate_limited, saturated;
+    const double y = act::shape(act::channel(P, c), P.dt, r, c, delayed, prev, rate_limited, saturated);   // 5 - 8
+    const int mine = (nonfinite ? 1 : 0) | (rate_limited ? 2 : 0) | (saturated ? 4 : 0);
+    const int flags = mine | __shfl_xor(mine, 1);
+    if (!live) return;                                       // nothing but stores below
+#pragma unroll
+    for (int k = 0; k < act::kRing; ++k) {
+        if (k == slot)
+            buf.state[act::at(k, B, b, c)] = u;
+        else if (clear)
+            buf.state[act::at(k, B, b, c)] = 0.0;
+    }
+    buf.state[act::at(act::kLast, B, b, c)] = delayed;
+    buf.state[act::at(act::kPrev, B, b, c)] = y;                                         // 9
+    buf.applied[act::at(0, B, b, c)] = y;
+    const double dev = act::deviation(y, u);
+    const double top = buf.sums[act::at(1, B, b, c)];
+    buf.sums[act::at(0, B, b, c)] = buf.sums[act::at(0, B, b, c)] + dev;
+    buf.sums[act::at(1, B, b, c)] = dev > top ? dev : top;
+    if (c == 0) {
+        buf.age[b] = age + 1;
+        buf.ctr[b] = ctr + 1;
+        const int n[act::kCounts] = {1, held ? 1 : 0, (flags >> 1) & 1, (flags >> 2) & 1, flags & 1};
+#pragma unroll
+        for (int f = 0; f < act::kCounts; ++f) buf.counts[(size_t)f * B + b] += n[f];
+    }
+}
+
 // end of a rollout (mpc_rollout_glue.hpp: truncation bootstrap + GAE): one workgroup per environment; thread t computes the
 // terms of step t (strided over T), thread 0 runs the reversed recurrence over the LDS copies, all threads store
 __global__ __launch_bounds__(256) void mpc_rollout_finish_kernel(mpc::glue::GaeArgs g) {
@@ -2309,6 +2386,32 @@ int mpc_track_rows(int32_t device, int32_t B, int32_t R, int32_t reset, double d
     const mpc::track::Params P{dt, gate * gate, alpha_pos, alpha_vel, coast};
     const mpc::track::Buffers buf{(int)B, (int)R, obs_meas, done, obs_out, row_slot, row_miss, track_f64, track_i32, counts};
     hipLaunchKernelGGL(mpc_track_kernel, dim3((unsigned)((B + 3) / 4)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream_),
+                       P, buf, (int)reset);
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_actuate(int32_t device, int32_t B, int32_t reset, const mpc_actuator *params, const double *command,
+                const uint8_t *done_prev, double *applied, double *state_f64, int32_t *age, int64_t *ctr, int64_t *counts,
+                double *sums, void *stream_) {
+    namespace act = mpc::act;
+    if (B < 0) return fail(MPC_ERR_INVALID_ARG, "mpc_actuate: bad size (B >= 0)");
+    if (!params || !state_f64 || !age || !ctr || !counts || !sums)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_actuate: null params / state_f64 / age / ctr / counts / sums pointer");
+    if (reset == 0 && (!command || !applied))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_actuate: null command / applied pointer in a launch without reset");
+    if (params->struct_size != (int32_t)sizeof(mpc_actuator))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_actuate: mpc_actuator.struct_size mismatch");
+    const mpc_actuator &p = *params;
+    const act::Params P{p.dt, p.p_hold, {p.gain[0], p.gain[1]}, {p.offset[0], p.offset[1]}, {p.sigma[0], p.sigma[1]},
+                        {p.alpha[0], p.alpha[1]}, {p.rate[0], p.rate[1]}, {p.lo[0], p.lo[1]}, {p.hi[0], p.hi[1]}, p.seed,
+                        p.delay, p.env_offset};
+    if (const char *why = act::refusal(P))
+        return fail(MPC_ERR_INVALID_ARG, std::string("mpc_actuate: bad parameter (") + why + ")");
+    if (B == 0) return MPC_OK;
+    HIP_TRY(hipSetDevice(device));
+    const act::Buffers buf{(int)B, command, done_prev, applied, state_f64, age, ctr, counts, sums};
+    hipLaunchKernelGGL(mpc_actuate_kernel, dim3((unsigned)((B + 31) / 32)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream_),
                        P, buf, (int)reset);
     HIP_TRY(hipGetLastError());
     return MPC_OK;

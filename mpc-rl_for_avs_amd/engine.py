@@ -1,7 +1,7 @@
 """ctypes binding of the C ABI (include/mpc_mi355x.h) - the only way Python reaches the HIP kernels: the entry points that
 take an engine handle through `MPCEngine`'s methods, the handle-less ones (environment step, policy step, rollout glue,
-evaluation accounting, perception, episode traces, tracker) through `call` / `caller`, by parameter name, in the order of
-`SIGNATURES`, `EVALUATION_SIGNATURES` and `TRACKER_SIGNATURES`.
+evaluation accounting, perception, episode traces, tracker, actuator) through `call` / `caller`, by parameter name, in the
+order of `SIGNATURES`, `EVALUATION_SIGNATURES`, `TRACKER_SIGNATURES` and `ACTUATION_SIGNATURES`.
 
 There is no CPU fallback: if the shared library is missing, or no MI355X is visible, construction fails
 loudly (`EngineError`).  Host numpy arrays are copied by the library; torch device tensors are passed
@@ -61,8 +61,17 @@ class PerceptionParams(ctypes.Structure):
                 ("seed", ctypes.c_uint64)]
 
 
+class ActuatorParams(ctypes.Structure):
+    """mpc_actuator of include/mpc_mi355x.h (csrc/mpc_actuator.hpp has the model); the per-channel fields take a pair."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("delay", ctypes.c_int32), ("env_offset", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("dt", ctypes.c_double), ("p_hold", ctypes.c_double)] + \
+        [(name, ctypes.c_double * 2) for name in ("gain", "offset", "sigma", "alpha", "rate", "lo", "hi")] + \
+        [("seed", ctypes.c_uint64)]
+
+
 # The handle-less entry points: every parameter of the prototype in include/mpc_mi355x.h, in its order, as name:kind - i32
-# (int32_t), u64 (uint64_t), f64 (double), ptr (any pointer, the stream included), perception (const mpc_perception *).
+# (int32_t), u64 (uint64_t), f64 (double), ptr (any pointer, the stream included), perception (const mpc_perception *),
+# actuator (const mpc_actuator *).
 # load_library builds their argtypes from this table and `caller` orders its named arguments by it; tests/test_abi.py holds
 # it against the header.
 _POLICY_IN = "obs:ptr w1:ptr b1:ptr w2:ptr b2:ptr wh:ptr bh:ptr"
@@ -75,7 +84,7 @@ _CONTROL = (f"device:i32 B:i32 H2:i32 {_POLICY_IN} std_:ptr c0:ptr noise:ptr noi
             f"{_POLICY_OUT} control:ptr stream:ptr")
 _RECORDS = "state_i32:ptr state_f64:ptr rec_i32:ptr rec_f64:ptr"
 _KINDS = dict(i32=ctypes.c_int32, u64=ctypes.c_uint64, f64=ctypes.c_double, ptr=ctypes.c_void_p,
-              perception=ctypes.POINTER(PerceptionParams))
+              perception=ctypes.POINTER(PerceptionParams), actuator=ctypes.POINTER(ActuatorParams))
 SIGNATURES = {name: tuple(tuple(word.split(":")) for word in text.split()) for name, text in dict(
     mpc_synth_env_step=f"{_SYNTH_IN} {_SYNTH_OUT}",
     mpc_synth_env_step_idm=f"{_SYNTH_IN} oroute:ptr oprog:ptr otarget:ptr {_SYNTH_OUT}",
@@ -113,13 +122,18 @@ EVALUATION_SIGNATURES = {name: tuple(tuple(word.split(":")) for word in text.spl
 TRACKER_SIGNATURES = {name: tuple(tuple(word.split(":")) for word in text.split()) for name, text in dict(
     mpc_track_rows="device:i32 B:i32 R:i32 reset:i32 dt:f64 gate:f64 coast:i32 alpha_pos:f64 alpha_vel:f64 obs_meas:ptr "
                    "done:ptr obs_out:ptr row_slot:ptr row_miss:ptr track_f64:ptr track_i32:ptr counts:ptr stream:ptr").items()}
-_TABLES = (SIGNATURES, EVALUATION_SIGNATURES, TRACKER_SIGNATURES)
+# The actuator model of the evaluation (csrc/mpc_actuator.hpp), likewise; tests/test_actuator_cpu.py holds this one against the
+# header.
+ACTUATION_SIGNATURES = {name: tuple(tuple(word.split(":")) for word in text.split()) for name, text in dict(
+    mpc_actuate="device:i32 B:i32 reset:i32 params:actuator command:ptr done_prev:ptr applied:ptr state_f64:ptr age:ptr "
+                "ctr:ptr counts:ptr sums:ptr stream:ptr").items()}
+_TABLES = (SIGNATURES, EVALUATION_SIGNATURES, TRACKER_SIGNATURES, ACTUATION_SIGNATURES)
 
 _EXPORTS = ["mpc_version", "mpc_last_error", "mpc_default_config", "mpc_default_config_sized", "mpc_create", "mpc_destroy",
             "mpc_set_reference", "mpc_solve_batch", "mpc_workspace_bytes", "mpc_predict_batch",
             "mpc_reset_env_state", "mpc_reset_env_mask", "mpc_get_env_state", "mpc_get_last_inputs",
             "mpc_ltv_solve_batch", "mpc_ltv_predict_batch", "mpc_env_state_bytes", "mpc_save_env_state",
-            "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_policy_control", "mpc_policy_control_tile", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_interaction_metrics", "mpc_episode_trace", "mpc_perceive", "mpc_track_rows", "mpc_eval_nlp", "mpc_streams_overlap"]
+            "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_policy_control", "mpc_policy_control_tile", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_interaction_metrics", "mpc_episode_trace", "mpc_perceive", "mpc_track_rows", "mpc_actuate", "mpc_eval_nlp", "mpc_streams_overlap"]
 ABI_VERSION = 8          # MPC_ABI_VERSION of include/mpc_mi355x.h this binding is written for
 MAX_OTHERS = 16
 _lib = None
@@ -219,7 +233,7 @@ def _caller(name, sig):
     an eager step makes three such calls: Python binds the keywords to the names itself, and raises the TypeError that
     names the entry point and the missing or unexpected parameter."""
     convert = dict(i32="{0}", u64="{0}", f64="{0}", ptr="None if {0} is None else c_void_p({0}.data_ptr())",
-                   perception="None if {0} is None else byref({0})")
+                   perception="None if {0} is None else byref({0})", actuator="None if {0} is None else byref({0})")
     args = ", ".join("_stream_handle(stream)" if n == "stream" else convert[kind].format(n) for n, kind in sig)
     scope = dict(c_void_p=ctypes.c_void_p, byref=ctypes.byref, _stream_handle=_stream_handle, EngineError=EngineError,
                  load_library=load_library)
@@ -237,10 +251,10 @@ _CALLERS = {name: _caller(name, sig) for table in _TABLES for name, sig in table
 
 def caller(name: str):
     """The handle-less entry point `name` as a function of keywords alone: every one of SIGNATURES[name] (or
-    EVALUATION_SIGNATURES[name], TRACKER_SIGNATURES[name]) and no other (TypeError
+    EVALUATION_SIGNATURES[name], TRACKER_SIGNATURES[name], ACTUATION_SIGNATURES[name]) and no other (TypeError
     naming the entry point and the parameter otherwise, before anything is called).  Python ints and floats pass through;
     a pointer is a torch tensor (its address; a bool tensor's bytes are the uint8 the kernels read) or None; `stream` is a
-    torch stream, its raw handle or None; `params` of mpc_perceive a PerceptionParams.  Enqueue only; EngineError with the
+    torch stream, its raw handle or None; `params` of mpc_perceive a PerceptionParams, of mpc_actuate an ActuatorParams.  Enqueue only; EngineError with the
     library's text when the entry point refuses.  lib: the library, load_library() by default."""
     return _CALLERS[name]
 

@@ -38,9 +38,15 @@ same captured step (mpc_episode_trace) in an order that does not depend on timin
 vehicle that vanishes for a few steps stays in the agent's observation, moved on with its last velocity, the noise is smoothed,
 and every row the agent gets has an identity (`row_slot`), inside the same captured step (mpc_track_rows), or by the same update
 in numpy on the CPU path.
+
+`actuation=` puts an actuator model (csrc/mpc_actuator.hpp, `Actuation`) between the agent and the environment: transport
+delay, lost commands, calibration error, noise, first-order lag, rate limits and saturation.  The environment is handed the
+applied action instead of the command, inside the same captured step (mpc_actuate), or by the same update in numpy on the CPU
+path; every observer's `act` is then the applied action, what the environment was handed.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import time
 from dataclasses import dataclass
@@ -83,6 +89,12 @@ TRACE_MAX_WINDOW = 4096
 # csrc/mpc_tracker.hpp: the planes of `counts`, the slots per environment, the longest coast, row_slot of a row without a slot
 TRACKER_COUNTS = ("measured", "matched", "born", "coasted", "expired", "evicted", "cut")   # mpc_track_rows counts [7][B]
 TRACK_SLOTS, TRACK_MAX_COAST, TRACK_NO_SLOT = 16, 200, 255
+# csrc/mpc_actuator.hpp: the planes of `counts`, the salt of the draws, the ring's length, the longest delay, the planes of
+# `state` that hold what reached the actuator last and what was applied last; the environment's own clamp of the two channels
+# (csrc/mpc_synth_env.hpp::step_ego)
+ACTUATION_COUNTS = ("steps", "held", "rate_limited", "saturated", "nonfinite")             # mpc_actuate counts [5][B]
+ACTUATION_SALT, ACT_RING, ACT_MAX_DELAY, ACT_LAST, ACT_PREV = 0x9FB21C651E98DF25, 8, 7, 8, 9
+ENV_LIMITS = ((-5.0, 5.0), (-math.pi / 4, math.pi / 4))
 
 
 def records_from_planes(rec_i32, rec_f64, names_i32=REC_I32, names_f64=REC_F64, bools=_BOOL) -> dict:
@@ -1005,6 +1017,188 @@ class Tracker:
         return {k: int(c[i]) for i, k in enumerate(TRACKER_COUNTS)}
 
 
+def _pair(name, value):
+    """`value` as the two floats of a per-channel parameter (acceleration, steering)"""
+    try:
+        a, b = value
+        return float(a), float(b)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a pair (acceleration, steering)") from None
+
+
+class Actuation:
+    """What the vehicle makes of the agent's command (csrc/mpc_actuator.hpp states the model step by step), per channel
+    (acceleration m/s^2, steering rad): the command arrives `delay` whole policy steps late (0..7; zero until then), is lost
+    with probability `p_hold` (the previous one is held, both channels together), scaled and shifted by `gain` and `offset`,
+    disturbed by bounded noise of standard deviation `sigma`, followed with a first-order lag of time constant `tau` [s]
+    (alpha = dt / (tau + dt), formed once here; tau = 0 gives exactly 1), changed by at most `rate` per second, and clamped to
+    `limits`: None for (-inf, +inf) on both channels, "env" for the environment's own clamp (+-5 m/s^2, +-pi/4), or
+    ((lo, hi), (lo, hi)).  The default of every parameter switches it off: the applied action is then the command bit for bit.
+    The draws are keyed by (seed, env_offset + b, launches since the reset), so they do not depend on the batch size or on
+    how the environments are sharded.  The parameters are fixed at construction.
+
+    `apply(command, out, done_prev=None)` fills `out` [B, 2] f64 (it may be `command`) and returns it; done_prev [B]: the
+    environments whose episode ended on the previous step (their delay line, held command and lag state are cleared before the
+    command is read).  `reset()` clears everything.  `state` [10, B, 2] f64 holds the last eight commands, what reached the
+    actuator last and what was applied last, `age` [B] i32 the commands of the episode, `ctr` [B] i64 the launches, `counts`
+    [5, B] i64 the steps of each of ACTUATION_COUNTS, `sums` [2, B, 2] f64 the sum and the maximum of |applied - command|.
+    Backend "hip" is the kernel (mpc_actuate, enqueue only, capturable); backend "torch" is the same update in numpy for the
+    CPU environment, the same bits."""
+
+    def __init__(self, B: int, device, backend: str = "torch", dt: float = 0.1, delay: int = 0, p_hold: float = 0.0,
+                 gain=(1.0, 1.0), offset=(0.0, 0.0), sigma=(0.0, 0.0), tau=(0.0, 0.0), rate=(math.inf, math.inf),
+                 limits=None, seed: int = 0, env_offset: int = 0):
+        if backend not in ("hip", "torch"):
+            raise ValueError("backend must be 'hip' or 'torch'")
+        if int(B) < 0:
+            raise ValueError("B must be >= 0")
+        if not float(dt) > 0.0:
+            raise ValueError("dt must be > 0")
+        if int(delay) != delay or not 0 <= int(delay) <= ACT_MAX_DELAY:
+            raise ValueError(f"delay must be an integer 0..{ACT_MAX_DELAY}")
+        if not 0.0 <= float(p_hold) <= 1.0:
+            raise ValueError("p_hold must be in [0, 1]")
+        gain, offset, sigma, tau, rate = (_pair(n, v) for n, v in (("gain", gain), ("offset", offset), ("sigma", sigma),
+                                                                   ("tau", tau), ("rate", rate)))
+        if limits is None:
+            limits = ((-math.inf, math.inf), (-math.inf, math.inf))
+        elif isinstance(limits, str):
+            if limits != "env":
+                raise ValueError("limits must be None, 'env' or ((lo, hi), (lo, hi))")
+            limits = ENV_LIMITS
+        limits = tuple(_pair("limits", v) for v in _pair_of_pairs(limits))
+        for c in (0, 1):
+            if not (math.isfinite(gain[c]) and math.isfinite(offset[c])):
+                raise ValueError("gain and offset must be finite")
+            if not (sigma[c] >= 0.0 and math.isfinite(sigma[c])):
+                raise ValueError("sigma must be >= 0 and finite")
+            if not (tau[c] >= 0.0 and math.isfinite(tau[c])):
+                raise ValueError("tau must be >= 0 and finite")
+            if not rate[c] > 0.0:
+                raise ValueError("rate must be > 0 (inf: no limit)")
+            if not limits[c][0] <= limits[c][1]:
+                raise ValueError("limits must be lo <= hi")
+        if not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("seed must fit 64 unsigned bits")
+        self.B, self.device, self.backend = int(B), torch.device(device), backend
+        self.dt, self.delay, self.p_hold = float(dt), int(delay), float(p_hold)
+        self.gain, self.offset, self.sigma, self.tau, self.rate, self.limits = gain, offset, sigma, tau, rate, limits
+        self.alpha = tuple(self.dt / (t + self.dt) for t in tau)
+        if not all(0.0 < a <= 1.0 for a in self.alpha):
+            raise ValueError("tau is too large for dt: alpha = dt / (tau + dt) must be in (0, 1]")
+        self.seed, self.env_offset = int(seed), int(env_offset)
+        z = lambda *s, dt: torch.zeros(s, dtype=dt, device=self.device)
+        self.state, self.sums = z(ACT_PREV + 1, self.B, 2, dt=torch.float64), z(2, self.B, 2, dt=torch.float64)
+        self.age, self.ctr = z(self.B, dt=torch.int32), z(self.B, dt=torch.int64)
+        self.counts = z(len(ACTUATION_COUNTS), self.B, dt=torch.int64)
+        pair = lambda v: (ctypes.c_double * 2)(*v)
+        self._params = _engine.ActuatorParams(
+            struct_size=ctypes.sizeof(_engine.ActuatorParams), delay=self.delay, env_offset=self.env_offset, reserved=0,
+            dt=self.dt, p_hold=self.p_hold, gain=pair(gain), offset=pair(offset), sigma=pair(sigma), alpha=pair(self.alpha),
+            rate=pair(rate), lo=pair((limits[0][0], limits[1][0])), hi=pair((limits[0][1], limits[1][1])), seed=self.seed)
+
+    @property
+    def config(self) -> dict:
+        """The keyword arguments that make an Actuation with the same model and the same draws."""
+        return dict(dt=self.dt, delay=self.delay, p_hold=self.p_hold, gain=self.gain, offset=self.offset, sigma=self.sigma,
+                    tau=self.tau, rate=self.rate, limits=self.limits, seed=self.seed, env_offset=self.env_offset)
+
+    def _launch(self, reset, command=None, done_prev=None, applied=None):
+        _engine.caller("mpc_actuate")(
+            device=self.device.index, B=self.B, reset=reset, params=self._params, command=command, done_prev=done_prev,
+            applied=applied, state_f64=self.state, age=self.age, ctr=self.ctr, counts=self.counts, sums=self.sums,
+            stream=_engine.current_stream(self.device))
+
+    def reset(self) -> None:
+        """Everything starts anew: the delay line, the held command, the lag state, the draw counter, the counts, the sums."""
+        if self.backend == "hip":
+            self._launch(1)
+        else:
+            for t in (self.state, self.sums, self.age, self.ctr, self.counts):
+                t.zero_()
+
+    def apply(self, command, out, done_prev=None):
+        B, dev = self.B, self.device
+        _check(command, "command", (B, 2), torch.float64, dev)
+        _check(out, "out", (B, 2), torch.float64, dev)
+        if done_prev is not None:
+            done_prev = _check(done_prev, "done_prev", (B,), torch.uint8, dev)
+        if self.backend == "torch":
+            applied = self._numpy_apply(command.cpu().numpy(), None if done_prev is None else done_prev.cpu().numpy())
+            out.copy_(torch.from_numpy(applied))
+        else:
+            self._launch(0, command, done_prev, out)
+        return out
+
+    def _numpy_apply(self, cmd, done_prev):
+        """csrc/mpc_actuator.hpp over the batch: every statement acts on all environments, the channels one after the other."""
+        B = self.B
+        state, sums, age, ctr, counts = (t.cpu().numpy() for t in (self.state, self.sums, self.age, self.ctr, self.counts))
+        env = np.arange(B)
+        draws = lambda slots: _u01(self.seed ^ ACTUATION_SALT, self.env_offset + env, ctr, slots)
+        clear = np.zeros(B, bool) if done_prev is None else done_prev != 0
+        age[clear] = 0                                                             # 1
+        state[:, clear] = 0.0
+        with np.errstate(invalid="ignore", over="ignore"):
+            finite = (cmd - cmd) == 0.0                                            # 2
+            u = np.where(finite, cmd, 0.0)
+            state[age & (ACT_RING - 1), env] = u                                   # 3
+            delayed = np.where((age >= self.delay)[:, None], state[(age - self.delay) & (ACT_RING - 1), env], 0.0)
+            held = draws(np.arange(1))[:, 0] < self.p_hold if self.p_hold > 0.0 else np.zeros(B, bool)     # 4
+            delayed = np.where(held[:, None], state[ACT_LAST], delayed)
+            state[ACT_LAST] = delayed
+            prev = state[ACT_PREV].copy()
+            y, limited, clipped = np.empty((B, 2)), np.zeros((B, 2), bool), np.zeros((B, 2), bool)
+            for c in (0, 1):
+                v, p = delayed[:, c], prev[:, c]
+                if not (self.gain[c] == 1.0 and self.offset[c] == 0.0):            # 5
+                    v = self.gain[c] * v + self.offset[c]
+                if self.sigma[c] != 0.0:
+                    d = draws(1 + 4 * c + np.arange(4))
+                    v = v + self.sigma[c] * (((d[:, 0] + d[:, 1]) + (d[:, 2] + d[:, 3]) - 2.0) * UNIT_SCALE)
+                yc = v
+                if self.alpha[c] != 1.0:                                           # 6
+                    yc = p + self.alpha[c] * (v - p)
+                if math.isfinite(self.rate[c]):                                    # 7
+                    m, d = self.rate[c] * self.dt, yc - p
+                    yc = np.where(d > m, p + m, np.where(d < -m, p - m, yc))
+                    limited[:, c] = (d > m) | (d < -m)
+                lo, hi = self.limits[c]                                            # 8
+                below = yc < lo
+                yc = np.where(below, lo, yc)
+                above = yc > hi
+                y[:, c], clipped[:, c] = np.where(above, hi, yc), below | above
+            dev = np.abs(y - u)                                                    # 9
+        state[ACT_PREV] = y
+        sums[0] += dev
+        sums[1] = np.where(dev > sums[1], dev, sums[1])
+        age += 1
+        ctr += 1
+        for k, n in enumerate((np.ones(B, bool), held, limited.any(axis=1), clipped.any(axis=1), ~finite.all(axis=1))):
+            counts[k] += n
+        _write_back(((self.state, state), (self.sums, sums), (self.age, age), (self.ctr, ctr), (self.counts, counts)))
+        return y
+
+    def totals(self) -> dict:
+        """Since the reset, summed over the environments: steps, and the steps on which the command was held, the rate limit
+        acted, the saturation acted, the command was not finite; mean_abs_dev and max_abs_dev (2,): the mean over the steps
+        and the maximum of |applied - command| per channel."""
+        c = self.counts.sum(dim=1).cpu().numpy()
+        s = self.sums.cpu().numpy()
+        out = {k: int(c[i]) for i, k in enumerate(ACTUATION_COUNTS)}
+        out["mean_abs_dev"] = s[0].sum(axis=0) / max(out["steps"], 1)
+        out["max_abs_dev"] = s[1].max(axis=0, initial=0.0)
+        return out
+
+
+def _pair_of_pairs(limits):
+    try:
+        a, b = limits
+        return a, b
+    except (TypeError, ValueError):
+        raise ValueError("limits must be None, 'env' or ((lo, hi), (lo, hi))") from None
+
+
 def _keep_bits(keep) -> int:
     names = (keep,) if isinstance(keep, str) else tuple(keep)
     bits = 0
@@ -1075,9 +1269,10 @@ class EpisodeTrace:
     chronological order, to the next free of `capacity` slots, ordered by (launch on which it ended, environment); one that
     finds the store full is counted as dropped.  keep: a name or an iterable of names from collision, truncated, success,
     unsolved, all; "failed" is collision | truncated.  seen=True also records what the agent acted on (with a perception
-    model).  `update` after the environment's step is the kernel (backend "hip": enqueue only, capturable) or the same update
-    in numpy (backend "torch", for the CPU environment); both give the same bytes.  Memory is bounded by B, window and
-    capacity alone (`nbytes`)."""
+    model).  The `action` plane is what the environment was handed: in an evaluation with an actuator model (`Actuation`)
+    the applied action, not the agent's command, so a trace can be replayed against the environment.  `update` after the
+    environment's step is the kernel (backend "hip": enqueue only, capturable) or the same update in numpy (backend "torch",
+    for the CPU environment); both give the same bytes.  Memory is bounded by B, window and capacity alone (`nbytes`)."""
 
     def __init__(self, B: int, Q: int, device, backend: str = "torch", R: int = VEHICLES_COUNT, keep="failed",
                  capacity: int = 64, window: int = EPISODE_STEPS, seen: bool = False, env_offset: int = 0):
@@ -1237,7 +1432,9 @@ class EvalResult:
     records (dict of numpy arrays [B, Q], keys INTERACT_I32 + INTERACT_F64, the same slots) when the evaluation ran with
     interaction=True, else None; traces: the episodes the trace recorder kept (`EpisodeTraces`) when the evaluation ran with
     trace=, else None; tracker: the totals of the tracker (`Tracker.totals()`: measured, matched, born, coasted, expired,
-    evicted, cut over the whole evaluation, idle steps included) when the evaluation ran with one, else None."""
+    evicted, cut over the whole evaluation, idle steps included) when the evaluation ran with one, else None; actuation: the
+    totals of the actuator model (`Actuation.totals()`: steps, held, rate_limited, saturated, nonfinite, mean_abs_dev and
+    max_abs_dev per channel, idle steps included) when the evaluation ran with one, else None."""
     records: dict
     dt: float
     steps: int
@@ -1248,6 +1445,7 @@ class EvalResult:
     interaction: dict | None = None
     traces: EpisodeTraces | None = None
     tracker: dict | None = None
+    actuation: dict | None = None
 
     @property
     def travel_time(self):
@@ -1268,7 +1466,10 @@ class EvalResult:
         over episodes, speed_deficit_per_episode [m/s], conflicts_per_episode, pet_critical_frac and ego_first_frac (of the
         conflicts; 0 when there is none) and min_pet_p05 (the 5th percentile of min_pet over the episodes with a conflict;
         inf when there is none).  With a tracker also coasted_frac: the output rows that were coasted, as a share of all
-        output rows, coasted / (matched + born + coasted) (0 when there was none)."""
+        output rows, coasted / (matched + born + coasted) (0 when there was none).  With an actuator model also act_held_frac,
+        act_rate_limited_frac and act_saturated_frac (the steps on which a command was lost, the rate limit acted, the
+        saturation acted, over all steps) and act_mean_abs_dev_accel [m/s^2], act_mean_abs_dev_steer [rad]: the mean of
+        |applied - command| per channel."""
         out = self._base_summary()
         if self.drive is not None:
             out.update(self._drive_summary())
@@ -1280,6 +1481,10 @@ class EvalResult:
         if self.tracker is not None:
             t = self.tracker
             out["coasted_frac"] = t["coasted"] / max(t["matched"] + t["born"] + t["coasted"], 1)
+        if self.actuation is not None:
+            a = self.actuation
+            out.update({f"act_{k}_frac": a[k] / max(a["steps"], 1) for k in ("held", "rate_limited", "saturated")})
+            out.update(act_mean_abs_dev_accel=float(a["mean_abs_dev"][0]), act_mean_abs_dev_steer=float(a["mean_abs_dev"][1]))
         return out
 
     def _interaction_summary(self) -> dict:
@@ -1343,7 +1548,7 @@ def _instance(cls, given, defaults: dict, *args):
 def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = False, reset_mpc_on_done: bool = False,
                    use_graph: bool | None = None, poll_every: int = 16, seed: int = 0, on_step=None,
                    metrics: bool = False, perception=None, interaction: bool = False, trace=None,
-                   tracker=None) -> EvalResult:
+                   tracker=None, actuation=None) -> EvalResult:
     """Run `agent` in closed loop on the B environments of `env` (a SyntheticIntersectionEnv) until each environment has
     finished `episodes_per_env` episodes; returns their records.
 
@@ -1377,6 +1582,14 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     inside the step with the step's `done` (so inside the captured graph).  on_step's dict then also holds obs, seen (the
     tracker's output, what the agent gets), row_slot and row_miss; the trace recorder's `seen` is the tracker's output;
     EvalResult.tracker holds the totals.  The accounting and every metric keep reading the true scene.  None: nothing changes.
+    actuation: an `Actuation` for this environment's batch, or a dict of its keyword arguments (dt and env_offset default to
+    the environment's): the environment is handed `actuation.apply(command)` instead of the agent's command, launched between
+    the agent's action and the environment's step (so inside the captured graph) with the `done` of the previous step, and
+    reset where the observers get their reset frame, so the graph's warm-up and capture steps leave no trace.  Every
+    observer's `act` is then the applied action, what the environment was handed - the drive metrics' `action`, and the
+    `action` plane of a trace, which can therefore be replayed against the environment; on_step's dict then also holds act
+    (applied) and command (the agent's output).  The agent's own memory of its last action stays its command.
+    EvalResult.actuation holds the totals.  None: no launch, no buffer, nothing changes.
     Every episode ends by EPISODE_STEPS (200) steps, so Q * 200 steps bound the loop; RuntimeError if the episodes are not
     all recorded by then."""
     Q = int(episodes_per_env)
@@ -1407,6 +1620,12 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     tracker = _instance(Tracker, tracker, dict(R=VEHICLES_COUNT, dt=float(env.dt)), B, dev, backend)
     if tracker is not None and (tracker.B != B or tracker.R != VEHICLES_COUNT or tracker.device != dev):
         raise ValueError(f"tracker must be built for {B} environments of {VEHICLES_COUNT} rows on {dev}")
+    actuation = _instance(Actuation, actuation, dict(dt=float(env.dt), env_offset=offset), B, dev, backend)
+    if actuation is not None and (actuation.B != B or actuation.device != dev):
+        raise ValueError(f"actuation must be built for {B} environments on {dev}")
+    # with an actuator model: what the environment is handed, and the `done` of the previous step (zero after the reset)
+    applied = torch.zeros((B, 2), dtype=torch.float64, device=dev) if actuation is not None else None
+    ended = torch.zeros(B, dtype=torch.uint8, device=dev) if actuation is not None else None
     filtered = perception is not None or tracker is not None       # the agent acts on something other than the true scene
     sensed = torch.zeros_like(obs) if perception is not None and tracker is not None else None    # between the two
     trace = _instance(EpisodeTrace, trace, dict(R=VEHICLES_COUNT, env_offset=offset, seen=filtered), B, Q, dev, backend)
@@ -1427,7 +1646,8 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     # what on_step is shown of a frame: the accounting's inputs; with metrics=True also the scenes and the action; with a
     # perception model also the true observation, what the agent gets next and (below) the class of every row
     shown = ("ego", "done", "truncated", "crashed", "arrived", "reward", "status", "iters") + \
-        (("terminal_obs", "obs", "act") if metrics else ()) + (("obs", "seen") if filtered else ())
+        (("terminal_obs", "obs", "act") if metrics else ()) + (("obs", "seen") if filtered else ()) + \
+        (("act", "command") if actuation is not None else ())
 
     def show(frame, **first):
         first.update((k, frame[k]) for k in shown if k in frame)
@@ -1449,18 +1669,23 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
 
     def step():
         out = agent.act_batch_torch(obs, **kw)
-        new_obs, reward, done, info = env.step(out["act"])
+        act = out["act"] if actuation is None else actuation.apply(out["act"], applied, done_prev=ended)
+        new_obs, reward, done, info = env.step(act)
         if reset_mpc_on_done and eng is not None:
             eng.reset_env_mask_torch(_u8(done))
         elif warm:                    # a new episode must not start from the old one's plan
             eng.reset_env_mask_torch(_u8(done), warm_only=True)
-        frame = dict(env=env, ego=env.ego, terminal_obs=info["terminal_obs"], obs=new_obs, act=out["act"], reward=reward,
+        frame = dict(env=env, ego=env.ego, terminal_obs=info["terminal_obs"], obs=new_obs, act=act, reward=reward,
                      done=done, truncated=info["truncated"], crashed=info["crashed"], arrived=info["arrived"],
                      status=out["status"], iters=out["iters"], step=out.get("step"))
         if filtered:
             frame["seen"] = obs       # still what the agent acted on while the observers run; what it gets next after them
+        if actuation is not None:
+            frame["command"] = out["act"]
         for o in observers:
             o.observe(frame)
+        if actuation is not None:
+            ended.copy_(done)
         sense(new_obs, done=done)
         return out, frame
 
@@ -1507,6 +1732,9 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
         frame["seen"] = obs
     for o in observers:
         o.observe(frame, reset=True)
+    if actuation is not None:
+        actuation.reset()
+        ended.zero_()
     if on_step is not None:
         show(frame, reset=True)
     target, max_steps = B * Q, Q * EPISODE_STEPS
@@ -1536,11 +1764,12 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
                       perception=None if perception is None else perception.totals(),
                       interaction=None if inter is None else inter.records(),
                       traces=None if trace is None else trace.traces(),
-                      tracker=None if tracker is None else tracker.totals())
+                      tracker=None if tracker is None else tracker.totals(),
+                      actuation=None if actuation is None else actuation.totals())
 
 
 def compare(agents: dict, make_env, episodes_per_env: int = 1, metrics: bool = False, perception=None,
-            interaction: bool = False, trace=None, results=None, tracker=None, **kw) -> dict:
+            interaction: bool = False, trace=None, results=None, tracker=None, actuation=None, **kw) -> dict:
     """Evaluate every agent on a fresh environment from make_env() (same seed: the HIP environment keys its draws by seed and
     environment id, so every agent meets the same initial episodes) -> {name: summary}; metrics=True adds the drive metrics'
     keys to every summary.  perception (a dict of `Perception`'s keyword arguments, or a Perception whose configuration is
@@ -1548,14 +1777,16 @@ def compare(agents: dict, make_env, episodes_per_env: int = 1, metrics: bool = F
     interaction=True adds the interaction metrics' keys (the environments must have traffic="idm").  trace (a dict of
     `EpisodeTrace`'s keyword arguments, or an EpisodeTrace whose settings are copied): every agent gets a fresh recorder with
     the same settings.  tracker (a dict of `Tracker`'s keyword arguments, or a Tracker whose configuration is copied): every
-    agent gets a fresh tracker.  results: a dict that receives every agent's EvalResult by name (its traces, its records)."""
-    perception, trace, tracker = (x.config if isinstance(x, (Perception, EpisodeTrace, Tracker)) else x
-                                  for x in (perception, trace, tracker))
+    agent gets a fresh tracker.  actuation (a dict of `Actuation`'s keyword arguments, or an Actuation whose configuration is
+    copied): every agent gets a fresh actuator model with the same seed, hence the same draws on the same steps.  results: a dict that receives every agent's EvalResult by name (its traces, its records)."""
+    perception, trace, tracker, actuation = (x.config if isinstance(x, (Perception, EpisodeTrace, Tracker, Actuation)) else x
+                                             for x in (perception, trace, tracker, actuation))
     fresh = lambda settings: None if settings is None else dict(settings)
     out = {}
     for name, agent in agents.items():
         res = evaluate_agent(agent, make_env(), episodes_per_env, metrics=metrics, perception=fresh(perception),
-                             interaction=interaction, trace=fresh(trace), tracker=fresh(tracker), **kw)
+                             interaction=interaction, trace=fresh(trace), tracker=fresh(tracker),
+                             actuation=fresh(actuation), **kw)
         if results is not None:
             results[name] = res
         out[name] = res.summary()

@@ -10,6 +10,10 @@ in the JSON line, which then also holds the share of present rows that were seen
 observation; evaluate.Tracker): a vehicle that vanishes for up to --track-coast steps stays in the observation at its last
 velocity, measurements within --track-gate metres of a track are smoothed by the two gains.  Any of them switches it on; they
 are echoed in the JSON line, which then also holds coasted_frac, the share of the agent's rows that were coasted.
+--act-delay, --act-tau-*, --act-rate-*, --act-sigma-*, --act-p-hold, --act-steer-offset and --act-limits put an actuator model
+between every agent and the environment (evaluate.Actuation: transport delay in policy steps, first-order lag, rate limit,
+noise, lost commands, a steering offset, saturation); any of them switches it on; they are echoed in the JSON line, which then
+also holds the act_* shares and mean deviations.  tools/robustness_sweep.py runs the comparison over a grid of them.
 
 Agents: pure MPC with the collision cost off and on, the iterative-linear (LTV) agent, and MPC-RL - an SB3 `.zip` given with
 --mpcrl, or with --fixture the v0 PPO (gSDE) policy rebuilt from tests/golden/sb3_policies.npz.  --ppo PATH adds the reference's
@@ -20,6 +24,7 @@ in the layout ActorCritic.save_sb3 writes; --ppo-random adds it with a seeded un
   python tools/compare_models.py --metrics --traffic idm --envs 256 --fixture
   python tools/compare_models.py --metrics --traffic idm --occlusion buildings --range 60 --sigma-pos 0.2
   python tools/compare_models.py --metrics --traffic idm --occlusion buildings --dropout 0.05 --track-coast 10
+  python tools/compare_models.py --metrics --traffic idm --act-delay 2 --act-tau-steer 0.2 --act-limits env
   python tools/compare_models.py --metrics --traffic idm --interaction --envs 256
   python tools/compare_models.py --envs 256 --fixture --ppo baseline.zip
   python tools/compare_models.py --traffic idm --trace failed --trace-window 50 --trace-dir out
@@ -38,6 +43,75 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+
+class Env:          # what the agents read of the reference's highway-env configuration
+    config = {"simulation_frequency": 30, "policy_frequency": 10, "observation": {"vehicles_count": 10}}
+
+
+def build_agents(dev, seed=0, mpcrl=None, fixture=False, ppo=None, ppo_random=False):
+    """-> ({name: agent}, a TemporaryDirectory to clean up or None): pure MPC without and with the collision cost, the
+    iterative-linear agent, and where asked for MPC-RL and the end-to-end PPO baseline"""
+    import torch
+    from mpc_rl_for_avs_amd import rollout
+    from mpc_rl_for_avs_amd.engine import MPCEngine
+    from mpc_rl_for_avs_amd.pure_mpc import PureMPC_Agent
+    from mpc_rl_for_avs_amd.pure_mpc_linear import IterativeLinearMPC_Agent
+    cfg = dict(horizon=20, render=False, weight_speed=1, weight_control=1, weight_input_diff=1)
+    agents = {"pure_mpc": PureMPC_Agent(Env(), dict(cfg), collision_cost=False),
+              "pure_mpc_collision": PureMPC_Agent(Env(), dict(cfg), collision_cost=True),
+              "ltv": IterativeLinearMPC_Agent(Env(), dict(cfg))}
+    path, tmp = mpcrl, None
+    if fixture:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import sde_host
+        tmp = tempfile.TemporaryDirectory()
+        path = sde_host.sb3_zip(tmp.name, "ppo_v0")
+    if path:
+        agents["mpcrl"], _ = rollout.MPCRLAgent.from_sb3(path, MPCEngine(horizon=20, device=0), device=dev)
+    if ppo:
+        agents["ppo"], _ = rollout.PPOAgent.from_sb3(ppo, MPCEngine(horizon=20, device=0), device=dev)
+    elif ppo_random:
+        torch.manual_seed(seed)
+        agents["ppo"] = rollout.PPOAgent(rollout.ActorCritic(2).to(dev), MPCEngine(horizon=20, device=0))
+    return agents, tmp
+
+
+def add_agent_flags(ap):
+    src = ap.add_mutually_exclusive_group()
+    src.add_argument("--mpcrl", help="an SB3 checkpoint (.zip) of the reference's MPC-RL agent")
+    src.add_argument("--fixture", action="store_true", help="MPC-RL: the v0 PPO policy of tests/golden/sb3_policies.npz")
+    base = ap.add_mutually_exclusive_group()
+    base.add_argument("--ppo", metavar="PATH", help="the end-to-end PPO baseline: a checkpoint (.zip) as ActorCritic.save_sb3 writes it")
+    base.add_argument("--ppo-random", action="store_true", help="the end-to-end PPO baseline with an untrained policy seeded by --seed")
+
+
+def actuation_of(args):
+    """The --act-* flags as evaluate.Actuation's keyword arguments; None when none was given: no actuator model, the launches
+    of before"""
+    given = dict(delay=args.act_delay, p_hold=args.act_p_hold, limits=args.act_limits,
+                 tau=None if args.act_tau_accel is None and args.act_tau_steer is None
+                 else (args.act_tau_accel or 0.0, args.act_tau_steer or 0.0),
+                 rate=None if args.act_rate_accel is None and args.act_rate_steer is None
+                 else (args.act_rate_accel or float("inf"), args.act_rate_steer or float("inf")),
+                 sigma=None if args.act_sigma_accel is None and args.act_sigma_steer is None
+                 else (args.act_sigma_accel or 0.0, args.act_sigma_steer or 0.0),
+                 offset=None if args.act_steer_offset is None else (0.0, args.act_steer_offset))
+    given = {k: v for k, v in given.items() if v is not None}
+    return dict(given, seed=args.seed) if given else None
+
+
+def add_actuation_flags(ap):
+    ap.add_argument("--act-delay", type=int, metavar="N", help="actuator: transport delay in whole policy steps (0..7)")
+    ap.add_argument("--act-tau-accel", type=float, metavar="S", help="actuator: time constant of the acceleration's lag [s]")
+    ap.add_argument("--act-tau-steer", type=float, metavar="S", help="actuator: time constant of the steering's lag [s]")
+    ap.add_argument("--act-rate-accel", type=float, metavar="R", help="actuator: largest change of the acceleration [m/s^3]")
+    ap.add_argument("--act-rate-steer", type=float, metavar="R", help="actuator: largest steering rate [rad/s]")
+    ap.add_argument("--act-sigma-accel", type=float, metavar="S", help="actuator: noise on the acceleration [m/s^2]")
+    ap.add_argument("--act-sigma-steer", type=float, metavar="S", help="actuator: noise on the steering [rad]")
+    ap.add_argument("--act-p-hold", type=float, metavar="P", help="actuator: probability that a step's command is lost")
+    ap.add_argument("--act-steer-offset", type=float, metavar="D", help="actuator: steering calibration offset [rad]")
+    ap.add_argument("--act-limits", choices=("env",), help="actuator: saturate at the environment's clamp (+-5 m/s^2, +-pi/4)")
 
 
 def main():
@@ -64,18 +138,14 @@ def main():
     ap.add_argument("--track-gate", type=float, metavar="G", help="tracker: association gate [m] (default 3)")
     ap.add_argument("--track-alpha-pos", type=float, metavar="A", help="tracker: gain on the measured position, (0, 1]")
     ap.add_argument("--track-alpha-vel", type=float, metavar="A", help="tracker: gain on the measured velocity, (0, 1]")
-    src = ap.add_mutually_exclusive_group()
-    src.add_argument("--mpcrl", help="an SB3 checkpoint (.zip) of the reference's MPC-RL agent")
-    src.add_argument("--fixture", action="store_true", help="MPC-RL: the v0 PPO policy of tests/golden/sb3_policies.npz")
+    add_actuation_flags(ap)
+    add_agent_flags(ap)
     ap.add_argument("--trace", metavar="KEEP", help="keep the step-by-step record of episodes (evaluate.EpisodeTrace): failed, all, "
                                                      "or a comma-separated list of collision, truncated, success, unsolved")
     ap.add_argument("--trace-window", type=int, default=200, metavar="W", help="--trace: the last W steps of each kept episode")
     ap.add_argument("--trace-capacity", type=int, default=64, metavar="C", help="--trace: at most C episodes per model")
     ap.add_argument("--trace-dir", default="traces", metavar="DIR", help="--trace: one DIR/<model>.npz per model "
                                                                          "(tools/show_episode.py prints them)")
-    base = ap.add_mutually_exclusive_group()
-    base.add_argument("--ppo", metavar="PATH", help="the end-to-end PPO baseline: a checkpoint (.zip) as ActorCritic.save_sb3 writes it")
-    base.add_argument("--ppo-random", action="store_true", help="the end-to-end PPO baseline with an untrained policy seeded by --seed")
     args = ap.parse_args()
     if args.interaction and args.traffic != "idm":
         ap.error("--interaction requires --traffic idm")
@@ -84,32 +154,9 @@ def main():
 
     import torch
     from mpc_rl_for_avs_amd import evaluate, rollout
-    from mpc_rl_for_avs_amd.engine import MPCEngine
-    from mpc_rl_for_avs_amd.pure_mpc import PureMPC_Agent
-    from mpc_rl_for_avs_amd.pure_mpc_linear import IterativeLinearMPC_Agent
 
-    class Env:          # what the agents read of the reference's highway-env configuration
-        config = {"simulation_frequency": 30, "policy_frequency": 10, "observation": {"vehicles_count": 10}}
-
-    cfg = dict(horizon=20, render=False, weight_speed=1, weight_control=1, weight_input_diff=1)
     dev = torch.device("cuda", 0)
-    agents = {"pure_mpc": PureMPC_Agent(Env(), dict(cfg), collision_cost=False),
-              "pure_mpc_collision": PureMPC_Agent(Env(), dict(cfg), collision_cost=True),
-              "ltv": IterativeLinearMPC_Agent(Env(), dict(cfg))}
-    path = args.mpcrl
-    tmp = None
-    if args.fixture:
-        sys.path.insert(0, os.path.join(ROOT, "tests"))
-        import sde_host
-        tmp = tempfile.TemporaryDirectory()
-        path = sde_host.sb3_zip(tmp.name, "ppo_v0")
-    if path:
-        agents["mpcrl"], _ = rollout.MPCRLAgent.from_sb3(path, MPCEngine(horizon=20, device=0), device=dev)
-    if args.ppo:
-        agents["ppo"], _ = rollout.PPOAgent.from_sb3(args.ppo, MPCEngine(horizon=20, device=0), device=dev)
-    elif args.ppo_random:
-        torch.manual_seed(args.seed)
-        agents["ppo"] = rollout.PPOAgent(rollout.ActorCritic(2).to(dev), MPCEngine(horizon=20, device=0))
+    agents, tmp = build_agents(dev, args.seed, args.mpcrl, args.fixture, args.ppo, args.ppo_random)
     make_env = lambda: rollout.SyntheticIntersectionEnv(args.envs, device=dev, seed=args.seed, n_others=4,
                                                          traffic=args.traffic)
     flags = dict(range=args.range, occlusion=args.occlusion, dropout=args.dropout,
@@ -125,6 +172,9 @@ def main():
     tracker = {k: v for k, v in given.items() if v is not None} or None        # no flag given: no tracker, the launches of before
     if tracker is not None:
         echo["tracker"] = {k: finite(v) for k, v in evaluate.Tracker(0, dev, "hip", **tracker).config.items() if k in given}
+    actuation = actuation_of(args)
+    if actuation is not None:
+        echo["actuation"] = {k: [finite(x) for x in v] if isinstance(v, tuple) else v for k, v in actuation.items()}
     trace = None
     if args.trace:
         keep = args.trace.split(",") if "," in args.trace else args.trace
@@ -134,7 +184,8 @@ def main():
         results = {}
         s = evaluate.compare({name: agent}, make_env, args.episodes_per_env, deterministic=args.deterministic,
                              seed=args.seed, metrics=args.metrics, perception=perception,
-                             interaction=args.interaction, trace=trace, tracker=tracker, results=results)[name]
+                             interaction=args.interaction, trace=trace, tracker=tracker, actuation=actuation,
+                             results=results)[name]
         s = {k: finite(v) for k, v in s.items()}
         if trace is not None:
             path = os.path.join(args.trace_dir, f"{name}.npz")

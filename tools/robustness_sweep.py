@@ -1,0 +1,71 @@
+"""How much latency and actuator lag each model tolerates: the model comparison (evaluate.compare, the agents of
+tools/compare_models.py) over a grid of actuator models (evaluate.Actuation) - by default a transport delay of 0, 1, 2, 3
+policy steps without lag, then a steering lag of time constant 0, 0.2, 0.5 s without delay - on the same episodes: the same
+environment seed in every cell, every agent a fresh environment and a fresh actuator.  Prints one table per model (success
+rate, collision rate, mean steps per cell) and one JSON line with every cell's numbers.
+
+  python tools/robustness_sweep.py --envs 256 --traffic idm --fixture
+  python tools/robustness_sweep.py --delays 0 2 4 6 --taus 0 1.0 --act-limits env
+
+One run of --envs episodes per cell: a rate carries the sampling noise of that many episodes (at 256, a standard error of up
+to 3.1 points), so differences of a few points between cells are within it.
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tools")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def main():
+    import compare_models
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--envs", type=int, default=256)
+    ap.add_argument("--episodes-per-env", type=int, default=1)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--deterministic", action="store_true", help="MPC-RL acts with the policy's mean")
+    ap.add_argument("--traffic", default="idm", choices=("constant", "idm"))
+    ap.add_argument("--delays", type=int, nargs="*", default=[0, 1, 2, 3], metavar="N",
+                    help="transport delays in policy steps, each without lag")
+    ap.add_argument("--taus", type=float, nargs="*", default=[0.0, 0.2, 0.5], metavar="S",
+                    help="steering time constants [s], each without delay")
+    ap.add_argument("--act-limits", choices=("env",), help="saturate at the environment's clamp in every cell")
+    compare_models.add_agent_flags(ap)
+    args = ap.parse_args()
+
+    import torch
+    from mpc_rl_for_avs_amd import evaluate, rollout
+
+    dev = torch.device("cuda", 0)
+    agents, tmp = compare_models.build_agents(dev, args.seed, args.mpcrl, args.fixture, args.ppo, args.ppo_random)
+    make_env = lambda: rollout.SyntheticIntersectionEnv(args.envs, device=dev, seed=args.seed, n_others=4,
+                                                         traffic=args.traffic)
+    cells = [(d, 0.0) for d in args.delays] + [(0, t) for t in args.taus if (0, t) not in [(d, 0.0) for d in args.delays]]
+    table = {name: [] for name in agents}
+    for delay, tau in cells:
+        model = dict(delay=delay, tau=(0.0, tau), limits=args.act_limits, seed=args.seed)
+        out = evaluate.compare(agents, make_env, args.episodes_per_env, deterministic=args.deterministic, seed=args.seed,
+                               actuation=model)
+        for name, s in out.items():
+            table[name].append(dict(delay=delay, tau_steer=tau, success_rate=s["success_rate"],
+                                    collision_rate=s["collision_rate"], avg_steps=s["avg_steps"],
+                                    act_mean_abs_dev_accel=s["act_mean_abs_dev_accel"],
+                                    act_mean_abs_dev_steer=s["act_mean_abs_dev_steer"]))
+    for name, rows in table.items():
+        print(f"{name}: {args.envs * args.episodes_per_env} episodes per cell, traffic {args.traffic}, seed {args.seed}")
+        print("  delay [steps]  tau_steer [s]  success %  collision %  mean steps  mean |applied - command| accel, steer")
+        for r in rows:
+            print(f"  {r['delay']:13d}  {r['tau_steer']:13.2f}  {r['success_rate']:9.1f}  {r['collision_rate']:11.1f}  "
+                  f"{r['avg_steps']:10.1f}  {r['act_mean_abs_dev_accel']:.3f}, {r['act_mean_abs_dev_steer']:.4f}")
+    print(json.dumps(dict(envs=args.envs, episodes_per_env=args.episodes_per_env, traffic=args.traffic, seed=args.seed,
+                          limits=args.act_limits, cells=table)), flush=True)
+    if tmp is not None:
+        tmp.cleanup()
+
+
+if __name__ == "__main__":
+    main()
