@@ -191,6 +191,24 @@ int mpc_predict_batch(mpc_handle *h, int32_t B, const float *obs, int32_t vehicl
                       void *stream);
 
 /*
+ * mpc_predict_batch_plan (an addition within ABI 8: old clients never call it, nothing else changes) - mpc_predict_batch that
+ * also hands out the plan the solve ended with; mpc_predict_batch is this entry with U = X = NULL (one body).  Arguments,
+ * flags and staging are those of mpc_predict_batch; with MPC_FLAG_DEVICE_PTRS U and X are device pointers, otherwise host
+ * pointers, copied back like act.  Each is optional.
+ *   U  [B][N][2]    the control sequence (acceleration, steer per stage), U[b][0] == act[b]
+ *   X  [B][N+1][4]  the state trajectory x, y, theta, v (the state order of mpc_solve_batch); X[b][0] is the parsed state
+ * Both hold the last iterate when the solve is not MPC_STATUS_IS_SOLVED, as in mpc_solve_batch.  The launches, and every bit
+ * of act / status / iters, are those of mpc_predict_batch, and nothing is allocated.  With MPC_FLAG_WARM_START the kernel
+ * writes its controls to the handle's warm-start memory as before and U is a device-to-device copy of that memory, enqueued
+ * after the solve (capturable): the memory and the next step's iterates are exactly what they are without U.  With
+ * MPC_FLAG_DETECT_ONLY nothing is solved and U and X are not written.  The two entries share one body, so the text of
+ * mpc_last_error after a refusal names mpc_predict_batch whichever of them was called (likewise mpc_ltv_predict_batch below).
+ */
+int mpc_predict_batch_plan(mpc_handle *h, int32_t B, const float *obs, int32_t vehicles_count, const double *weights,
+                           const double *ref_speed, uint32_t flags, double *act, double *U, double *X, int32_t *status,
+                           int32_t *iters, void *stream);
+
+/*
  * Iterative-linear MPC: B calls of IterativeLinearMPC_Agent._solve (agents/pure_mpc_linear.py:153-203): nearest
  * reference point (:38-60), forward simulation of the stored control profile (predict_motion, :84-110), linearisation
  * about it (linear_model_matrix, :62-82) and the QP of _linear_mpc_control (:205-257), which the reference gives to
@@ -215,6 +233,19 @@ int mpc_ltv_solve_batch(mpc_handle *h, int32_t B, const double *state, uint32_t 
  * for mpc_predict_batch. */
 int mpc_ltv_predict_batch(mpc_handle *h, int32_t B, const float *obs, int32_t vehicles_count, uint32_t flags, double *act,
                           int32_t *status, int32_t *iters, void *stream);
+
+/*
+ * mpc_ltv_predict_batch_plan (an addition within ABI 8) - mpc_ltv_predict_batch that also hands out the plan;
+ * mpc_ltv_predict_batch is this entry with U = X = NULL (one body, the same launch, the same bits).  U and X are optional,
+ * device pointers with MPC_FLAG_DEVICE_PTRS, else host pointers.
+ *   U  [B][N][2]    a device-to-device copy, enqueued after the solve, of the environment's stored profile (oa, od): the new
+ *                   profile where status is 0 (then U[b][0] == act[b]), the profile the call started from elsewhere
+ *   X  [B][N+1][4]  the states of the linear model under the profile of the last pass, x, y, v, yaw (the state order of
+ *                   mpc_ltv_solve_batch).  Where status is MPC_STATUS_INFEASIBLE_START the kernel writes no X: those rows
+ *                   are left as they were (with host pointers X is therefore copied in as well as out).
+ */
+int mpc_ltv_predict_batch_plan(mpc_handle *h, int32_t B, const float *obs, int32_t vehicles_count, uint32_t flags, double *act,
+                               double *U, double *X, int32_t *status, int32_t *iters, void *stream);
 
 /* Episode boundaries: forget collision memory / stop point of the listed environments (host array of n ids);
  * env_ids == NULL or n < 0 resets all.  Replaces constructing a new PureMPC_Agent (agents/pure_mpc.py:38-43,63). */
@@ -518,7 +549,7 @@ int mpc_interaction_metrics(int32_t device, int32_t B, int32_t K, int32_t Q, int
  * Rings: ring_scene [B][W + 1][R][8] f32 (scene t of the episode at index t mod (W + 1)), ring_seen [B][W][R][8] f32 or NULL,
  * ring_act [B][W][2] f64, ring_reward [B][W] f32, ring_i32 [B][W][3] = status, iters, flags (bit 0 done, 1 truncated, 2
  * crashed, 3 arrived); frame t at index t mod W.  slot [B] i32: work array between the two launches (the slot of an episode
- * that ends on this step, else -1).
+ * that ends on this step, else -1).  slot keeps these values until the next mpc_episode_trace call (mpc_plan_trace reads it).
  * Store: kept_scene [C][W + 1][R][8], kept_seen [C][W][R][8] or NULL, kept_act [C][W][2], kept_reward [C][W], kept_i32
  * [C][W][3]: of a kept episode of T steps the last L = min(T, W), first = T - L: kept frame i is step first + i (i < L), kept
  * scene i is s_{first + i} (i <= L); entries past L are not written.  index [C][6] i32 = environment b, ordinal j, steps T,
@@ -543,6 +574,61 @@ int mpc_episode_trace(int32_t device, int32_t B, int32_t R, int32_t Q, int32_t W
                       float *ring_scene, float *ring_seen, double *ring_act, float *ring_reward, int32_t *ring_i32,
                       int32_t *slot, float *kept_scene, float *kept_seen, double *kept_act, float *kept_reward,
                       int32_t *kept_i32, int32_t *index, int64_t *counts, void *stream);
+
+/*
+ * mpc_plan_metrics (an addition within ABI 8: old clients never call it, nothing else changes) - the MPC's plan against what
+ * happened in a closed-loop evaluation of B environments, per episode, beside mpc_drive_metrics: how close the planned path
+ * comes to where the observed vehicles will be (planned clearance), how far the ego ended up from where earlier plans put it
+ * (prediction error by lead) and how much a new plan's first control departs from what the previous plan intended for this
+ * step (replanning jump).  Formulas, in evaluation order, and the per-environment update in csrc/mpc_plan.hpp.  Device
+ * pointers, enqueue only on `stream`, never synchronises (capturable in a hipGraph); sixteen lanes per environment, no LDS, no
+ * atomics, no scratch.  One launch per policy step after the environment's step, and one with reset != 0 before the first.
+ *
+ * Inputs of a step: plan_X [B][N+1][4], plan_U [B][N][2] f64 and status [B] i32 (the step's solve, from
+ * mpc_predict_batch_plan / mpc_ltv_predict_batch_plan; a plan is valid iff MPC_STATUS_IS_SOLVED(status), an invalid one is
+ * counted and skipped everywhere), order (0: x, y, theta, v; 1: x, y, v, yaw - only x, y are read), acted [B][R][8] f32 (the
+ * observation the agent acted on), terminal_obs [B][R][8] f32 (the scene after the step, before the auto-reset), done [B] u8,
+ * dt [s], gap [m], lead0 .. lead3 (each 1 .. N, or 0 for unused; Lmax = the largest).
+ * Per step: c = the minimum over the stages k = 1 .. N and the rows j >= 1 of `acted` with presence != 0 of the distance
+ * between X[k].xy and (x_j + k dt vx_j, y_j + k dt vy_j); for each used lead h <= t + 1 whose plan p = t + 1 - h was valid,
+ * e = |terminal_obs row 0 xy - X_p[h].xy|; for t >= 1 with both plans valid |U_t[0] - U_{t-1}[min(1, N - 1)]| per channel.
+ * Running state: state_i32 [10][B] = steps, plans_valid, conflict_steps (c < gap), prev_valid, episode ordinal j, lead_n[4],
+ * replan_n; state_f64 [15][B] = min_plan_gap, replan_sum[2], replan_max[2], lead_sum[4], lead_max[4], prev_u[2]; ring_xy
+ * [B][Lmax][4][2] f64 = X_t[lead_i].xy at index t mod Lmax, ring_valid [B][Lmax] i32.
+ * Records, one slot per (environment b, ordinal j < Q), the slot mpc_episode_stats writes for the same episode: rec_i32
+ * [8][B][Q] = steps, plans_valid, plan_conflict_steps, replan_n, lead_n[4]; rec_f64 [13][B][Q] = min_plan_gap (+inf when no
+ * valid plan ever met a present vehicle), replan_accel_mean, replan_steer_mean, replan_accel_max, replan_steer_max,
+ * lead_mean[4], lead_max[4] (a mean is sum / n, 0 when n == 0).
+ *
+ * reset != 0 (the step inputs may be NULL): the running state of every environment returns to its start, the ring's validity
+ * is cleared.  Otherwise update; when done[b]: if j < Q write slot [b][j] and j += 1; then clear the running state and the
+ * ring's validity.  An environment past its quota writes no record.  All arithmetic is f64 without contraction on + - * /
+ * sqrt fabs: the kernel, a host build of the header and the evaluator's numpy path agree bit for bit.
+ * Errors (MPC_ERR_INVALID_ARG), one per rule: B < 0, N outside 1 .. MPC_MAX_HORIZON, R outside 1 .. MPC_MAX_OTHERS + 1,
+ * Q < 1, dt NaN or <= 0, gap NaN or < 0, a lead outside 0 .. N, no lead used, order outside 0 .. 1, a NULL state / ring /
+ * record pointer, a NULL step input of a non-reset launch.  B == 0 is a no-op.
+ */
+int mpc_plan_metrics(int32_t device, int32_t B, int32_t N, int32_t R, int32_t Q, int32_t reset, int32_t order, double dt,
+                     double gap, int32_t lead0, int32_t lead1, int32_t lead2, int32_t lead3, const double *plan_X,
+                     const double *plan_U, const int32_t *status, const float *acted, const float *terminal_obs,
+                     const uint8_t *done, int32_t *state_i32, double *state_f64, double *ring_xy, int32_t *ring_valid,
+                     int32_t *rec_i32, double *rec_f64, void *stream);
+
+/*
+ * mpc_plan_trace (an addition within ABI 8) - the plan planes of the episodes mpc_episode_trace keeps: call it right after
+ * mpc_episode_trace, on the same stream, for the same step, with that call's work array `slot` and the same B, Q, W, C and
+ * done.  Device pointers, enqueue only, capturable; one workgroup of four waves per environment, no atomics, no LDS.
+ * Every environment with ordinal j < Q appends plan_X [B][N+1][4] / plan_U [B][N][2] f64 to ring_X [B][W][N+1][4] / ring_U
+ * [B][W][N][2] at t mod W; when done[b] and 0 <= slot[b] < C the last L = min(T, W) frames are copied chronologically to
+ * kept_X [C][W][N+1][4] / kept_U [C][W][N][2] at slot[b]: kept frame i is the plan that produced the recorder's action frame
+ * i.  state_i32 [2][B] = steps of the current episode, ordinal j (done advances it; j >= Q writes nothing).  reset != 0 clears
+ * state_i32 (the step inputs may be NULL).  The order, the capacity and the selection are the recorder's.
+ * Errors (MPC_ERR_INVALID_ARG): B < 0, N outside 1 .. MPC_MAX_HORIZON, Q < 1, W outside 1 .. 4096, C < 1, a NULL state /
+ * ring / store pointer, a NULL step input of a non-reset launch.  B == 0 is a no-op.
+ */
+int mpc_plan_trace(int32_t device, int32_t B, int32_t N, int32_t Q, int32_t W, int32_t C, int32_t reset, const double *plan_X,
+                   const double *plan_U, const uint8_t *done, const int32_t *slot, int32_t *state_i32, double *ring_X,
+                   double *ring_U, double *kept_X, double *kept_U, void *stream);
 
 /*
  * mpc_perceive (an addition within ABI 8: old clients never call it, nothing else changes) - a perception model between the

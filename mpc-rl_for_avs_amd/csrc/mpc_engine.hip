@@ -36,6 +36,7 @@
 #include "mpc_interaction.hpp"
 #include "mpc_episode_stats.hpp"
 #include "mpc_episode_trace.hpp"
+#include "mpc_plan.hpp"
 
 namespace {
 
@@ -1266,6 +1267,40 @@ __global__ __launch_bounds__(64) void mpc_actuate_kernel(mpc::act::Params P, mpc
     }
 }
 
+// the plan against what happened (mpc_plan.hpp, mpc_plan_metrics): sixteen lanes per environment, four environments per wave,
+// the mapping of mpc_drive_metrics_kernel.  The N (R - 1) pairs of a planned stage and an observed vehicle are strided over
+// the sixteen lanes of a group, the group's minimum of the squared distances is taken by shuffles, then lane 0 does the
+// sequential update, the ring and the one record write.  The shuffles sit in wave-uniform control flow: a group with an invalid
+// plan, a lane without a pair, and a group past the end (it folds nothing) carry +inf; a group past the end writes nothing.
+// No LDS, no atomics.
+static_assert(mpc::plan::kMaxRows == MPC_MAX_OTHERS + 1 && mpc::plan::kMaxHorizon == MPC_MAX_HORIZON,
+              "mpc_plan.hpp restates the public header's limits");
+static_assert(mpc::plan::solved(0) == MPC_STATUS_IS_SOLVED(0) && mpc::plan::solved(1) == MPC_STATUS_IS_SOLVED(1) &&
+                  mpc::plan::solved(4) == MPC_STATUS_IS_SOLVED(4) && mpc::plan::solved(5) == MPC_STATUS_IS_SOLVED(5) &&
+                  mpc::plan::solved(7) == MPC_STATUS_IS_SOLVED(7) && mpc::plan::solved(8) == MPC_STATUS_IS_SOLVED(8),
+              "mpc_plan.hpp restates MPC_STATUS_IS_SOLVED");
+__global__ __launch_bounds__(64) void mpc_plan_metrics_kernel(mpc::plan::Accounts acc, mpc::plan::StepInputs in, int reset) {
+    namespace plan = mpc::plan;
+    const int l = threadIdx.x & 15, g = threadIdx.x >> 4;
+    const int b_ = blockIdx.x * 4 + g;
+    const bool live = b_ < acc.B;
+    const int b = live ? b_ : acc.B - 1;
+    double d2 = plan::kInf;
+    if (!reset && live) d2 = plan::fold_pairs(in, b, l, 16);
+    for (int off = 8; off >= 1; off >>= 1) d2 = plan::min2(d2, __shfl_xor(d2, off, 16));
+    if (live && l == 0) plan::episode_update(acc, in, b, reset != 0, d2);
+}
+
+// the plan planes of the kept episodes (mpc_plan.hpp, mpc_plan_trace): one workgroup of four waves per environment, the shape
+// of mpc_episode_trace_frame_kernel, whose slot [B] it reads.  The append is (N + 1) 4 + 2 N doubles, one per lane; the copy of
+// an episode that ends with a slot is lane-strided and coalesced, 256 loads in flight per pass.  ONE workgroup barrier between
+// append and copy, in uniform control flow (the conditions before it depend on the environment alone): the copy reads what
+// other lanes appended, and lane 0 writes the running state only after every lane has read it.  No atomics, no LDS.
+__global__ __launch_bounds__(kTraceFrameThreads) void mpc_plan_trace_kernel(mpc::plan::TraceStore store,
+                                                                             mpc::plan::TraceInputs in, int reset) {
+    mpc::plan::trace_env(store, in, (int)blockIdx.x, reset != 0, (int)threadIdx.x, kTraceFrameThreads, TraceBarrier{});
+}
+
 // end of a rollout (mpc_rollout_glue.hpp: truncation bootstrap + GAE): one workgroup per environment; thread t computes the
 // terms of step t (strided over T), thread 0 runs the reversed recurrence over the LDS copies, all threads store
 __global__ __launch_bounds__(256) void mpc_rollout_finish_kernel(mpc::glue::GaeArgs g) {
@@ -1746,6 +1781,15 @@ int mpc_reserve_envs(mpc_handle *h, int32_t B) {
 int mpc_predict_batch(mpc_handle *h, int32_t B, const float *obs, int32_t vehicles_count, const double *weights,
                       const double *ref_speed, uint32_t flags, double *act, int32_t *status, int32_t *iters,
                       void *stream_) {
+    return mpc_predict_batch_plan(h, B, obs, vehicles_count, weights, ref_speed, flags, act, nullptr, nullptr, status, iters,
+                                  stream_);
+}
+
+// the one body of the observation-level entry; U / X: the plan the solve ended with, or NULL (the launches, and every bit of
+// act / status / iters and of the handle's memory, are the same either way)
+int mpc_predict_batch_plan(mpc_handle *h, int32_t B, const float *obs, int32_t vehicles_count, const double *weights,
+                           const double *ref_speed, uint32_t flags, double *act, double *U, double *X, int32_t *status,
+                           int32_t *iters, void *stream_) {
     if (!h) return fail(MPC_ERR_INVALID_ARG, "mpc_predict_batch: null handle");
     const bool detect_only = (flags & MPC_FLAG_DETECT_ONLY) != 0, detected = (flags & MPC_FLAG_DETECTED) != 0;
     if (detect_only && detected)
@@ -1790,6 +1834,8 @@ int mpc_predict_batch(mpc_handle *h, int32_t B, const float *obs, int32_t vehicl
     const auto s_w = st.in(weights, (size_t)B * 3 * 8, Staging::kReserve);        // null with MPC_FLAG_DETECT_ONLY, like act
     const auto s_rs = st.in(ref_speed, (size_t)B * 8);                            // optional
     const auto s_act = st.out(act, (size_t)B * 2 * 8, Staging::kReserve);
+    const auto s_U = st.out(detect_only ? nullptr : U, (size_t)B * N * 2 * 8);                // optional
+    const auto s_X = st.out(detect_only ? nullptr : X, (size_t)B * N1 * 4 * 8);               // optional
     const auto s_st = st.out(status, (size_t)B * 4, Staging::kReserve);
     const auto s_it = st.out(iters, (size_t)B * 4, Staging::kReserve);
     if (int rc = st.commit()) return rc;
@@ -1822,8 +1868,11 @@ int mpc_predict_batch(mpc_handle *h, int32_t B, const float *obs, int32_t vehicl
     }
     if (int rc = dispatch_solve(h, B, cc, V, flags, stream, h->p_state, h->p_ego, h->p_vref, st.ptr(s_w), h->p_coll,
                                 h->p_others, h->p_nveh, warm ? h->d_warm : nullptr, 1, warm ? h->d_warm_valid : nullptr,
-                                st.ptr(s_act), warm ? h->d_warm : nullptr, nullptr, st.ptr(s_st), st.ptr(s_it)))
+                                st.ptr(s_act), warm ? h->d_warm : st.ptr(s_U), st.ptr(s_X), st.ptr(s_st), st.ptr(s_it)))
         return rc;
+    // with a warm start the kernel's U_out is the handle's memory, which stays what it is: the plan's U is a copy of it
+    if (warm && st.ptr(s_U))
+        HIP_TRY(hipMemcpyAsync(st.ptr(s_U), h->d_warm, (size_t)B * N * 2 * 8, hipMemcpyDeviceToDevice, stream));
     return st.finish(flags);
 }
 
@@ -1889,6 +1938,12 @@ int mpc_ltv_solve_batch(mpc_handle *h, int32_t B, const double *state, uint32_t 
 
 int mpc_ltv_predict_batch(mpc_handle *h, int32_t B, const float *obs, int32_t vehicles_count, uint32_t flags, double *act,
                           int32_t *status, int32_t *iters, void *stream_) {
+    return mpc_ltv_predict_batch_plan(h, B, obs, vehicles_count, flags, act, nullptr, nullptr, status, iters, stream_);
+}
+
+// the one body of that entry; U / X: the plan, or NULL (the same launch and the same bits either way)
+int mpc_ltv_predict_batch_plan(mpc_handle *h, int32_t B, const float *obs, int32_t vehicles_count, uint32_t flags, double *act,
+                               double *U, double *X, int32_t *status, int32_t *iters, void *stream_) {
     if (!h) return fail(MPC_ERR_INVALID_ARG, "mpc_ltv_predict_batch: null handle");
     if (B < 0 || !obs || !act)
         return fail(MPC_ERR_INVALID_ARG, "mpc_ltv_predict_batch: null required pointer or negative batch");
@@ -1898,18 +1953,23 @@ int mpc_ltv_predict_batch(mpc_handle *h, int32_t B, const float *obs, int32_t ve
     if (B == 0) return MPC_OK;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
-    const int rows = vehicles_count;
+    const int rows = vehicles_count, N = h->cfg.horizon;
     const bool dev = (flags & MPC_FLAG_DEVICE_PTRS) != 0;
     if (int rc = ensure_env(h, B, stream)) return rc;
     Staging st(h, stream, dev);
     const auto s_obs = st.in(obs, (size_t)B * rows * mpc::pre::kObsCols * 4);
     const auto s_act = st.out(act, (size_t)B * 2 * 8);
+    const auto s_U = st.out(U, (size_t)B * N * 2 * 8);                        // optional
+    const auto s_X = st.inout(X, (size_t)B * ((size_t)N + 1) * 4 * 8);        // optional; in: the kernel skips some rows
     const auto s_st = st.out(status, (size_t)B * 4, Staging::kReserve);
     const auto s_it = st.out(iters, (size_t)B * 4, Staging::kReserve);
     if (int rc = st.commit()) return rc;
-    if (int rc = launch_ltv(h, B, stream, nullptr, st.ptr(s_obs), rows, h->d_ltv_u, st.ptr(s_act), nullptr, st.ptr(s_st),
+    if (int rc = launch_ltv(h, B, stream, nullptr, st.ptr(s_obs), rows, h->d_ltv_u, st.ptr(s_act), st.ptr(s_X), st.ptr(s_st),
                             st.ptr(s_it), nullptr))
         return rc;
+    // the kernel's U is the stored profile, which stays what it is: the plan's U is a copy of it
+    if (st.ptr(s_U))
+        HIP_TRY(hipMemcpyAsync(st.ptr(s_U), h->d_ltv_u, (size_t)B * N * 2 * 8, hipMemcpyDeviceToDevice, stream));
     return st.finish(flags);
 }
 
@@ -2413,6 +2473,50 @@ int mpc_actuate(int32_t device, int32_t B, int32_t reset, const mpc_actuator *pa
     const act::Buffers buf{(int)B, command, done_prev, applied, state_f64, age, ctr, counts, sums};
     hipLaunchKernelGGL(mpc_actuate_kernel, dim3((unsigned)((B + 31) / 32)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream_),
                        P, buf, (int)reset);
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_plan_metrics(int32_t device, int32_t B, int32_t N, int32_t R, int32_t Q, int32_t reset, int32_t order, double dt,
+                     double gap, int32_t lead0, int32_t lead1, int32_t lead2, int32_t lead3, const double *plan_X,
+                     const double *plan_U, const int32_t *status, const float *acted, const float *terminal_obs,
+                     const uint8_t *done, int32_t *state_i32, double *state_f64, double *ring_xy, int32_t *ring_valid,
+                     int32_t *rec_i32, double *rec_f64, void *stream_) {
+    namespace plan = mpc::plan;
+    const int32_t leads[plan::kLeads] = {lead0, lead1, lead2, lead3};
+    if (const char *why = plan::refusal(B, N, R, Q, order, dt, gap, leads))
+        return fail(MPC_ERR_INVALID_ARG, std::string("mpc_plan_metrics: bad argument (") + why + ")");
+    if (!state_i32 || !state_f64 || !ring_xy || !ring_valid || !rec_i32 || !rec_f64)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_plan_metrics: null state / ring / record pointer");
+    if (!reset && (!plan_X || !plan_U || !status || !acted || !terminal_obs || !done))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_plan_metrics: null step-input pointer of a non-reset launch");
+    if (B == 0) return MPC_OK;
+    HIP_TRY(hipSetDevice(device));
+    const plan::Accounts acc{(int)B, (int)Q, plan::max_lead(leads), state_i32, state_f64, ring_xy, ring_valid, rec_i32, rec_f64};
+    const plan::StepInputs in{(int)N, (int)R, (int)order, dt, gap, {lead0, lead1, lead2, lead3}, plan_X, plan_U, status, acted,
+                              terminal_obs, done};
+    hipLaunchKernelGGL(mpc_plan_metrics_kernel, dim3((unsigned)((B + 3) / 4)), dim3(64), 0,
+                       reinterpret_cast<hipStream_t>(stream_), acc, in, (int)reset);
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_plan_trace(int32_t device, int32_t B, int32_t N, int32_t Q, int32_t W, int32_t C, int32_t reset, const double *plan_X,
+                   const double *plan_U, const uint8_t *done, const int32_t *slot, int32_t *state_i32, double *ring_X,
+                   double *ring_U, double *kept_X, double *kept_U, void *stream_) {
+    namespace plan = mpc::plan;
+    if (B < 0 || N < 1 || N > MPC_MAX_HORIZON || Q < 1 || W < 1 || W > mpc::trace::kMaxWindow || C < 1)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_plan_trace: bad size (B >= 0, 1 <= N <= 64, Q >= 1, 1 <= W <= 4096, C >= 1)");
+    if (!state_i32 || !ring_X || !ring_U || !kept_X || !kept_U)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_plan_trace: null state / ring / store pointer");
+    if (!reset && (!plan_X || !plan_U || !done || !slot))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_plan_trace: null step-input pointer of a non-reset launch");
+    if (B == 0) return MPC_OK;
+    HIP_TRY(hipSetDevice(device));
+    const plan::TraceStore store{(int)B, (int)N, (int)Q, (int)W, (int)C, state_i32, ring_X, ring_U, kept_X, kept_U};
+    const plan::TraceInputs in{plan_X, plan_U, done, slot};
+    hipLaunchKernelGGL(mpc_plan_trace_kernel, dim3((unsigned)B), dim3(kTraceFrameThreads), 0,
+                       reinterpret_cast<hipStream_t>(stream_), store, in, (int)reset);
     HIP_TRY(hipGetLastError());
     return MPC_OK;
 }

@@ -1,7 +1,8 @@
 """ctypes binding of the C ABI (include/mpc_mi355x.h) - the only way Python reaches the HIP kernels: the entry points that
 take an engine handle through `MPCEngine`'s methods, the handle-less ones (environment step, policy step, rollout glue,
-evaluation accounting, perception, episode traces, tracker, actuator) through `call` / `caller`, by parameter name, in the
-order of `SIGNATURES`, `EVALUATION_SIGNATURES`, `TRACKER_SIGNATURES` and `ACTUATION_SIGNATURES`.
+evaluation accounting, perception, episode traces, tracker, plan metrics, actuator) through `call` / `caller`, by parameter
+name, in the order of `SIGNATURES`, `EVALUATION_SIGNATURES`, `TRACKER_SIGNATURES`, `PLAN_SIGNATURES` and
+`ACTUATION_SIGNATURES`.
 
 There is no CPU fallback: if the shared library is missing, or no MI355X is visible, construction fails
 loudly (`EngineError`).  Host numpy arrays are copied by the library; torch device tensors are passed
@@ -122,18 +123,26 @@ EVALUATION_SIGNATURES = {name: tuple(tuple(word.split(":")) for word in text.spl
 TRACKER_SIGNATURES = {name: tuple(tuple(word.split(":")) for word in text.split()) for name, text in dict(
     mpc_track_rows="device:i32 B:i32 R:i32 reset:i32 dt:f64 gate:f64 coast:i32 alpha_pos:f64 alpha_vel:f64 obs_meas:ptr "
                    "done:ptr obs_out:ptr row_slot:ptr row_miss:ptr track_f64:ptr track_i32:ptr counts:ptr stream:ptr").items()}
+# The plan metrics and the plan planes of the traces (csrc/mpc_plan.hpp), likewise; tests/test_plan_cpu.py holds this one against
+# the header.
+PLAN_SIGNATURES = {name: tuple(tuple(word.split(":")) for word in text.split()) for name, text in dict(
+    mpc_plan_metrics="device:i32 B:i32 N:i32 R:i32 Q:i32 reset:i32 order:i32 dt:f64 gap:f64 lead0:i32 lead1:i32 lead2:i32 "
+                     "lead3:i32 plan_X:ptr plan_U:ptr status:ptr acted:ptr terminal_obs:ptr done:ptr state_i32:ptr "
+                     "state_f64:ptr ring_xy:ptr ring_valid:ptr rec_i32:ptr rec_f64:ptr stream:ptr",
+    mpc_plan_trace="device:i32 B:i32 N:i32 Q:i32 W:i32 C:i32 reset:i32 plan_X:ptr plan_U:ptr done:ptr slot:ptr state_i32:ptr "
+                   "ring_X:ptr ring_U:ptr kept_X:ptr kept_U:ptr stream:ptr").items()}
 # The actuator model of the evaluation (csrc/mpc_actuator.hpp), likewise; tests/test_actuator_cpu.py holds this one against the
 # header.
 ACTUATION_SIGNATURES = {name: tuple(tuple(word.split(":")) for word in text.split()) for name, text in dict(
     mpc_actuate="device:i32 B:i32 reset:i32 params:actuator command:ptr done_prev:ptr applied:ptr state_f64:ptr age:ptr "
                 "ctr:ptr counts:ptr sums:ptr stream:ptr").items()}
-_TABLES = (SIGNATURES, EVALUATION_SIGNATURES, TRACKER_SIGNATURES, ACTUATION_SIGNATURES)
+_TABLES = (SIGNATURES, EVALUATION_SIGNATURES, TRACKER_SIGNATURES, PLAN_SIGNATURES, ACTUATION_SIGNATURES)
 
 _EXPORTS = ["mpc_version", "mpc_last_error", "mpc_default_config", "mpc_default_config_sized", "mpc_create", "mpc_destroy",
-            "mpc_set_reference", "mpc_solve_batch", "mpc_workspace_bytes", "mpc_predict_batch",
+            "mpc_set_reference", "mpc_solve_batch", "mpc_workspace_bytes", "mpc_predict_batch", "mpc_predict_batch_plan",
             "mpc_reset_env_state", "mpc_reset_env_mask", "mpc_get_env_state", "mpc_get_last_inputs",
-            "mpc_ltv_solve_batch", "mpc_ltv_predict_batch", "mpc_env_state_bytes", "mpc_save_env_state",
-            "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_policy_control", "mpc_policy_control_tile", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_interaction_metrics", "mpc_episode_trace", "mpc_perceive", "mpc_track_rows", "mpc_actuate", "mpc_eval_nlp", "mpc_streams_overlap"]
+            "mpc_ltv_solve_batch", "mpc_ltv_predict_batch", "mpc_ltv_predict_batch_plan", "mpc_env_state_bytes", "mpc_save_env_state",
+            "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_policy_control", "mpc_policy_control_tile", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_interaction_metrics", "mpc_episode_trace", "mpc_plan_metrics", "mpc_plan_trace", "mpc_perceive", "mpc_track_rows", "mpc_actuate", "mpc_eval_nlp", "mpc_streams_overlap"]
 ABI_VERSION = 8          # MPC_ABI_VERSION of include/mpc_mi355x.h this binding is written for
 MAX_OTHERS = 16
 _lib = None
@@ -188,10 +197,14 @@ def load_library(path: str | None = None):
     lib.mpc_workspace_bytes.restype = ctypes.c_int64
     lib.mpc_predict_batch.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_int32, dp, dp, ctypes.c_uint32, dp, ip, ip, vp]
     lib.mpc_predict_batch.restype = ctypes.c_int
+    lib.mpc_predict_batch_plan.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_int32, dp, dp, ctypes.c_uint32, dp, dp, dp, ip, ip, vp]
+    lib.mpc_predict_batch_plan.restype = ctypes.c_int
     lib.mpc_ltv_solve_batch.argtypes = [vp, ctypes.c_int32, dp, ctypes.c_uint32, dp, dp, dp, ip, ip, ip, vp]
     lib.mpc_ltv_solve_batch.restype = ctypes.c_int
     lib.mpc_ltv_predict_batch.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_int32, ctypes.c_uint32, dp, ip, ip, vp]
     lib.mpc_ltv_predict_batch.restype = ctypes.c_int
+    lib.mpc_ltv_predict_batch_plan.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_int32, ctypes.c_uint32, dp, dp, dp, ip, ip, vp]
+    lib.mpc_ltv_predict_batch_plan.restype = ctypes.c_int
     lib.mpc_reset_env_state.argtypes = [vp, ip, ctypes.c_int32, vp]
     lib.mpc_reset_env_state.restype = ctypes.c_int
     lib.mpc_reset_env_mask.argtypes = [vp, ctypes.c_int32, vp, ctypes.c_uint32, vp]
@@ -251,7 +264,7 @@ _CALLERS = {name: _caller(name, sig) for table in _TABLES for name, sig in table
 
 def caller(name: str):
     """The handle-less entry point `name` as a function of keywords alone: every one of SIGNATURES[name] (or
-    EVALUATION_SIGNATURES[name], TRACKER_SIGNATURES[name], ACTUATION_SIGNATURES[name]) and no other (TypeError
+    EVALUATION_SIGNATURES[name], TRACKER_SIGNATURES[name], PLAN_SIGNATURES[name], ACTUATION_SIGNATURES[name]) and no other (TypeError
     naming the entry point and the parameter otherwise, before anything is called).  Python ints and floats pass through;
     a pointer is a torch tensor (its address; a bool tensor's bytes are the uint8 the kernels read) or None; `stream` is a
     torch stream, its raw handle or None; `params` of mpc_perceive a PerceptionParams, of mpc_actuate an ActuatorParams.  Enqueue only; EngineError with the
@@ -355,6 +368,20 @@ def _torch_out(out, key, B, dev):
     import torch
     return {key: torch.empty((B, 2), dtype=torch.float64, device=dev),
             "status": torch.empty(B, dtype=torch.int32, device=dev), "iters": torch.empty(B, dtype=torch.int32, device=dev)}
+
+
+PLAN_ORDER_NLP, PLAN_ORDER_LTV = 0, 1     # `order` of mpc_plan_metrics: x, y, theta, v / x, y, v, yaw
+
+
+def _torch_plan(out, order, B, N, dev):
+    """`out` with the plan's tensors: plan_U [B, N, 2] and plan_X [B, N + 1, 4] float64 (zeros at first, then reused like act)
+    and plan_order."""
+    import torch
+    if out.get("plan_U") is None or tuple(out["plan_U"].shape) != (B, N, 2) or out["plan_U"].device != dev:
+        out["plan_U"] = torch.zeros((B, N, 2), dtype=torch.float64, device=dev)
+        out["plan_X"] = torch.zeros((B, N + 1, 4), dtype=torch.float64, device=dev)
+    out["plan_order"] = order
+    return out
 
 
 class MPCEngine:
@@ -470,11 +497,13 @@ class MPCEngine:
         self._check(rc, "mpc_predict_batch")
 
     def predict_batch(self, obs, weights, ref_speed=None, collision_cost=False, warm_start=False, detected=False,
-                      strict_discontinuity=False):
+                      strict_discontinuity=False, plan=False):
         """obs[B, vehicles_count, 8] float32 -> dict(act[B, 2], status, iters): parsing, collision detector (with the
         per-environment memory kept inside the engine), speed-profile rewrite and solve, all on the device.
         warm_start (not in the reference): each environment starts from its previous solution advanced one stage.
-        detected: `detect_batch` has already advanced the records for this observation."""
+        detected: `detect_batch` has already advanced the records for this observation.
+        plan=True (mpc_predict_batch_plan): also plan_U [B, N, 2], plan_X [B, N + 1, 4] (x, y, theta, v) - the controls and
+        states the solve ended with - and plan_order 0."""
         obs = _obs_array(obs)
         B, rows = obs.shape[:2]
         weights = np.ascontiguousarray(weights, dtype=np.float64).reshape(B, 3)
@@ -482,15 +511,20 @@ class MPCEngine:
         o = _host_out("act", B)
         flags = (FLAG_COLLISION_COST if collision_cost else 0) | (FLAG_WARM_START if warm_start else 0) | \
             (FLAG_DETECTED if detected else 0) | (FLAG_STRICT_DISCONTINUITY if strict_discontinuity else 0)
-        rc = self._lib.mpc_predict_batch(self._h, B, _ptr(obs), rows, _ptr(weights), _ptr(rs), flags, _ptr(o["act"]),
-                                         _ptr(o["status"]), _ptr(o["iters"]), None)
-        self._check(rc, "mpc_predict_batch")
+        if plan:
+            o.update(plan_U=np.zeros((B, self.horizon, 2)), plan_X=np.zeros((B, self.horizon + 1, 4)), plan_order=PLAN_ORDER_NLP)
+        rc = self._lib.mpc_predict_batch_plan(self._h, B, _ptr(obs), rows, _ptr(weights), _ptr(rs), flags, _ptr(o["act"]),
+                                              _ptr(o.get("plan_U")), _ptr(o.get("plan_X")), _ptr(o["status"]),
+                                              _ptr(o["iters"]), None)
+        self._check(rc, "mpc_predict_batch_plan")
         return o
 
     def predict_batch_torch(self, obs, weights, ref_speed=None, collision_cost=False, out=None, sync=False,
-                            warm_start=False, throughput=False, strict_discontinuity=False):
+                            warm_start=False, throughput=False, strict_discontinuity=False, plan=False):
         """Zero-copy variant on torch device tensors (obs float32 [B, R, 8], weights float64 [B, 3], ref_speed float64
-        [B] or None), enqueued on torch's current stream.  Returns dict(act, status, iters) of device tensors."""
+        [B] or None), enqueued on torch's current stream.  Returns dict(act, status, iters) of device tensors.
+        plan=True (mpc_predict_batch_plan): `out` gains plan_U [B, N, 2], plan_X [B, N + 1, 4] (x, y, theta, v), reused
+        across calls like act, and plan_order 0; plan=False is the same launches without them."""
         import torch
         B, rows = int(obs.shape[0]), int(obs.shape[1])
         dev = obs.device
@@ -502,9 +536,16 @@ class MPCEngine:
         flags = FLAG_DEVICE_PTRS | (FLAG_COLLISION_COST if collision_cost else 0) | (0 if sync else FLAG_NO_SYNC) | \
             (FLAG_WARM_START if warm_start else 0) | (FLAG_THROUGHPUT if throughput else 0) | \
             (FLAG_STRICT_DISCONTINUITY if strict_discontinuity else 0)   # throughput: several groups in flight
-        rc = self._lib.mpc_predict_batch(self._h, B, _ptr(obs), rows, _ptr(weights), _ptr(ref_speed), flags,
-                                         _ptr(out["act"]), _ptr(out["status"]), _ptr(out["iters"]), _stream(dev))
-        self._check(rc, "mpc_predict_batch")
+        if not plan:
+            rc = self._lib.mpc_predict_batch(self._h, B, _ptr(obs), rows, _ptr(weights), _ptr(ref_speed), flags,
+                                             _ptr(out["act"]), _ptr(out["status"]), _ptr(out["iters"]), _stream(dev))
+            self._check(rc, "mpc_predict_batch")
+            return out
+        out = _torch_plan(out, PLAN_ORDER_NLP, B, self.horizon, dev)
+        rc = self._lib.mpc_predict_batch_plan(self._h, B, _ptr(obs), rows, _ptr(weights), _ptr(ref_speed), flags,
+                                              _ptr(out["act"]), _ptr(out["plan_U"]), _ptr(out["plan_X"]), _ptr(out["status"]),
+                                              _ptr(out["iters"]), _stream(dev))
+        self._check(rc, "mpc_predict_batch_plan")
         return out
 
     def eval_nlp(self, ego_index, weights, is_collide, X, U, vref=None, others=None, collision_cost=False):
@@ -568,27 +609,40 @@ class MPCEngine:
         self._check(rc, "mpc_ltv_solve_batch")
         return out
 
-    def ltv_predict_batch(self, obs):
+    def ltv_predict_batch(self, obs, plan=False):
         """obs[B, vehicles_count, 8] float32 -> dict(act, status, iters): Agent.predict of the iterative-linear agent
-        with the per-environment stored profile kept inside the engine."""
+        with the per-environment stored profile kept inside the engine.  plan=True (mpc_ltv_predict_batch_plan): also plan_U
+        [B, N, 2] (the stored profile after the call), plan_X [B, N + 1, 4] (x, y, v, yaw; zeros where the kernel writes none:
+        an infeasible start) and plan_order 1."""
         obs = _obs_array(obs)
         B, rows = obs.shape[:2]
         o = _host_out("act", B)
-        rc = self._lib.mpc_ltv_predict_batch(self._h, B, _ptr(obs), rows, 0, _ptr(o["act"]), _ptr(o["status"]),
-                                             _ptr(o["iters"]), None)
-        self._check(rc, "mpc_ltv_predict_batch")
+        if plan:
+            o.update(plan_U=np.zeros((B, self.horizon, 2)), plan_X=np.zeros((B, self.horizon + 1, 4)), plan_order=PLAN_ORDER_LTV)
+        rc = self._lib.mpc_ltv_predict_batch_plan(self._h, B, _ptr(obs), rows, 0, _ptr(o["act"]), _ptr(o.get("plan_U")),
+                                                  _ptr(o.get("plan_X")), _ptr(o["status"]), _ptr(o["iters"]), None)
+        self._check(rc, "mpc_ltv_predict_batch_plan")
         return o
 
-    def ltv_predict_batch_torch(self, obs, out=None, sync=False):
-        """Zero-copy variant on a float32 device tensor [B, R, 8], enqueued on torch's current stream."""
+    def ltv_predict_batch_torch(self, obs, out=None, sync=False, plan=False):
+        """Zero-copy variant on a float32 device tensor [B, R, 8], enqueued on torch's current stream.  plan=True
+        (mpc_ltv_predict_batch_plan): `out` gains plan_U [B, N, 2], plan_X [B, N + 1, 4] (x, y, v, yaw; rows of an infeasible
+        start keep what they held), reused across calls like act, and plan_order 1."""
         import torch
         if obs.dtype != torch.float32 or not obs.is_contiguous() or not obs.is_cuda or obs.dim() != 3 or obs.shape[2] != 8:
             raise ValueError("obs: expected contiguous float32 device tensor [B, vehicles_count, 8]")
         B, rows, dev = int(obs.shape[0]), int(obs.shape[1]), obs.device
         out = _torch_out(out, "act", B, dev)
-        rc = self._lib.mpc_ltv_predict_batch(self._h, B, _ptr(obs), rows, FLAG_DEVICE_PTRS | (0 if sync else FLAG_NO_SYNC),
-                                             _ptr(out["act"]), _ptr(out["status"]), _ptr(out["iters"]), _stream(dev))
-        self._check(rc, "mpc_ltv_predict_batch")
+        flags = FLAG_DEVICE_PTRS | (0 if sync else FLAG_NO_SYNC)
+        if not plan:
+            rc = self._lib.mpc_ltv_predict_batch(self._h, B, _ptr(obs), rows, flags, _ptr(out["act"]), _ptr(out["status"]),
+                                                 _ptr(out["iters"]), _stream(dev))
+            self._check(rc, "mpc_ltv_predict_batch")
+            return out
+        out = _torch_plan(out, PLAN_ORDER_LTV, B, self.horizon, dev)
+        rc = self._lib.mpc_ltv_predict_batch_plan(self._h, B, _ptr(obs), rows, flags, _ptr(out["act"]), _ptr(out["plan_U"]),
+                                                  _ptr(out["plan_X"]), _ptr(out["status"]), _ptr(out["iters"]), _stream(dev))
+        self._check(rc, "mpc_ltv_predict_batch_plan")
         return out
 
     def reset_env_state(self, env_ids=None):

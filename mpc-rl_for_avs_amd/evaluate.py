@@ -43,10 +43,17 @@ in numpy on the CPU path.
 delay, lost commands, calibration error, noise, first-order lag, rate limits and saturation.  The environment is handed the
 applied action instead of the command, inside the same captured step (mpc_actuate), or by the same update in numpy on the CPU
 path; every observer's `act` is then the applied action, what the environment was handed.
+
+`plan=` asks the MPC agent for the plan behind every action (mpc_predict_batch_plan / mpc_ltv_predict_batch_plan: the planned
+states and controls the solve ended with) and scores it against what happened (csrc/mpc_plan.hpp, `PlanMetrics`): the planned
+clearance to the vehicles the agent saw, the ego's distance from where earlier plans put it, and the jump between consecutive
+plans, per episode, inside the same captured step (mpc_plan_metrics), or by the same update in numpy on the CPU path.  A trace
+recorder with plan=True keeps the plan of every step of the episodes it keeps (mpc_plan_trace).
 """
 from __future__ import annotations
 
 import ctypes
+import inspect
 import math
 import time
 from dataclasses import dataclass
@@ -95,6 +102,12 @@ TRACK_SLOTS, TRACK_MAX_COAST, TRACK_NO_SLOT = 16, 200, 255
 ACTUATION_COUNTS = ("steps", "held", "rate_limited", "saturated", "nonfinite")             # mpc_actuate counts [5][B]
 ACTUATION_SALT, ACT_RING, ACT_MAX_DELAY, ACT_LAST, ACT_PREV = 0x9FB21C651E98DF25, 8, 7, 8, 9
 ENV_LIMITS = ((-5.0, 5.0), (-math.pi / 4, math.pi / 4))
+# csrc/mpc_plan.hpp: the records of mpc_plan_metrics (lead{i}: the i-th of its four leads), the planes of its running state,
+# the leads per launch, MPC_MAX_HORIZON
+PLAN_I32 = ("steps", "plans_valid", "plan_conflict_steps", "replan_n") + tuple(f"lead{i}_n" for i in range(4))   # rec_i32 [8][B][Q]
+PLAN_F64 = ("min_plan_gap", "replan_accel_mean", "replan_steer_mean", "replan_accel_max", "replan_steer_max") + \
+    tuple(f"lead{i}_mean" for i in range(4)) + tuple(f"lead{i}_max" for i in range(4))                           # rec_f64 [13][B][Q]
+PLAN_STATE_I32, PLAN_STATE_F64, PLAN_LEADS, PLAN_MAX_HORIZON = 10, 15, 4, 64
 
 
 def records_from_planes(rec_i32, rec_f64, names_i32=REC_I32, names_f64=REC_F64, bools=_BOOL) -> dict:
@@ -409,6 +422,158 @@ class DriveMetrics(_EpisodeAccounts):
             sf[i] = torch.where(keep, v, torch.full_like(v, float("inf") if i < 3 else 0.0))
         for i, v in enumerate(carry(ax, ay, steer)):
             sf[10 + i] = v
+
+
+def default_leads(N: int) -> tuple:
+    """The leads `plan=True` scores: 1, N // 4, N // 2, N with duplicates and zeros dropped."""
+    out = []
+    for h in (1, int(N) // 4, int(N) // 2, int(N)):
+        if h > 0 and h not in out:
+            out.append(h)
+    return tuple(out)
+
+
+class PlanMetrics(_EpisodeAccounts):
+    """The MPC's plan against what happened, per episode (csrc/mpc_plan.hpp states the update step by step; layouts in
+    include/mpc_mi355x.h, mpc_plan_metrics): the planned clearance to where the vehicles the agent saw will be, the distance
+    between where the ego ended up and where the plans of `leads` steps ago put it, and the jump between a plan's first
+    control and what the previous plan intended for this step.  N: the horizon of the plans; R: rows of an observation; leads:
+    up to four leads in 1..N (None: default_leads(N)); gap [m]: a step whose planned clearance is below it is a planned
+    conflict (default: the environment's crash distance).  A plan whose status is not solved is counted and skipped.
+    `update` after the environment's step is the kernel (backend "hip": enqueue only, capturable) or the same update in numpy
+    (backend "torch", for the CPU environment); both give the same bits."""
+
+    def __init__(self, B: int, Q: int, device, backend: str = "torch", N: int = 20, R: int = VEHICLES_COUNT, dt: float = 0.1,
+                 leads=None, gap: float = CRASH_DISTANCE):
+        N = int(N)
+        if not 1 <= N <= PLAN_MAX_HORIZON:
+            raise ValueError(f"N must be 1..{PLAN_MAX_HORIZON}")
+        if not 1 <= int(R) <= MAX_ROWS:
+            raise ValueError(f"R must be 1..{MAX_ROWS}")
+        if not float(dt) > 0:
+            raise ValueError("dt must be > 0")
+        if not float(gap) >= 0:
+            raise ValueError("gap must be >= 0")
+        leads = default_leads(N) if leads is None else tuple(int(h) for h in leads)
+        if not 1 <= len(leads) <= PLAN_LEADS or any(h < 0 for h in leads) or not any(leads):
+            raise ValueError(f"leads: 1..{PLAN_LEADS} leads, each >= 1 (0: unused), at least one used")
+        if max(leads) > N:
+            raise ValueError(f"leads {leads} reach beyond the horizon {N}")
+        super().__init__(B, Q, device, backend, PLAN_STATE_I32, PLAN_STATE_F64, PLAN_I32, PLAN_F64)
+        self.N, self.R, self.dt, self.gap = N, int(R), float(dt), float(gap)
+        self.leads = leads + (0,) * (PLAN_LEADS - len(leads))
+        self.Lmax = max(self.leads)
+        self.ring_xy = torch.zeros((self.B, self.Lmax, PLAN_LEADS, 2), dtype=torch.float64, device=self.device)
+        self.ring_valid = torch.zeros((self.B, self.Lmax), dtype=torch.int32, device=self.device)
+
+    @property
+    def config(self) -> dict:
+        """The keyword arguments that make a PlanMetrics with the same settings."""
+        return dict(N=self.N, R=self.R, dt=self.dt, leads=tuple(h for h in self.leads if h), gap=self.gap)
+
+    def observe(self, frame, reset=False):
+        f = frame.get
+        self.update(f("plan_X"), f("plan_U"), f("status"), f("acted"), f("terminal_obs"), f("done"), f("plan_order", 0), reset)
+
+    def update(self, plan_X, plan_U, status, acted, terminal_obs, done, order: int = 0, reset: bool = False):
+        B, N, R, dev = self.B, self.N, self.R, self.device
+        if order not in (0, 1):
+            raise ValueError("order must be 0 (x, y, theta, v) or 1 (x, y, v, yaw)")
+        if reset:
+            plan_X = plan_U = status = acted = terminal_obs = done = None
+        else:
+            _check(plan_X, "plan_X", (B, N + 1, 4), torch.float64, dev)
+            _check(plan_U, "plan_U", (B, N, 2), torch.float64, dev)
+            _check(status, "status", (B,), torch.int32, dev)
+            _check(acted, "acted", (B, R, 8), torch.float32, dev)
+            _check(terminal_obs, "terminal_obs", (B, R, 8), torch.float32, dev)
+            done = _check(done, "done", (B,), torch.uint8, dev)
+        if self.backend == "torch":
+            self._numpy_update(plan_X, plan_U, status, acted, terminal_obs, done, reset)
+            return
+        l0, l1, l2, l3 = self.leads
+        _engine.caller("mpc_plan_metrics")(
+            device=self.device.index, B=B, N=N, R=R, Q=self.Q, reset=1 if reset else 0, order=int(order), dt=self.dt,
+            gap=self.gap, lead0=l0, lead1=l1, lead2=l2, lead3=l3, plan_X=plan_X, plan_U=plan_U, status=status, acted=acted,
+            terminal_obs=terminal_obs, done=done, state_i32=self.state_i32, state_f64=self.state_f64, ring_xy=self.ring_xy,
+            ring_valid=self.ring_valid, rec_i32=self.rec_i32, rec_f64=self.rec_f64, stream=_engine.current_stream(self.device))
+
+    def _numpy_update(self, plan_X, plan_U, status, acted, terminal_obs, done, reset):
+        """csrc/mpc_plan.hpp over the batch: every statement acts on all environments, in the header's order."""
+        B, N, R, Q, L = self.B, self.N, self.R, self.Q, self.Lmax
+        planes = (self.state_i32, self.state_f64, self.ring_xy, self.ring_valid, self.rec_i32, self.rec_f64)
+        si, sf, ring, ring_valid, ri, rf = (t.cpu().numpy() for t in planes)
+        inf = float("inf")
+        if reset:
+            si[:], sf[:], ring_valid[:] = 0, 0.0, 0
+            sf[0] = inf
+            _write_back(zip(planes, (si, sf, ring, ring_valid, ri, rf)))
+            return
+        X, U, a, term = (t.cpu().numpy() for t in (plan_X, plan_U, acted, terminal_obs))
+        valid = _solved(status.cpu().numpy())
+        done = done.cpu().numpy() != 0
+        env, t = np.arange(B), si[0].copy()
+        with np.errstate(invalid="ignore", over="ignore"):
+            d2 = np.full(B, inf)                                                   # 1
+            if R > 1:
+                a64 = a.astype(np.float64)
+                kd = np.arange(1, N + 1).astype(np.float64) * self.dt
+                qx = a64[:, None, 1:, 1] + kd[None, :, None] * a64[:, None, 1:, 3]
+                qy = a64[:, None, 1:, 2] + kd[None, :, None] * a64[:, None, 1:, 4]
+                ex, ey = X[:, 1:, None, 0] - qx, X[:, 1:, None, 1] - qy
+                pair = np.where((a[:, None, 1:, 0] != 0) & valid[:, None, None], ex * ex + ey * ey, inf)
+                d2 = pair.reshape(B, -1).min(axis=1)
+            c = np.sqrt(d2)
+            sf[0] = np.where(valid & (c < sf[0]), c, sf[0])
+            si[2] += valid & (c < self.gap)
+            si[0] = t + 1                                                          # 2
+            si[1] += valid
+            at = t % L                                                             # 3
+            for i, h in enumerate(self.leads):
+                if h > 0:
+                    ring[env, at, i] = X[:, h, :2]
+            ring_valid[env, at] = valid
+            ox, oy = term[:, 0, 1].astype(np.float64), term[:, 0, 2].astype(np.float64)   # 4
+            for i, h in enumerate(self.leads):
+                if h < 1:
+                    continue
+                old = h <= t + 1
+                p = np.where(old, t + 1 - h, 0) % L
+                ok = old & (ring_valid[env, p] != 0)
+                ex, ey = ox - ring[env, p, i, 0], oy - ring[env, p, i, 1]
+                e = np.sqrt(ex * ex + ey * ey)
+                si[5 + i] += ok
+                sf[5 + i] = np.where(ok, sf[5 + i] + e, sf[5 + i])
+                sf[9 + i] = np.where(ok & (e > sf[9 + i]), e, sf[9 + i])
+            both = (t >= 1) & valid & (si[3] != 0)                                 # 5
+            for ch in (0, 1):
+                jump = np.abs(U[:, 0, ch] - sf[13 + ch])
+                sf[1 + ch] = np.where(both, sf[1 + ch] + jump, sf[1 + ch])
+                sf[3 + ch] = np.where(both & (jump > sf[3 + ch]), jump, sf[3 + ch])
+            si[9] += both
+            nxt = 1 if N > 1 else 0
+            sf[13], sf[14], si[3] = U[:, nxt, 0], U[:, nxt, 1], valid
+            j = si[4].copy()                                                       # 6
+            w = np.nonzero(done & (j < Q))[0]
+            mean = lambda total, n: np.where(n > 0, total / np.maximum(n, 1), 0.0)
+            ri[0, w, j[w]], ri[1, w, j[w]], ri[2, w, j[w]], ri[3, w, j[w]] = si[0, w], si[1, w], si[2, w], si[9, w]
+            rf[0, w, j[w]] = sf[0, w]
+            for ch in (0, 1):
+                rf[1 + ch, w, j[w]] = mean(sf[1 + ch, w], si[9, w])
+                rf[3 + ch, w, j[w]] = sf[3 + ch, w]
+            for i in range(PLAN_LEADS):
+                ri[4 + i, w, j[w]] = si[5 + i, w]
+                rf[5 + i, w, j[w]] = mean(sf[5 + i, w], si[5 + i, w])
+                rf[9 + i, w, j[w]] = sf[9 + i, w]
+        j[w] += 1
+        si[:, done], sf[:, done], ring_valid[done] = 0, 0.0, 0
+        sf[0, done] = inf
+        si[4] = j
+        _write_back(zip(planes, (si, sf, ring, ring_valid, ri, rf)))
+
+    def records(self) -> dict:
+        """The records (PLAN_I32 + PLAN_F64, numpy arrays [B, Q]) and `leads`, the four leads the lead{i}_* fields belong to."""
+        return dict(super().records(), leads=self.leads)
 
 
 def _wrap_pi(a):
@@ -1216,11 +1381,13 @@ class EpisodeTraces:
     b -, ordinal, steps, first, outcome, launch), `counts` (dict: matched, kept, dropped, launches), the store's planes cut to
     the n kept episodes (scene [n, W + 1, R, 8], seen [n, W, R, 8] or None, action [n, W, 2], reward [n, W], frame_i32
     [n, W, 3]; entries past an episode's L = min(steps, W) are whatever the store held) and `nbytes`, the memory the recorder
-    took (running state, rings, work array and store).  `keep` is the bit set the recorder ran with."""
+    took (running state, rings, work array and store).  `keep` is the bit set the recorder ran with.  plan_X [n, W, N + 1, 4]
+    and plan_U [n, W, N, 2] (or None): the plan that produced each action frame, when the recorder ran with plan=True."""
 
-    def __init__(self, index, counts, scene, seen, action, reward, frame_i32, keep, nbytes):
+    def __init__(self, index, counts, scene, seen, action, reward, frame_i32, keep, nbytes, plan_X=None, plan_U=None):
         self.index, self.counts, self.keep, self.nbytes = index, counts, int(keep), int(nbytes)
         self.scene, self.seen, self.action, self.reward, self.frame_i32 = scene, seen, action, reward, frame_i32
+        self.plan_X, self.plan_U = plan_X, plan_U
 
     def __len__(self):
         return int(self.index["env"].shape[0])
@@ -1233,7 +1400,7 @@ class EpisodeTraces:
         """Kept episode i in chronological order: its index fields as ints (env, ordinal, steps, first, outcome, launch),
         and of its last L = min(steps, W) steps action [L, 2], reward [L], status, iters, flags [L] (TRACE_FLAGS), scene
         [L + 1, R, 8] (scene k is the one step first + k started from; the last is the scene the episode ended in) and,
-        when it was recorded, seen [L, R, 8]."""
+        when it was recorded, seen [L, R, 8] and plan_X [L, N + 1, 4], plan_U [L, N, 2] (frame k: the plan behind action k)."""
         if not 0 <= int(i) < len(self):
             raise IndexError(f"episode {i} of {len(self)}")
         out = {k: int(v[i]) for k, v in self.index.items()}
@@ -1243,6 +1410,8 @@ class EpisodeTraces:
                    scene=self.scene[i, :L + 1].copy())
         if self.seen is not None:
             out["seen"] = self.seen[i, :L].copy()
+        if self.plan_X is not None:
+            out.update(plan_X=self.plan_X[i, :L].copy(), plan_U=self.plan_U[i, :L].copy())
         return out
 
     def save(self, path) -> None:
@@ -1252,6 +1421,8 @@ class EpisodeTraces:
                       reward=self.reward, frame_i32=self.frame_i32, keep=np.int64(self.keep), nbytes=np.int64(self.nbytes))
         if self.seen is not None:
             arrays["seen"] = self.seen
+        if self.plan_X is not None:
+            arrays.update(plan_X=self.plan_X, plan_U=self.plan_U)
         np.savez_compressed(path, **arrays)
 
     @classmethod
@@ -1259,7 +1430,8 @@ class EpisodeTraces:
         with np.load(path) as z:
             return cls({k: z[f"index_{k}"] for k in TRACE_INDEX}, {k: int(v) for k, v in zip(TRACE_COUNTS, z["counts"])},
                        z["scene"], z["seen"] if "seen" in z.files else None, z["action"], z["reward"], z["frame_i32"],
-                       int(z["keep"]), int(z["nbytes"]))
+                       int(z["keep"]), int(z["nbytes"]), z["plan_X"] if "plan_X" in z.files else None,
+                       z["plan_U"] if "plan_U" in z.files else None)
 
 
 class EpisodeTrace:
@@ -1272,10 +1444,13 @@ class EpisodeTrace:
     model).  The `action` plane is what the environment was handed: in an evaluation with an actuator model (`Actuation`)
     the applied action, not the agent's command, so a trace can be replayed against the environment.  `update` after the
     environment's step is the kernel (backend "hip": enqueue only, capturable) or the same update in numpy (backend "torch",
-    for the CPU environment); both give the same bytes.  Memory is bounded by B, window and capacity alone (`nbytes`)."""
+    for the CPU environment); both give the same bytes.  Memory is bounded by B, window and capacity alone (`nbytes`).
+    plan=True also keeps the plan behind every action frame (mpc_plan_trace, launched right after the recorder's own
+    kernels with their `slot`; csrc/mpc_plan.hpp): plan_X [N + 1, 4] and plan_U [N, 2] per frame, N = `horizon`, the agent's."""
 
     def __init__(self, B: int, Q: int, device, backend: str = "torch", R: int = VEHICLES_COUNT, keep="failed",
-                 capacity: int = 64, window: int = EPISODE_STEPS, seen: bool = False, env_offset: int = 0):
+                 capacity: int = 64, window: int = EPISODE_STEPS, seen: bool = False, env_offset: int = 0,
+                 plan: bool = False, horizon: int | None = None):
         if backend not in ("hip", "torch"):
             raise ValueError("backend must be 'hip' or 'torch'")
         if int(B) < 0 or int(Q) < 1:
@@ -1299,42 +1474,65 @@ class EpisodeTrace:
         self.kept_scene, self.kept_seen = z(C, W + 1, R, 8, dt=f32), z(C, W, R, 8, dt=f32) if self.seen else None
         self.kept_act, self.kept_reward, self.kept_i32 = z(C, W, 2, dt=f64), z(C, W, dt=f32), z(C, W, 3, dt=i32)
         self.index, self.counts = z(C, 6, dt=i32), z(4, dt=torch.int64)
+        self.plan, self.N = bool(plan), None
+        self.plan_state_i32 = self.ring_X = self.ring_U = self.kept_X = self.kept_U = None
+        if self.plan:
+            if horizon is None or not 1 <= int(horizon) <= PLAN_MAX_HORIZON:
+                raise ValueError(f"plan=True needs horizon, the agent's, 1..{PLAN_MAX_HORIZON}")
+            N = self.N = int(horizon)
+            self.plan_state_i32 = z(2, B, dt=i32)            # steps, ordinal
+            self.ring_X, self.ring_U = z(B, W, N + 1, 4, dt=f64), z(B, W, N, 2, dt=f64)
+            self.kept_X, self.kept_U = z(C, W, N + 1, 4, dt=f64), z(C, W, N, 2, dt=f64)
 
+    _PLAN_PLANES = ("plan_state_i32", "ring_X", "ring_U", "kept_X", "kept_U")
     _PLANES = ("state_i32", "ring_scene", "ring_seen", "ring_act", "ring_reward", "ring_i32", "slot", "kept_scene", "kept_seen",
                "kept_act", "kept_reward", "kept_i32", "index", "counts")
     _STORE = ("kept_scene", "kept_seen", "kept_act", "kept_reward", "kept_i32", "index")
 
     @staticmethod
-    def bytes_for(B: int, R: int, W: int, C: int, seen: bool = False) -> int:
+    def bytes_for(B: int, R: int, W: int, C: int, seen: bool = False, plan: bool = False, horizon: int = 0) -> int:
         """The layout formula: running state and work array 20 B, rings ((W + 1) + [W]) 32 R + 32 W per environment; store
-        ((W + 1) + [W]) 32 R + 32 W + 24 per slot; counts 32."""
+        ((W + 1) + [W]) 32 R + 32 W + 24 per slot; counts 32.  With plan: 8 B of running state per environment and
+        W (48 N + 32) of plans per environment and per slot."""
         planes = ((W + 1) + (W if seen else 0)) * 32 * R + 32 * W
-        return B * (20 + planes) + C * (planes + 24) + 32
+        plans = W * (48 * horizon + 32) if plan else 0
+        return B * (20 + planes + (8 if plan else 0) + plans) + C * (planes + 24 + plans) + 32
 
     @property
     def nbytes(self) -> int:
-        return sum(t.numel() * t.element_size() for t in (getattr(self, n) for n in self._PLANES) if t is not None)
+        return sum(t.numel() * t.element_size() for t in (getattr(self, n) for n in self._PLANES + self._PLAN_PLANES)
+                   if t is not None)
 
     @property
     def config(self) -> dict:
         """The keyword arguments that make an EpisodeTrace with the same settings."""
         return dict(R=self.R, keep=[k for k, bit in TRACE_KEEP.items() if k != "failed" and self.keep & bit],
-                    capacity=self.C, window=self.W, seen=self.seen, env_offset=self.env_offset)
+                    capacity=self.C, window=self.W, seen=self.seen, env_offset=self.env_offset,
+                    **(dict(plan=True, horizon=self.N) if self.plan else {}))
 
     def observe(self, frame, reset=False):
         f = frame.get
         self.update(f("terminal_obs"), frame["obs"], f("seen") if self.seen else None, f("act"), f("reward"), f("done"),
-                    f("truncated"), f("crashed"), f("arrived"), f("status"), f("iters"), reset)
+                    f("truncated"), f("crashed"), f("arrived"), f("status"), f("iters"), reset,
+                    plan_X=f("plan_X") if self.plan else None, plan_U=f("plan_U") if self.plan else None)
 
-    def update(self, terminal_obs, obs, seen, action, reward, done, truncated, crashed, arrived, status, iters, reset=False):
+    def update(self, terminal_obs, obs, seen, action, reward, done, truncated, crashed, arrived, status, iters, reset=False,
+               plan_X=None, plan_U=None):
         """After the reset of the environments (reset=True: only `obs` is read; the store is zeroed as well) and after every
         step, before the buffer the agent acted on is overwritten.  seen: that buffer when the recorder was built with
-        seen=True, else None."""
+        seen=True, else None.  plan_X [B, N + 1, 4], plan_U [B, N, 2]: the step's plan when the recorder was built with
+        plan=True, else None."""
         B, R, dev = self.B, self.R, self.device
         _check(obs, "obs", (B, R, 8), torch.float32, dev)
+        if not reset:
+            if (plan_X is not None or plan_U is not None) != self.plan:
+                raise ValueError("plan_X and plan_U must be given exactly when the recorder was built with plan=True")
+            if self.plan:
+                _check(plan_X, "plan_X", (B, self.N + 1, 4), torch.float64, dev)
+                _check(plan_U, "plan_U", (B, self.N, 2), torch.float64, dev)
         flags = {}
         if reset:
-            for n in self._STORE:
+            for n in self._STORE + (("kept_X", "kept_U") if self.plan else ()):
                 if getattr(self, n) is not None:
                     getattr(self, n).zero_()
             terminal_obs = seen = action = reward = status = iters = None
@@ -1353,11 +1551,41 @@ class EpisodeTrace:
                 flags[n] = _check(t, n, (B,), torch.uint8, dev)
         if self.backend == "torch":
             self._numpy_update(terminal_obs, obs, seen, action, reward, flags, status, iters, reset)
+            if self.plan:
+                self._numpy_plan(None if reset else plan_X, plan_U, flags["done"], reset)
             return
         _engine.caller("mpc_episode_trace")(
             device=self.device.index, B=B, R=R, Q=self.Q, W=self.W, C=self.C, keep=self.keep, reset=1 if reset else 0,
             terminal_obs=terminal_obs, obs=obs, seen=seen, action=action, reward=reward, **flags, status=status, iters=iters,
             **{n: getattr(self, n) for n in self._PLANES}, stream=_engine.current_stream(self.device))
+        if self.plan:                                        # right after it, on the same stream: it reads that call's slot
+            _engine.caller("mpc_plan_trace")(
+                device=self.device.index, B=B, N=self.N, Q=self.Q, W=self.W, C=self.C, reset=1 if reset else 0,
+                plan_X=None if reset else plan_X, plan_U=None if reset else plan_U, done=flags["done"], slot=self.slot,
+                state_i32=self.plan_state_i32, ring_X=self.ring_X, ring_U=self.ring_U, kept_X=self.kept_X, kept_U=self.kept_U,
+                stream=_engine.current_stream(self.device))
+
+    def _numpy_plan(self, plan_X, plan_U, done, reset):
+        """mpc_plan_trace (csrc/mpc_plan.hpp) over the batch, after `_numpy_update` has written this step's `slot`"""
+        Q, W, C = self.Q, self.W, self.C
+        planes = tuple(getattr(self, n) for n in self._PLAN_PLANES)
+        st, ring_X, ring_U, kept_X, kept_U = (t.cpu().numpy() for t in planes)
+        if reset:
+            st[:] = 0
+        else:
+            X, U, done, slot = plan_X.cpu().numpy(), plan_U.cpu().numpy(), done.cpu().numpy() != 0, self.slot.cpu().numpy()
+            t, j = st[0].copy(), st[1].copy()
+            live = j < Q
+            e = np.nonzero(live)[0]
+            ring_X[e, t[e] % W], ring_U[e, t[e] % W] = X[e], U[e]
+            for b in np.nonzero(live & done & (slot >= 0) & (slot < C))[0]:
+                T = int(t[b]) + 1
+                L = min(T, W)
+                frames = (T - L + np.arange(L)) % W
+                kept_X[slot[b], :L], kept_U[slot[b], :L] = ring_X[b, frames], ring_U[b, frames]
+            st[0] = np.where(live, np.where(done, 0, t + 1), st[0])
+            st[1] = j + (live & done)
+        _write_back(zip(planes, (st, ring_X, ring_U, kept_X, kept_U)))
 
     def _numpy_update(self, terminal_obs, obs, seen, action, reward, flags, status, iters, reset):
         """csrc/mpc_episode_trace.hpp over the batch: the claim is a cumulative sum in environment order."""
@@ -1418,7 +1646,8 @@ class EpisodeTrace:
         index = {k: ix[:, i].copy() for i, k in enumerate(TRACE_INDEX)}
         index["env"] = index["env"] + np.int32(self.env_offset)
         return EpisodeTraces(index, counts, cut(self.kept_scene), cut(self.kept_seen), cut(self.kept_act),
-                             cut(self.kept_reward), cut(self.kept_i32), self.keep, self.nbytes)
+                             cut(self.kept_reward), cut(self.kept_i32), self.keep, self.nbytes, cut(self.kept_X),
+                             cut(self.kept_U))
 
 
 @dataclass
@@ -1434,7 +1663,9 @@ class EvalResult:
     trace=, else None; tracker: the totals of the tracker (`Tracker.totals()`: measured, matched, born, coasted, expired,
     evicted, cut over the whole evaluation, idle steps included) when the evaluation ran with one, else None; actuation: the
     totals of the actuator model (`Actuation.totals()`: steps, held, rate_limited, saturated, nonfinite, mean_abs_dev and
-    max_abs_dev per channel, idle steps included) when the evaluation ran with one, else None."""
+    max_abs_dev per channel, idle steps included) when the evaluation ran with one, else None; plan: the plan metrics'
+    records (`PlanMetrics.records()`: dict of numpy arrays [B, Q], keys PLAN_I32 + PLAN_F64, the same slots, and `leads`) when
+    the evaluation ran with plan=, else None."""
     records: dict
     dt: float
     steps: int
@@ -1446,6 +1677,7 @@ class EvalResult:
     traces: EpisodeTraces | None = None
     tracker: dict | None = None
     actuation: dict | None = None
+    plan: dict | None = None
 
     @property
     def travel_time(self):
@@ -1469,7 +1701,11 @@ class EvalResult:
         output rows, coasted / (matched + born + coasted) (0 when there was none).  With an actuator model also act_held_frac,
         act_rate_limited_frac and act_saturated_frac (the steps on which a command was lost, the rate limit acted, the
         saturation acted, over all steps) and act_mean_abs_dev_accel [m/s^2], act_mean_abs_dev_steer [rad]: the mean of
-        |applied - command| per channel."""
+        |applied - command| per channel.  With the plan metrics also plans_valid_frac (solved plans over all steps),
+        plan_conflict_frac (steps whose planned clearance was below the gap, over the steps with a valid plan), min_plan_gap
+        (the smallest of any episode, inf when there is none), pred_err_lead{h}_mean for every lead h in use (the mean
+        distance between the ego and where the plan of h steps before put it, over all scored steps; 0 when there is none)
+        and replan_accel_mean [m/s^2], replan_steer_mean [rad] (the mean replanning jump over all scored steps)."""
         out = self._base_summary()
         if self.drive is not None:
             out.update(self._drive_summary())
@@ -1485,6 +1721,19 @@ class EvalResult:
             a = self.actuation
             out.update({f"act_{k}_frac": a[k] / max(a["steps"], 1) for k in ("held", "rate_limited", "saturated")})
             out.update(act_mean_abs_dev_accel=float(a["mean_abs_dev"][0]), act_mean_abs_dev_steer=float(a["mean_abs_dev"][1]))
+        if self.plan is not None:
+            out.update(self._plan_summary())
+        return out
+
+    def _plan_summary(self) -> dict:
+        d = self.plan
+        valid = int(d["plans_valid"].sum())
+        over = lambda mean, n: float((d[mean] * d[n]).sum()) / max(int(d[n].sum()), 1)     # the mean over all scored steps
+        out = dict(plans_valid_frac=valid / max(int(d["steps"].sum()), 1),
+                   plan_conflict_frac=int(d["plan_conflict_steps"].sum()) / max(valid, 1),
+                   min_plan_gap=float(d["min_plan_gap"].min()) if d["min_plan_gap"].size else float("inf"),
+                   replan_accel_mean=over("replan_accel_mean", "replan_n"), replan_steer_mean=over("replan_steer_mean", "replan_n"))
+        out.update({f"pred_err_lead{h}_mean": over(f"lead{i}_mean", f"lead{i}_n") for i, h in enumerate(d["leads"]) if h})
         return out
 
     def _interaction_summary(self) -> dict:
@@ -1548,7 +1797,7 @@ def _instance(cls, given, defaults: dict, *args):
 def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = False, reset_mpc_on_done: bool = False,
                    use_graph: bool | None = None, poll_every: int = 16, seed: int = 0, on_step=None,
                    metrics: bool = False, perception=None, interaction: bool = False, trace=None,
-                   tracker=None, actuation=None) -> EvalResult:
+                   tracker=None, actuation=None, plan=None) -> EvalResult:
     """Run `agent` in closed loop on the B environments of `env` (a SyntheticIntersectionEnv) until each environment has
     finished `episodes_per_env` episodes; returns their records.
 
@@ -1590,6 +1839,16 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     `action` plane of a trace, which can therefore be replayed against the environment; on_step's dict then also holds act
     (applied) and command (the agent's output).  The agent's own memory of its last action stays its command.
     EvalResult.actuation holds the totals.  None: no launch, no buffer, nothing changes.
+    plan (None and False: off): True, a dict of `PlanMetrics`'s keyword arguments such as dict(leads=(1, 5, 10, 20), gap=2.5) (N defaults to the
+    agent's horizon, dt to the environment's; True is the empty dict: default_leads(N), the crash distance), or a PlanMetrics
+    for this environment's batch and quota and the agent's horizon.  The agent is then asked for its plan
+    (act_batch_torch(plan=True): the solve's planned states and controls, mpc_predict_batch_plan), and the plan metrics of
+    every episode (EvalResult.plan) are updated after the interaction metrics and before the trace recorder inside the step
+    (so inside the captured graph) from the plan, the observation the agent acted on and the scene after the step.
+    on_step's dict then also holds plan_X, plan_U and plan_order (valid until the next step; the observation they were planned
+    on is the previous call's obs, or seen).  A trace recorder with
+    plan=True (a dict of its arguments gets horizon from the agent) asks for the plan in the same way.  ValueError for an
+    agent without a plan (PPOAgent) and for leads beyond the horizon.  None: no launch, no buffer, nothing changes.
     Every episode ends by EPISODE_STEPS (200) steps, so Q * 200 steps bound the loop; RuntimeError if the episodes are not
     all recorded by then."""
     Q = int(episodes_per_env)
@@ -1628,26 +1887,43 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     ended = torch.zeros(B, dtype=torch.uint8, device=dev) if actuation is not None else None
     filtered = perception is not None or tracker is not None       # the agent acts on something other than the true scene
     sensed = torch.zeros_like(obs) if perception is not None and tracker is not None else None    # between the two
-    trace = _instance(EpisodeTrace, trace, dict(R=VEHICLES_COUNT, env_offset=offset, seen=filtered), B, Q, dev, backend)
+    horizon = getattr(eng, "horizon", None)
+    plan = {} if plan is True else None if plan is False else plan
+    trace_plan = bool(trace.get("plan")) if isinstance(trace, dict) else bool(getattr(trace, "plan", False))
+    wants_plan = plan is not None or trace_plan
+    if wants_plan and (not getattr(agent, "HAS_PLAN", True) or horizon is None or
+                       "plan" not in inspect.signature(agent.act_batch_torch).parameters):
+        raise ValueError(f"{type(agent).__name__} has no plan: plan= and a trace with plan=True need an MPC agent")
+    trace = _instance(EpisodeTrace, trace, dict(R=VEHICLES_COUNT, env_offset=offset, seen=filtered,
+                                                **(dict(horizon=horizon) if trace_plan else {})), B, Q, dev, backend)
     if trace is not None:
         if (trace.B, trace.Q, trace.R, trace.device) != (B, Q, VEHICLES_COUNT, dev):
             raise ValueError(f"trace must be built for {B} environments, {Q} episodes each, {VEHICLES_COUNT} rows, on {dev}")
         if trace.seen and not filtered:
             raise ValueError("trace records seen=True only with a perception model or a tracker")
+        if trace.plan and trace.N != horizon:
+            raise ValueError(f"trace keeps plans of horizon {trace.N}, the agent's is {horizon}")
+    planm = _instance(PlanMetrics, plan, dict(N=horizon, R=VEHICLES_COUNT, dt=float(env.dt)), B, Q, dev, backend)
+    if planm is not None and (planm.B, planm.Q, planm.N, planm.R, planm.device) != (B, Q, horizon, VEHICLES_COUNT, dev):
+        raise ValueError(f"plan must be built for {B} environments, {Q} episodes each, horizon {horizon}, "
+                         f"{VEHICLES_COUNT} rows, on {dev}")
     stats = EpisodeStats(B, Q, dev, backend)
     drive = DriveMetrics(B, Q, dev, backend, env.ref_xy, env.dt, VEHICLES_COUNT) if metrics else None
     inter = InteractionMetrics(B, Q, dev, backend, env.ref_xy, env.dt, env.K) if interaction else None
     # The order of a step's launches, after the agent's and the environment's: the accounting, the drive metrics, the
-    # interaction metrics, the trace recorder - each `observe` of the step's frame - and then perception.apply and
+    # interaction metrics, the plan metrics, the trace recorder - each `observe` of the step's frame - and then perception.apply and
     # tracker.apply (or the plain copy), which overwrite the buffer the agent acted on: the recorder has to have read it by
     # then.
-    observers = [o for o in (stats, drive, inter, trace) if o is not None]
+    observers = [o for o in (stats, drive, inter, planm, trace) if o is not None]
     kw = dict(deterministic=bool(deterministic), seed=int(seed), env_offset=offset)
+    if wants_plan:
+        kw["plan"] = True
     # what on_step is shown of a frame: the accounting's inputs; with metrics=True also the scenes and the action; with a
     # perception model also the true observation, what the agent gets next and (below) the class of every row
     shown = ("ego", "done", "truncated", "crashed", "arrived", "reward", "status", "iters") + \
         (("terminal_obs", "obs", "act") if metrics else ()) + (("obs", "seen") if filtered else ()) + \
-        (("act", "command") if actuation is not None else ())
+        (("act", "command") if actuation is not None else ()) + \
+        (("plan_X", "plan_U", "plan_order") if wants_plan else ())
 
     def show(frame, **first):
         first.update((k, frame[k]) for k in shown if k in frame)
@@ -1682,6 +1958,8 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
             frame["seen"] = obs       # still what the agent acted on while the observers run; what it gets next after them
         if actuation is not None:
             frame["command"] = out["act"]
+        if wants_plan:                # `acted`: the observation the agent acted on, until `sense` overwrites it
+            frame.update(plan_X=out["plan_X"], plan_U=out["plan_U"], plan_order=out["plan_order"], acted=obs)
         for o in observers:
             o.observe(frame)
         if actuation is not None:
@@ -1765,11 +2043,12 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
                       interaction=None if inter is None else inter.records(),
                       traces=None if trace is None else trace.traces(),
                       tracker=None if tracker is None else tracker.totals(),
-                      actuation=None if actuation is None else actuation.totals())
+                      actuation=None if actuation is None else actuation.totals(),
+                      plan=None if planm is None else planm.records())
 
 
 def compare(agents: dict, make_env, episodes_per_env: int = 1, metrics: bool = False, perception=None,
-            interaction: bool = False, trace=None, results=None, tracker=None, actuation=None, **kw) -> dict:
+            interaction: bool = False, trace=None, results=None, tracker=None, actuation=None, plan=None, **kw) -> dict:
     """Evaluate every agent on a fresh environment from make_env() (same seed: the HIP environment keys its draws by seed and
     environment id, so every agent meets the same initial episodes) -> {name: summary}; metrics=True adds the drive metrics'
     keys to every summary.  perception (a dict of `Perception`'s keyword arguments, or a Perception whose configuration is
@@ -1778,15 +2057,22 @@ def compare(agents: dict, make_env, episodes_per_env: int = 1, metrics: bool = F
     `EpisodeTrace`'s keyword arguments, or an EpisodeTrace whose settings are copied): every agent gets a fresh recorder with
     the same settings.  tracker (a dict of `Tracker`'s keyword arguments, or a Tracker whose configuration is copied): every
     agent gets a fresh tracker.  actuation (a dict of `Actuation`'s keyword arguments, or an Actuation whose configuration is
-    copied): every agent gets a fresh actuator model with the same seed, hence the same draws on the same steps.  results: a dict that receives every agent's EvalResult by name (its traces, its records)."""
-    perception, trace, tracker, actuation = (x.config if isinstance(x, (Perception, EpisodeTrace, Tracker, Actuation)) else x
-                                             for x in (perception, trace, tracker, actuation))
+    copied): every agent gets a fresh actuator model with the same seed, hence the same draws on the same steps.  plan (True, a dict of `PlanMetrics`'s keyword arguments, or a PlanMetrics whose settings are
+    copied): every agent gets fresh plan metrics; an agent without a plan (PPOAgent) is evaluated without them.  results: a dict that receives every agent's EvalResult by name (its traces, its records)."""
+    perception, trace, tracker, actuation, plan = (
+        x.config if isinstance(x, (Perception, EpisodeTrace, Tracker, Actuation, PlanMetrics)) else x
+        for x in (perception, trace, tracker, actuation, plan))
+    plan = {} if plan is True else None if plan is False else plan
     fresh = lambda settings: None if settings is None else dict(settings)
     out = {}
     for name, agent in agents.items():
+        planned = getattr(agent, "HAS_PLAN", True)
+        settings = fresh(trace)
+        if settings is not None and not planned:         # the recorder of an agent without a plan keeps no plan planes
+            settings.pop("plan", None), settings.pop("horizon", None)
         res = evaluate_agent(agent, make_env(), episodes_per_env, metrics=metrics, perception=fresh(perception),
-                             interaction=interaction, trace=fresh(trace), tracker=fresh(tracker),
-                             actuation=fresh(actuation), **kw)
+                             interaction=interaction, trace=settings, tracker=fresh(tracker), actuation=fresh(actuation),
+                             plan=fresh(plan) if planned else None, **kw)
         if results is not None:
             results[name] = res
         out[name] = res.summary()

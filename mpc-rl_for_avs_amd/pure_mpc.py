@@ -302,10 +302,11 @@ class PureMPC_Agent:
             print(f"NOTICE: Not found solution ({bad} of {B} instances)")
         return out["act"]
 
-    def act_batch_torch(self, obs, deterministic=False, seed=0, env_offset=0):
+    def act_batch_torch(self, obs, deterministic=False, seed=0, env_offset=0, plan=False):
         """Closed-loop evaluation (evaluate.evaluate_agent): obs float32 device tensor [B, vehicles_count, 8] -> dict(act [B, 2]
         f64, status, iters) through engine.predict_batch_torch with the agent's default weights, collision cost and warm start;
-        enqueue-only, the same output tensors every call.  deterministic / seed / env_offset: the MPC draws nothing."""
+        enqueue-only, the same output tensors every call.  deterministic / seed / env_offset: the MPC draws nothing.
+        plan=True: also plan_U [B, N, 2], plan_X [B, N + 1, 4] (x, y, theta, v) and plan_order 0, what the solve ended with."""
         import torch
         B, st = int(obs.shape[0]), getattr(self, "_act_state", None)
         if st is None or st["w"].shape[0] != B or st["w"].device != obs.device:
@@ -313,7 +314,8 @@ class PureMPC_Agent:
             st = self._act_state = dict(w=torch.tensor(w, dtype=torch.float64, device=obs.device).repeat(B, 1).contiguous(),
                                         out=None)
         st["out"] = self._engine.predict_batch_torch(obs, st["w"], None, collision_cost=self.collision_cost,
-                                                     warm_start=self.warm_start, out=st["out"])
+                                                     warm_start=self.warm_start, out=st["out"],
+                                                     **(dict(plan=True) if plan else {}))
         return st["out"]
 
     def batch_env_state(self, B):

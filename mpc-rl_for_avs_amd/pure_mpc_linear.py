@@ -127,13 +127,14 @@ class IterativeLinearMPC_Agent:
         self.last_solve = out
         return out["act"]
 
-    def act_batch_torch(self, obs, deterministic=False, seed=0, env_offset=0):
+    def act_batch_torch(self, obs, deterministic=False, seed=0, env_offset=0, plan=False):
         """Closed-loop evaluation (evaluate.evaluate_agent): obs float32 device tensor [B, vehicles_count, 8] -> dict(act [B, 2]
-        f64, status, iters) through engine.ltv_predict_batch_torch; enqueue-only, the same output tensors every call."""
+        f64, status, iters) through engine.ltv_predict_batch_torch; enqueue-only, the same output tensors every call.
+        plan=True: also plan_U [B, N, 2] (the stored profile), plan_X [B, N + 1, 4] (x, y, v, yaw) and plan_order 1."""
         out = getattr(self, "_act_out", None)
         if out is not None and (out["act"].shape[0] != obs.shape[0] or out["act"].device != obs.device):
             out = None
-        self._act_out = self._engine.ltv_predict_batch_torch(obs, out=out)
+        self._act_out = self._engine.ltv_predict_batch_torch(obs, out=out, **(dict(plan=True) if plan else {}))
         return self._act_out
 
     def reset_env_state(self, env_ids=None):

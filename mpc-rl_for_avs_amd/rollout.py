@@ -1297,6 +1297,7 @@ class _PolicyAgent:
     buffers its state needs besides (`_act_buffers`), and how the action becomes what the environment gets (`_act`)."""
 
     DETERMINISTIC = False          # policy_output's default, the one of the reference's predict
+    HAS_PLAN = True                # act_batch_torch(plan=True) returns the MPC's planned trajectory
 
     @classmethod
     def from_sb3(cls, path, engine=None, device="cpu", **kw):
@@ -1317,9 +1318,10 @@ class _PolicyAgent:
         return actions
 
     @torch.no_grad()
-    def act_batch_torch(self, obs, deterministic: bool = False, seed: int = 0, env_offset: int = 0):
+    def act_batch_torch(self, obs, deterministic: bool = False, seed: int = 0, env_offset: int = 0, plan: bool = False):
         """obs float32 device tensor [B, 10, 8] -> dict(act [B, 2] f64, status, iters, step, generator): the policy, then the
-        subclass's `_act`.  Enqueue-only, the same output tensors every call.  With `_fusable` and the observation on a GPU
+        subclass's `_act`; plan=True: also the MPC's plan_U, plan_X and plan_order (engine.predict_batch_torch), on the fused
+        and the unfused path alike - ValueError for an agent without an MPC (PPOAgent).  Enqueue-only, the same output tensors every call.  With `_fusable` and the observation on a GPU
         the policy is one launch (FusedPolicy, the collector's kernels), otherwise ActorCritic.act.
           deterministic  the mean: the fused kernel reads all-zero noise, `step` is None and no generator is returned
           stochastic     fused: noise keyed by (seed, env_offset + b, step), `step` the int64 [1] counter the caller
@@ -1328,6 +1330,8 @@ class _PolicyAgent:
                          resampled, agents/ppo_mpc.py:627-628): fused, keyed by (seed, env_offset + b, epoch 0); torch, drawn
                          once from a generator seeded by seed
         restart_actions() puts the counters / matrices back to their start."""
+        if plan and not self.HAS_PLAN:
+            raise ValueError(f"{type(self).__name__} has no plan: there is no MPC between the policy and the controls")
         key = (int(obs.shape[0]), obs.device, bool(deterministic), int(seed), int(env_offset))
         st = getattr(self, "_act_state", None)
         if st is None or st["key"] != key:
@@ -1338,7 +1342,7 @@ class _PolicyAgent:
         else:
             actions, _, _ = self.policy.act(obs, generator=st["gen"], noise=st["noise"])
         draws = not st["fused"] and not deterministic and not self.policy.use_sde
-        return dict(self._act(st, obs, actions), step=st["step"], generator=st["gen"] if draws else None)
+        return dict(self._act(st, obs, actions, plan), step=st["step"], generator=st["gen"] if draws else None)
 
     def _fused_policy(self, key):
         B, dev, deterministic, seed, env_offset = key
@@ -1441,13 +1445,14 @@ class MPCRLAgent(_PolicyAgent):
     def _act_buffers(self, st, B, dev):
         st["w"] = self._weights(B, dev)
 
-    def _act(self, st, obs, actions):
+    def _act(self, st, obs, actions, plan=False):
         if actions is None:                    # the fused launch left the MPC's inputs in its buffers
             fg = st["fg"]
             weights, ref_speed = (fg["w"], None) if self.version == "v1" else (st["w"], fg["rs"])
         else:
             weights, ref_speed = mpc_inputs(actions, self.version, st["w"])
-        st["out"] = self.engine.predict_batch_torch(obs, weights, ref_speed, collision_cost=self.collision_cost, out=st["out"])
+        st["out"] = self.engine.predict_batch_torch(obs, weights, ref_speed, collision_cost=self.collision_cost, out=st["out"],
+                                                    **(dict(plan=True) if plan else {}))
         return st["out"]
 
     def predict(self, obs, deterministic: bool = False, generator=None):
@@ -1466,6 +1471,7 @@ class PPOAgent(_PolicyAgent):
     mpc_policy_control on a GPU; None runs the policy in torch, on any device."""
 
     DETERMINISTIC = True           # agents/ppo_agent.py's default
+    HAS_PLAN = False               # no MPC, hence no planned trajectory
     _mode = "direct"
 
     def __init__(self, policy: ActorCritic, engine=None):
@@ -1497,7 +1503,7 @@ class PPOAgent(_PolicyAgent):
         st["out"] = dict(act=st["fg"]["ctrl"] if st["fused"] else torch.zeros((B, 2), dtype=torch.float64, device=dev),
                          status=zi(), iters=zi())
 
-    def _act(self, st, obs, actions):
+    def _act(self, st, obs, actions, plan=False):
         if actions is not None:
             map_control(actions, out=st["out"]["act"], scale=st["scale"])
         return st["out"]

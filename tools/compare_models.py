@@ -140,6 +140,12 @@ def main():
     ap.add_argument("--track-alpha-vel", type=float, metavar="A", help="tracker: gain on the measured velocity, (0, 1]")
     add_actuation_flags(ap)
     add_agent_flags(ap)
+    ap.add_argument("--plan", action="store_true",
+                    help="also score every MPC agent's plan against what happened (evaluate.PlanMetrics): planned clearance, "
+                         "prediction error by lead, replanning jump; with --trace the kept episodes also hold the plans")
+    ap.add_argument("--plan-leads", type=int, nargs="+", metavar="H",
+                    help="--plan: up to four leads in steps, within the horizon (default 1, N/4, N/2, N)")
+    ap.add_argument("--plan-gap", type=float, metavar="M", help="--plan: a planned clearance below it is a conflict (default 2.5 m)")
     ap.add_argument("--trace", metavar="KEEP", help="keep the step-by-step record of episodes (evaluate.EpisodeTrace): failed, all, "
                                                      "or a comma-separated list of collision, truncated, success, unsolved")
     ap.add_argument("--trace-window", type=int, default=200, metavar="W", help="--trace: the last W steps of each kept episode")
@@ -175,17 +181,21 @@ def main():
     actuation = actuation_of(args)
     if actuation is not None:
         echo["actuation"] = {k: [finite(x) for x in v] if isinstance(v, tuple) else v for k, v in actuation.items()}
+    plan = None                          # no flag given: no plan is asked for, the launches of before
+    if args.plan or args.plan_leads or args.plan_gap is not None:
+        plan = {k: v for k, v in dict(leads=args.plan_leads and tuple(args.plan_leads), gap=args.plan_gap).items() if v is not None}
+        echo["plan"] = {k: list(v) if isinstance(v, tuple) else v for k, v in plan.items()}
     trace = None
     if args.trace:
         keep = args.trace.split(",") if "," in args.trace else args.trace
-        trace = dict(keep=keep, window=args.trace_window, capacity=args.trace_capacity)
+        trace = dict(keep=keep, window=args.trace_window, capacity=args.trace_capacity, **(dict(plan=True) if plan is not None else {}))
         os.makedirs(args.trace_dir, exist_ok=True)
     for name, agent in agents.items():
         results = {}
         s = evaluate.compare({name: agent}, make_env, args.episodes_per_env, deterministic=args.deterministic,
                              seed=args.seed, metrics=args.metrics, perception=perception,
                              interaction=args.interaction, trace=trace, tracker=tracker, actuation=actuation,
-                             results=results)[name]
+                             plan=plan, results=results)[name]
         s = {k: finite(v) for k, v in s.items()}
         if trace is not None:
             path = os.path.join(args.trace_dir, f"{name}.npz")

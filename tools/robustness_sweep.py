@@ -2,7 +2,9 @@
 tools/compare_models.py) over a grid of actuator models (evaluate.Actuation) - by default a transport delay of 0, 1, 2, 3
 policy steps without lag, then a steering lag of time constant 0, 0.2, 0.5 s without delay - on the same episodes: the same
 environment seed in every cell, every agent a fresh environment and a fresh actuator.  Prints one table per model (success
-rate, collision rate, mean steps per cell) and one JSON line with every cell's numbers.
+rate, collision rate, mean steps per cell) and one JSON line with every cell's numbers.  --plan also scores every MPC agent's
+plan against what happened (evaluate.PlanMetrics) and adds per cell the prediction error at the first and the last lead, the
+share of steps with a planned conflict and the replanning jump: whether the plans were bad or the outcome merely left them.
 
   python tools/robustness_sweep.py --envs 256 --traffic idm --fixture
   python tools/robustness_sweep.py --delays 0 2 4 6 --taus 0 1.0 --act-limits env
@@ -12,6 +14,7 @@ to 3.1 points), so differences of a few points between cells are within it.
 """
 import argparse
 import json
+import math
 import os
 import sys
 
@@ -34,6 +37,7 @@ def main():
     ap.add_argument("--taus", type=float, nargs="*", default=[0.0, 0.2, 0.5], metavar="S",
                     help="steering time constants [s], each without delay")
     ap.add_argument("--act-limits", choices=("env",), help="saturate at the environment's clamp in every cell")
+    ap.add_argument("--plan", action="store_true", help="also the plan metrics of every MPC agent, per cell")
     compare_models.add_agent_flags(ap)
     args = ap.parse_args()
 
@@ -49,18 +53,29 @@ def main():
     for delay, tau in cells:
         model = dict(delay=delay, tau=(0.0, tau), limits=args.act_limits, seed=args.seed)
         out = evaluate.compare(agents, make_env, args.episodes_per_env, deterministic=args.deterministic, seed=args.seed,
-                               actuation=model)
+                               actuation=model, plan=True if args.plan else None)
         for name, s in out.items():
             table[name].append(dict(delay=delay, tau_steer=tau, success_rate=s["success_rate"],
                                     collision_rate=s["collision_rate"], avg_steps=s["avg_steps"],
                                     act_mean_abs_dev_accel=s["act_mean_abs_dev_accel"],
-                                    act_mean_abs_dev_steer=s["act_mean_abs_dev_steer"]))
+                                    act_mean_abs_dev_steer=s["act_mean_abs_dev_steer"],
+                                    **{k: v if math.isfinite(v) else None for k, v in s.items()
+                                       if k.startswith(("pred_err_", "plan", "replan_", "min_plan"))}))
     for name, rows in table.items():
         print(f"{name}: {args.envs * args.episodes_per_env} episodes per cell, traffic {args.traffic}, seed {args.seed}")
         print("  delay [steps]  tau_steer [s]  success %  collision %  mean steps  mean |applied - command| accel, steer")
         for r in rows:
             print(f"  {r['delay']:13d}  {r['tau_steer']:13.2f}  {r['success_rate']:9.1f}  {r['collision_rate']:11.1f}  "
                   f"{r['avg_steps']:10.1f}  {r['act_mean_abs_dev_accel']:.3f}, {r['act_mean_abs_dev_steer']:.4f}")
+        leads = sorted(int(k[len("pred_err_lead"):-len("_mean")]) for k in rows[0] if k.startswith("pred_err_lead"))
+        if leads:
+            lo, hi = leads[0], leads[-1]
+            print(f"  delay [steps]  tau_steer [s]  lead-{lo} error [m]  lead-{hi} error [m]  planned conflict  replan accel, steer  "
+                  "plans valid")
+            for r in rows:
+                print(f"  {r['delay']:13d}  {r['tau_steer']:13.2f}  {r[f'pred_err_lead{lo}_mean']:16.3e}  "
+                      f"{r[f'pred_err_lead{hi}_mean']:16.3e}  {r['plan_conflict_frac']:16.4f}  {r['replan_accel_mean']:.3f}, "
+                      f"{r['replan_steer_mean']:.4f}  {r['plans_valid_frac']:.4f}")
     print(json.dumps(dict(envs=args.envs, episodes_per_env=args.episodes_per_env, traffic=args.traffic, seed=args.seed,
                           limits=args.act_limits, cells=table)), flush=True)
     if tmp is not None:
