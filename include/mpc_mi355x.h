@@ -164,6 +164,9 @@ int mpc_set_reference(mpc_handle *h, const double *ref, int32_t M);
  *   u0     [B][2]      first control (acceleration, steer) = MPC_Action    (agents/pure_mpc.py:311-318)
  *   U      [B][N][2]   full control sequence;  X [B][N+1][4] state trajectory
  *   status [B], iters [B]
+ *   Where status is MPC_STATUS_INFEASIBLE_START nothing was iterated: U holds the controls of the start and, when U, X and
+ *   status are all asked for, X their trajectory with every node written, outside the bounds as it is (without one of the
+ *   three, X behind its first node outside the bounds is left as it was).
  *   stream: hipStream_t to enqueue on (NULL = the null stream)
  */
 int mpc_solve_batch(mpc_handle *h, int32_t B, const double *state, const int32_t *ego_index, const double *vref,

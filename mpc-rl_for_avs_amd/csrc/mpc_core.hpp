@@ -226,4 +226,31 @@ MPC_HD void beta_derivs(double sb, double cb, double &bp, double &bpp) {
     bpp = 6.0 * sb * cb * q2;
 }
 
+
+// The trajectory X [N + 1][4] of the controls U [N][2] from x0 with every node written, whatever the bounds say: what an
+// infeasible start (MPC_STATUS_INFEASIBLE_START) returns next to its controls, like the oracle.  The solver's own start
+// rollout stops at the first node outside the bounds; the nodes behind it are completed with this AFTER the solve (a
+// kernel of its own on the device, the harness on the host), so that nothing is added to the solve kernels.
+MPC_HD void infeasible_start_rollout(const double *x0, const double *U, int N, double dt, double *X) {
+    TrigCoef K;
+    for (int i = 0; i < 6; ++i) {
+        K.s[i] = trig_coef(i);
+        K.c[i] = trig_coef(6 + i);
+    }
+    double x_0 = x0[0], x_1 = x0[1], x_2 = x0[2], x_3 = x0[3];
+    for (int k = 0; k <= N; ++k) {
+        X[4 * k + 0] = x_0;
+        X[4 * k + 1] = x_1;
+        X[4 * k + 2] = x_2;
+        X[4 * k + 3] = x_3;
+        if (k == N) break;
+        double Sn, Cn, sb, cb;
+        dyn_eval(K, x_2, U[2 * k + 1], Sn, Cn, sb, cb);
+        x_0 += dt * (x_3 * Cn);
+        x_1 += dt * (x_3 * Sn);
+        x_2 += dt * (x_3 * kInvWheelbase * sb);
+        x_3 += dt * U[2 * k + 0];
+    }
+}
+
 }  // namespace mpc

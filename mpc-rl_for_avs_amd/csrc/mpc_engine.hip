@@ -198,6 +198,18 @@ __global__ __launch_bounds__(kBlock, OCC) void mpc_solve_wave_kernel(
     }
 }
 
+// X of the instances that ended with MPC_STATUS_INFEASIBLE_START: the solve kernel's start rollout stops at the first node
+// outside the bounds and leaves the rows behind it as they were; one thread per instance rolls the returned controls out
+// to the end (mpc::infeasible_start_rollout).  A kernel of its own, enqueued behind the solve when U, X and status are all
+// asked for: any line added to the solve kernel itself moves the register allocation of its compiled-horizon builds.
+__global__ __launch_bounds__(256) void mpc_infeasible_start_kernel(int B, int N, double dt, const double *__restrict__ state,
+                                                                   const double *__restrict__ U,
+                                                                   const int32_t *__restrict__ status, double *__restrict__ X) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B || status[b] != MPC_STATUS_INFEASIBLE_START) return;
+    mpc::infeasible_start_rollout(state + (size_t)b * 4, U + (size_t)b * N * 2, N, dt, X + (size_t)b * (N + 1) * 4);
+}
+
 // one wave that ends `ticks` of the constant 100 MHz clock after it started (mpc_streams_overlap): the clock advances whatever
 // the wave does, so the loop ends
 __global__ __launch_bounds__(64) void mpc_timer_kernel(long long ticks) {
@@ -1577,6 +1589,11 @@ int dispatch_solve(const mpc_handle *h, int B, bool cc, int V, uint32_t flags, h
     }
 #undef MPC_LAUNCH_N
 #undef MPC_LAUNCH_W
+    if (rc == MPC_OK && d_X && d_U && d_status) {
+        hipLaunchKernelGGL(mpc_infeasible_start_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, stream, (int)B, N,
+                           h->cfg.dt, d_state, d_U, d_status, d_X);
+        HIP_TRY(hipGetLastError());
+    }
     return rc;
 }
 

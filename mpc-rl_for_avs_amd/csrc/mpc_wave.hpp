@@ -92,6 +92,9 @@ constexpr double kKappaEps = 30.0;
 // exactly 0, 1 / slack infinite, a NaN in the sweep that no regularisation repairs (status 2, seen on the GPU about once in
 // 4000 instances).  IPOPT corrects slacks that become too small likewise (Waechter & Biegler 2006, section 3.5).
 constexpr double kMinSlack = 1e-14;
+// the horizon from which the Riccati sweep symmetrises its value function at every stage (sweep4): every horizon above the
+// two with the loops compiled in (16, 20), whose builds - and the host build at the same horizons - keep the sweep they had
+constexpr int kSymFrom = 21;
 // how far inside its heading bound the cold start puts a node that zero controls would leave on or outside it (rad)
 constexpr double kInitPush = 1e-2;
 
@@ -452,6 +455,19 @@ struct Solver {
     //     M  = Luu + Pxp'B + B'T1  (Quu = M + Ppp)       qx = lx + A'px          qu = lu + B'px (+ pp)
     //     Ya = -adj(Quu) Qux (= det Kx)      and with Qs = Qux / det:
     //     Pxx' = Qxx + Qs'Ya     Pxp' = Qs'(rd adj(Quu))      px' = qx + Qs'(-adj(Quu) qu)
+    // "A symmetric matrix is its own A operand" holds for Pxx only up to the rounding of the products that made it, and
+    // A'Pxx A hands the antisymmetric part on from stage to stage, where nothing damps it (the correction Qs'Ya is symmetric):
+    // it grows with the number of stages behind it.  Measured on the host build against the oracle, which symmetrises Pxx at
+    // every stage (tests/test_iterates_cpu.py, profiles/iterate_ladder.txt): at N = 20 the iterates differ by up to 1.3e-7 at
+    // iteration 8; at N = 32 by 3.8e-7 after ONE iteration (7.4e-9 symmetrised); at N = 64 the gains of stage 0 are off by 2e-5
+    // relative in the first iteration and an iterate is 2.8e-4 away at iteration 8 (6.3e-8 symmetrised).  So from kSymFrom
+    // stages on a thirteenth product does what the oracle does, Pxx' <- (Pxx' + Pxx'^T) / 2 = Pxx' / 2 + Pxx'^T (I / 2), exact
+    // up to its one addition, in the oracle's place between two stages: on instances that are sensitive to the last bit the
+    // host build then follows the oracle's path (tests/test_core_cpu.py::test_stall_window_guard; symmetrising Qxx beside Ya
+    // instead is as stable and leaves the stage's dependency chain alone, but took another path there).  Horizons up to 20 keep
+    // the sweep as it was - the condition folds away in the builds with the horizon compiled in, whose code does not change:
+    // there the product costs 2.9 % of a batch of 4096 (N = 20: 3.74 -> 3.84 ms on Qxx, 3.89 ms on Pxx) for 1.3e-7.  What it
+    // costs the runtime-horizon builds: profiles/iterate_ladder.txt.
     // The 8x8 form needed nine products and eight block moves (22 DPP moves + 20 copies + the masks: 52 of the stage's 165
     // instructions; 145 now).  Measured (profiles/r04_sweep4.txt): a wave alone on its SIMD 33.2 -> 32.3 us per iteration,
     // a straggler 39.1 -> 37.6, config 2 0.99 -> 0.95 ms, one launch of 65 536 2.70 -> 2.80 M solves/s, 231 -> 218 registers
@@ -529,6 +545,7 @@ struct Solver {
         double pp00 = 0.0, pp01 = 0.0, pp11 = 0.0, ppv0 = 0.0, ppv1 = 0.0;    // Ppp, pp of the node behind the stage
         c.tick(T_RIC_INIT);
         const double rd_full = RD();
+        const bool sym = (CTX::kN > 0 ? CTX::kN : N) >= kSymFrom;
 #pragma unroll 1      // (two stages per trip: no gain for a lone wave, 2 % slower batches - profiles/r04_sweep4.txt)
         for (int k = N - 1; k >= 0; --k) {
             const double rdk = (k >= 1) ? rd_full : 0.0;
@@ -665,6 +682,16 @@ struct Solver {
             c.tick(T_RIC_2X2);
             dV1 += 0.5 * (kf0 * hu0 + kf1 * hu1);
             const double kp00 = rdk * i00, kp01 = rdk * i01, kp11 = rdk * i11;
+            if (sym) {
+                PerLane<double> HALF, PXS;
+                c.lanes([&](int lane_) {
+                    const int lane = c.opaque_shared(lane_);
+                    HALF.at(lane_) = (lane >> 4) == (lane & 3) ? 0.5 : 0.0;
+                    PXS.at(lane_) = 0.5 * PXXn.at(lane_);
+                });
+                c.mfma(PXXn, HALF, PXS);    // (Pxx' + Pxx'^T) / 2
+                c.lanes([&](int lane) { PXXn.at(lane) = PXS.at(lane); });
+            }
             c.lanes([&](int lane) {
                 PXX.at(lane) = PXXn.at(lane);
                 PXP.at(lane) = PXPn.at(lane);

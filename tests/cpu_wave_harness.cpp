@@ -107,6 +107,8 @@ extern "C" int wave_solve_batch_warm(int B, int N, double dt, const double *ref_
         if (X)
             for (int k = 0; k <= N; ++k)
                 for (int i = 0; i < 4; ++i) X[((size_t)b * (N + 1) + k) * 4 + i] = L[k * SL + CB + mpc::wave::W_X + i];
+        if (st == 3 && U && X)   // as mpc_infeasible_start_kernel does behind the solve
+            mpc::infeasible_start_rollout(state + 4 * (size_t)b, U + (size_t)b * N * 2, N, dt, X + (size_t)b * (N + 1) * 4);
         status[b] = st;
         iters[b] = it;
         if (kkt) kkt[b] = e;

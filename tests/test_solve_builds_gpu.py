@@ -12,27 +12,13 @@ import numpy as np
 import pytest
 
 from conftest import unexplained_disagreements
+from iterate_cases import inputs as _inputs      # the input construction, shared with the iterate ladder
 from solve_gates import TOL, agreement, certify_converged
 
 pytestmark = pytest.mark.gpu
 
 INT32_MAX, INT32_MIN = 2 ** 31 - 1, -2 ** 31
 RUNTIME_N = (1, 31, 32, 33, 63, 64)           # 32 = kLanes / 2: the last horizon with two line-search trials per pass
-
-
-def _inputs(B, N, cc, seed):
-    """Synthetic solver inputs with a reference speed profile of N + 1 stages; with the collision cost on, 8 vehicles (16 at
-    N = 64: the 8 synthetic ones and 8 copies shifted sideways, the largest workspace the interface allows)."""
-    from mpc_rl_for_avs_amd import synth
-    inp = synth.solver_inputs(B, 8, seed=seed, N=N)
-    if cc and N == 64:
-        far = inp["others"].copy()
-        far[:, :, 0] += 7.0
-        far[:, :, 1] -= 9.0
-        inp["others"] = np.ascontiguousarray(np.concatenate([inp["others"], far], axis=1))
-    if not cc:
-        inp["others"] = None
-    return inp
 
 
 def _solve(e, inp, cc, throughput):
