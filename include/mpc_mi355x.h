@@ -744,6 +744,45 @@ int mpc_actuate(int32_t device, int32_t B, int32_t reset, const mpc_actuator *pa
                 double *sums, void *stream);
 
 /*
+ * mpc_compensate (an addition within ABI 8: old clients never call it, nothing else changes) - delay compensation in front of
+ * an agent whose command takes effect `steps` policy steps after the scene it was computed from: `out` is the observation
+ * predicted to that moment.  The compensator remembers the commands still in flight, rolls the ego through them with the
+ * environment's own vehicle model behind the nominal actuator (first-order lag, rate limit, saturation; no gain, offset, noise
+ * or hold: a compensator knows its nominal actuator, not its errors), and moves every other vehicle on with its observed
+ * velocity, re-ordered by distance to the predicted ego (every formula, in evaluation order, in csrc/mpc_compensate.hpp).
+ * Device pointers, enqueue only on `stream`, never synchronises (capturable in a hipGraph); sixteen lanes per environment, four
+ * environments per wave, no LDS, no atomics, no scratch.  One launch per policy step after the scene has been sensed, with the
+ * agent's command of the step that just ran, and one with reset != 0 on the first scene.  A deployment with a known latency
+ * calls it in front of mpc_predict_batch.
+ *
+ * obs, out [B][R][8] f32 (presence, x, y, vx, vy, heading, sin_h, cos_h; row 0 the ego; finite; out must not be obs);
+ * command [B][2] f64 (acceleration m/s^2, steering rad; a NaN or infinite one counts as 0.0); done [B] u8 or NULL: the
+ * environments whose episode ended on this step, so that obs is the first scene of a new one (their memory is cleared and
+ * their command is not read); pred [B][4] f64 or NULL: the predicted ego x, y, heading, speed.  State: ring [8][B][2] f64 the
+ * last eight commands; prev [B][2] f64 the nominal applied action of the step that just ran; age [B] i32 the commands of this
+ * episode; pring [8][B][2] f64 the predicted (x, y) of the last eight launches.  counts [B] i64 += the predictions scored
+ * against the ego observed `steps` launches later; sums [2][B] f64: the sum and the maximum of that position error [m].
+ * reset != 0: every environment starts anew, counts and sums become 0, command and done are not read (both may be NULL); obs is
+ * compensated like any other scene, with no command in flight.  With steps == 0, out is obs bit for bit.
+ * Errors (MPC_ERR_INVALID_ARG): B < 0, R outside 1 .. 17, a NULL params / obs / out / ring / prev / age / pring / counts /
+ * sums, a NULL command with reset == 0, out == obs, a wrong struct_size, steps outside 0 .. 7, dt NaN or <= 0, alpha outside
+ * (0, 1], rate NaN or <= 0 (+inf is allowed), lo > hi or either NaN.  B == 0 is a no-op.
+ */
+typedef struct mpc_compensator {
+    int32_t struct_size; /* sizeof(mpc_compensator), checked like mpc_config.struct_size */
+    int32_t steps;       /* 0..7 whole policy steps to look ahead: the delay being compensated */
+    double dt;           /* s, the policy step */
+    double alpha[2];     /* nominal lag per channel (0 acceleration, 1 steering), (0, 1]; 1 = none; dt / (tau + dt) */
+    double rate[2];      /* nominal largest change per second; +inf = none */
+    double lo[2];        /* nominal saturation; -inf = none */
+    double hi[2];        /* +inf = none */
+} mpc_compensator;
+
+int mpc_compensate(int32_t device, int32_t B, int32_t R, int32_t reset, const mpc_compensator *params, const float *obs,
+                   const double *command, const uint8_t *done, float *out, double *pred, double *ring, double *prev,
+                   int32_t *age, double *pring, int64_t *counts, double *sums, void *stream);
+
+/*
  * Diagnostics: the NLP's functions at GIVEN points, evaluated by the solve kernel's own code (csrc/mpc_wave.hpp:
  * Solver::evaluate - stage_terms / track / dist, which judge every line-search trial, and the model step of the rollouts),
  * so that f(z) and g(z) computed by the reference's statements (agents/pure_mpc.py:128-283; tests/golden/

@@ -33,6 +33,7 @@
 #include "mpc_perception.hpp"
 #include "mpc_tracker.hpp"
 #include "mpc_actuator.hpp"
+#include "mpc_compensate.hpp"
 #include "mpc_interaction.hpp"
 #include "mpc_episode_stats.hpp"
 #include "mpc_episode_trace.hpp"
@@ -1313,6 +1314,74 @@ __global__ __launch_bounds__(kTraceFrameThreads) void mpc_plan_trace_kernel(mpc:
     mpc::plan::trace_env(store, in, (int)blockIdx.x, reset != 0, (int)threadIdx.x, kTraceFrameThreads, TraceBarrier{});
 }
 
+// delay compensation of a closed-loop evaluation (mpc_compensate.hpp): the mapping of mpc_track_kernel, sixteen lanes per
+// environment, four environments per wave, lane l row l + 1 of the observation (R <= 17).  The ego's part - push, score and the
+// rollout through the commands in flight - is computed by every lane of the group (the environment kernels' convention), so
+// nothing is broadcast; lane 0 alone writes the state, row 0 and pred.  The rings stay in memory and are indexed by address:
+// every load of comp::predict_ego comes before its stores, and the command just pushed is used from its register.  A present
+// row's place is the count of rows with a smaller (key, row) over fifteen 16-wide shuffles (an absent row's key is +inf: a
+// present row's is finite), which is the stable sort; an absent row takes a zero row behind them, found from the group's
+// slice of one ballot.  Every shuffle and the ballot sit in wave-uniform control flow (P.steps and R are launch arguments): a
+// lane without a row counts as absent, a group past the end computes on the last environment; only stores are predicated.  No
+// LDS, no atomics, no scratch.
+__global__ __launch_bounds__(64) void mpc_compensate_kernel(mpc::comp::Params P, mpc::comp::Buffers buf, int reset) {
+#pragma clang fp contract(off)
+    namespace comp = mpc::comp;
+    const int l = threadIdx.x & 15, g = threadIdx.x >> 4;
+    const int b_ = blockIdx.x * 4 + g;
+    const bool live = b_ < buf.B;
+    const int b = live ? b_ : buf.B - 1;
+    const int R = buf.R, i = l + 1;
+    const bool has = i < R;
+    const float *in = buf.obs + (size_t)b * R * comp::kCols;
+    float row[comp::kCols];
+#pragma unroll
+    for (int c = 0; c < comp::kCols; ++c) row[c] = in[(has ? i : 0) * comp::kCols + c];
+    const mpc::env::Ego e = comp::predict_ego(P, buf, b, reset != 0, live && l == 0);    // 1 - 4
+    float *out = buf.out + (size_t)b * R * comp::kCols;
+    if (P.steps == 0) {                                      // 8, wave-uniform: every row in place
+        if (!live) return;
+        if (has) {
+#pragma unroll
+            for (int c = 0; c < comp::kCols; ++c) out[i * comp::kCols + c] = row[c];
+        }
+        if (l == 0) {
+#pragma unroll
+            for (int c = 0; c < comp::kCols; ++c) out[c] = in[c];
+        }
+        return;
+    }
+    float ego[comp::kCols];
+    comp::ego_row(e, ego);                                                               // 5
+    const double h = (double)P.steps * P.dt;
+    const bool present = has && row[0] != 0.0f;              // no row: absent
+    const float nx = comp::advance(row[1], row[3], h), ny = comp::advance(row[2], row[4], h);        // 6
+    const double key = present ? comp::order_key(nx, ny, ego[1], ego[2]) : __builtin_huge_val();     // 7
+    int rank = 0;
+#pragma unroll
+    for (int s = 1; s < 16; ++s) {
+        const int o = (l + s) & 15;
+        const double other = __shfl(key, o, 16);
+        rank += comp::before(other, o, key, l) ? 1 : 0;
+    }
+    const unsigned present_mask = (unsigned)(__ballot(present) >> (g * 16)) & 0xFFFFu;
+    const int zero_row = 1 + (int)__popc(present_mask) + (int)__popc(~present_mask & ((1u << l) - 1u));
+    if (!live) return;                                        // nothing but stores below
+    if (present) {
+        float *o = out + (1 + rank) * comp::kCols;
+        o[0] = 1.0f, o[1] = nx, o[2] = ny;
+#pragma unroll
+        for (int c = 3; c < comp::kCols; ++c) o[c] = row[c];
+    } else if (has) {
+#pragma unroll
+        for (int c = 0; c < comp::kCols; ++c) out[zero_row * comp::kCols + c] = 0.0f;
+    }
+    if (l == 0) {
+#pragma unroll
+        for (int c = 0; c < comp::kCols; ++c) out[c] = ego[c];
+    }
+}
+
 // end of a rollout (mpc_rollout_glue.hpp: truncation bootstrap + GAE): one workgroup per environment; thread t computes the
 // terms of step t (strided over T), thread 0 runs the reversed recurrence over the LDS copies, all threads store
 __global__ __launch_bounds__(256) void mpc_rollout_finish_kernel(mpc::glue::GaeArgs g) {
@@ -2489,6 +2558,33 @@ int mpc_actuate(int32_t device, int32_t B, int32_t reset, const mpc_actuator *pa
     HIP_TRY(hipSetDevice(device));
     const act::Buffers buf{(int)B, command, done_prev, applied, state_f64, age, ctr, counts, sums};
     hipLaunchKernelGGL(mpc_actuate_kernel, dim3((unsigned)((B + 31) / 32)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream_),
+                       P, buf, (int)reset);
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_compensate(int32_t device, int32_t B, int32_t R, int32_t reset, const mpc_compensator *params, const float *obs,
+                   const double *command, const uint8_t *done, float *out, double *pred, double *ring, double *prev,
+                   int32_t *age, double *pring, int64_t *counts, double *sums, void *stream_) {
+    namespace comp = mpc::comp;
+    if (B < 0 || R < 1 || R > comp::kMaxRows)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_compensate: bad size (B >= 0, 1 <= R <= 17)");
+    if (!params || !obs || !out || !ring || !prev || !age || !pring || !counts || !sums)
+        return fail(MPC_ERR_INVALID_ARG,
+                    "mpc_compensate: null params / obs / out / ring / prev / age / pring / counts / sums pointer");
+    if (reset == 0 && !command)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_compensate: null command pointer in a launch without reset");
+    if (out == obs) return fail(MPC_ERR_INVALID_ARG, "mpc_compensate: out must not be obs");
+    if (params->struct_size != (int32_t)sizeof(mpc_compensator))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_compensate: mpc_compensator.struct_size mismatch");
+    const mpc_compensator &p = *params;
+    const comp::Params P{p.dt, {p.alpha[0], p.alpha[1]}, {p.rate[0], p.rate[1]}, {p.lo[0], p.lo[1]}, {p.hi[0], p.hi[1]}, p.steps};
+    if (const char *why = comp::refusal(P))
+        return fail(MPC_ERR_INVALID_ARG, std::string("mpc_compensate: bad parameter (") + why + ")");
+    if (B == 0) return MPC_OK;
+    HIP_TRY(hipSetDevice(device));
+    const comp::Buffers buf{(int)B, (int)R, obs, command, done, out, pred, ring, prev, age, pring, counts, sums};
+    hipLaunchKernelGGL(mpc_compensate_kernel, dim3((unsigned)((B + 3) / 4)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream_),
                        P, buf, (int)reset);
     HIP_TRY(hipGetLastError());
     return MPC_OK;

@@ -1,6 +1,6 @@
 """ctypes binding of the C ABI (include/mpc_mi355x.h) - the only way Python reaches the HIP kernels: the entry points that
 take an engine handle through `MPCEngine`'s methods, the handle-less ones (environment step, policy step, rollout glue,
-evaluation accounting, perception, episode traces, tracker, plan metrics, actuator) through `call` / `caller`, by parameter
+evaluation accounting, perception, episode traces, tracker, plan metrics, actuator, delay compensation) through `call` / `caller`, by parameter
 name, in the order of `SIGNATURES`, `EVALUATION_SIGNATURES`, `TRACKER_SIGNATURES`, `PLAN_SIGNATURES` and
 `ACTUATION_SIGNATURES`.
 
@@ -70,9 +70,15 @@ class ActuatorParams(ctypes.Structure):
         [("seed", ctypes.c_uint64)]
 
 
+class CompensatorParams(ctypes.Structure):
+    """mpc_compensator of include/mpc_mi355x.h (csrc/mpc_compensate.hpp has the model); the per-channel fields take a pair."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("steps", ctypes.c_int32), ("dt", ctypes.c_double)] + \
+        [(name, ctypes.c_double * 2) for name in ("alpha", "rate", "lo", "hi")]
+
+
 # The handle-less entry points: every parameter of the prototype in include/mpc_mi355x.h, in its order, as name:kind - i32
 # (int32_t), u64 (uint64_t), f64 (double), ptr (any pointer, the stream included), perception (const mpc_perception *),
-# actuator (const mpc_actuator *).
+# actuator (const mpc_actuator *), compensator (const mpc_compensator *).
 # load_library builds their argtypes from this table and `caller` orders its named arguments by it; tests/test_abi.py holds
 # it against the header.
 _POLICY_IN = "obs:ptr w1:ptr b1:ptr w2:ptr b2:ptr wh:ptr bh:ptr"
@@ -85,7 +91,8 @@ _CONTROL = (f"device:i32 B:i32 H2:i32 {_POLICY_IN} std_:ptr c0:ptr noise:ptr noi
             f"{_POLICY_OUT} control:ptr stream:ptr")
 _RECORDS = "state_i32:ptr state_f64:ptr rec_i32:ptr rec_f64:ptr"
 _KINDS = dict(i32=ctypes.c_int32, u64=ctypes.c_uint64, f64=ctypes.c_double, ptr=ctypes.c_void_p,
-              perception=ctypes.POINTER(PerceptionParams), actuator=ctypes.POINTER(ActuatorParams))
+              perception=ctypes.POINTER(PerceptionParams), actuator=ctypes.POINTER(ActuatorParams),
+              compensator=ctypes.POINTER(CompensatorParams))
 SIGNATURES = {name: tuple(tuple(word.split(":")) for word in text.split()) for name, text in dict(
     mpc_synth_env_step=f"{_SYNTH_IN} {_SYNTH_OUT}",
     mpc_synth_env_step_idm=f"{_SYNTH_IN} oroute:ptr oprog:ptr otarget:ptr {_SYNTH_OUT}",
@@ -137,12 +144,18 @@ ACTUATION_SIGNATURES = {name: tuple(tuple(word.split(":")) for word in text.spli
     mpc_actuate="device:i32 B:i32 reset:i32 params:actuator command:ptr done_prev:ptr applied:ptr state_f64:ptr age:ptr "
                 "ctr:ptr counts:ptr sums:ptr stream:ptr").items()}
 _TABLES = (SIGNATURES, EVALUATION_SIGNATURES, TRACKER_SIGNATURES, PLAN_SIGNATURES, ACTUATION_SIGNATURES)
+# The delay compensation of the evaluation (csrc/mpc_compensate.hpp), likewise, in a table of its own beside _TABLES;
+# tests/test_compensate_cpu.py holds this one against the header.
+COMPENSATION_SIGNATURES = {name: tuple(tuple(word.split(":")) for word in text.split()) for name, text in dict(
+    mpc_compensate="device:i32 B:i32 R:i32 reset:i32 params:compensator obs:ptr command:ptr done:ptr out:ptr pred:ptr "
+                   "ring:ptr prev:ptr age:ptr pring:ptr counts:ptr sums:ptr stream:ptr").items()}
+_ALL_TABLES = _TABLES + (COMPENSATION_SIGNATURES,)
 
 _EXPORTS = ["mpc_version", "mpc_last_error", "mpc_default_config", "mpc_default_config_sized", "mpc_create", "mpc_destroy",
             "mpc_set_reference", "mpc_solve_batch", "mpc_workspace_bytes", "mpc_predict_batch", "mpc_predict_batch_plan",
             "mpc_reset_env_state", "mpc_reset_env_mask", "mpc_get_env_state", "mpc_get_last_inputs",
             "mpc_ltv_solve_batch", "mpc_ltv_predict_batch", "mpc_ltv_predict_batch_plan", "mpc_env_state_bytes", "mpc_save_env_state",
-            "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_policy_control", "mpc_policy_control_tile", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_interaction_metrics", "mpc_episode_trace", "mpc_plan_metrics", "mpc_plan_trace", "mpc_perceive", "mpc_track_rows", "mpc_actuate", "mpc_eval_nlp", "mpc_streams_overlap"]
+            "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_policy_control", "mpc_policy_control_tile", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_interaction_metrics", "mpc_episode_trace", "mpc_plan_metrics", "mpc_plan_trace", "mpc_perceive", "mpc_track_rows", "mpc_actuate", "mpc_compensate", "mpc_eval_nlp", "mpc_streams_overlap"]
 ABI_VERSION = 8          # MPC_ABI_VERSION of include/mpc_mi355x.h this binding is written for
 MAX_OTHERS = 16
 _lib = None
@@ -225,7 +238,7 @@ def load_library(path: str | None = None):
     lib.mpc_set_diagnostics.restype = ctypes.c_int
     lib.mpc_get_last_paths.argtypes = [vp, ctypes.c_int32, dp, ip, vp]
     lib.mpc_get_last_paths.restype = ctypes.c_int
-    for name, sig in [item for table in _TABLES for item in table.items()]:
+    for name, sig in [item for table in _ALL_TABLES for item in table.items()]:
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = [_KINDS[kind] for _, kind in sig], ctypes.c_int
     lib.mpc_eval_nlp.argtypes = [vp, ctypes.c_int32] + [vp] * 5 + [ctypes.c_int32, ctypes.c_uint32] + [vp] * 4
@@ -246,7 +259,8 @@ def _caller(name, sig):
     an eager step makes three such calls: Python binds the keywords to the names itself, and raises the TypeError that
     names the entry point and the missing or unexpected parameter."""
     convert = dict(i32="{0}", u64="{0}", f64="{0}", ptr="None if {0} is None else c_void_p({0}.data_ptr())",
-                   perception="None if {0} is None else byref({0})", actuator="None if {0} is None else byref({0})")
+                   perception="None if {0} is None else byref({0})", actuator="None if {0} is None else byref({0})",
+                   compensator="None if {0} is None else byref({0})")
     args = ", ".join("_stream_handle(stream)" if n == "stream" else convert[kind].format(n) for n, kind in sig)
     scope = dict(c_void_p=ctypes.c_void_p, byref=ctypes.byref, _stream_handle=_stream_handle, EngineError=EngineError,
                  load_library=load_library)
@@ -259,15 +273,15 @@ def _caller(name, sig):
     return scope[name]
 
 
-_CALLERS = {name: _caller(name, sig) for table in _TABLES for name, sig in table.items()}
+_CALLERS = {name: _caller(name, sig) for table in _ALL_TABLES for name, sig in table.items()}
 
 
 def caller(name: str):
     """The handle-less entry point `name` as a function of keywords alone: every one of SIGNATURES[name] (or
-    EVALUATION_SIGNATURES[name], TRACKER_SIGNATURES[name], PLAN_SIGNATURES[name], ACTUATION_SIGNATURES[name]) and no other (TypeError
+    EVALUATION_SIGNATURES[name], TRACKER_SIGNATURES[name], PLAN_SIGNATURES[name], ACTUATION_SIGNATURES[name], COMPENSATION_SIGNATURES[name]) and no other (TypeError
     naming the entry point and the parameter otherwise, before anything is called).  Python ints and floats pass through;
     a pointer is a torch tensor (its address; a bool tensor's bytes are the uint8 the kernels read) or None; `stream` is a
-    torch stream, its raw handle or None; `params` of mpc_perceive a PerceptionParams, of mpc_actuate an ActuatorParams.  Enqueue only; EngineError with the
+    torch stream, its raw handle or None; `params` of mpc_perceive a PerceptionParams, of mpc_actuate an ActuatorParams, of mpc_compensate a CompensatorParams.  Enqueue only; EngineError with the
     library's text when the entry point refuses.  lib: the library, load_library() by default."""
     return _CALLERS[name]
 

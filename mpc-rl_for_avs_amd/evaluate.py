@@ -49,6 +49,12 @@ states and controls the solve ended with) and scores it against what happened (c
 clearance to the vehicles the agent saw, the ego's distance from where earlier plans put it, and the jump between consecutive
 plans, per episode, inside the same captured step (mpc_plan_metrics), or by the same update in numpy on the CPU path.  A trace
 recorder with plan=True keeps the plan of every step of the episodes it keeps (mpc_plan_trace).
+
+`compensation=` puts a delay compensator (csrc/mpc_compensate.hpp, `Compensation`) in front of the agent: the agent's command
+takes effect `steps` policy steps after the scene it was computed from, so the agent acts on the scene predicted to that moment
+- the ego rolled through the commands still in flight with the environment's own vehicle model behind the nominal actuator, the
+others moved on with their observed velocity - inside the same captured step (mpc_compensate), or by the same update in numpy
+on the CPU path.
 """
 from __future__ import annotations
 
@@ -102,6 +108,9 @@ TRACK_SLOTS, TRACK_MAX_COAST, TRACK_NO_SLOT = 16, 200, 255
 ACTUATION_COUNTS = ("steps", "held", "rate_limited", "saturated", "nonfinite")             # mpc_actuate counts [5][B]
 ACTUATION_SALT, ACT_RING, ACT_MAX_DELAY, ACT_LAST, ACT_PREV = 0x9FB21C651E98DF25, 8, 7, 8, 9
 ENV_LIMITS = ((-5.0, 5.0), (-math.pi / 4, math.pi / 4))
+# csrc/mpc_compensate.hpp: the ring's length, the longest look-ahead; csrc/mpc_synth_env.hpp::step_ego: the wheelbase and the
+# largest speed
+COMP_RING, COMP_MAX_STEPS, ENV_WHEELBASE, ENV_MAX_SPEED = 8, 7, 2.5, 30.0
 # csrc/mpc_plan.hpp: the records of mpc_plan_metrics (lead{i}: the i-th of its four leads), the planes of its running state,
 # the leads per launch, MPC_MAX_HORIZON
 PLAN_I32 = ("steps", "plans_valid", "plan_conflict_steps", "replan_n") + tuple(f"lead{i}_n" for i in range(4))   # rec_i32 [8][B][Q]
@@ -1364,6 +1373,205 @@ def _pair_of_pairs(limits):
         raise ValueError("limits must be None, 'env' or ((lo, hi), (lo, hi))") from None
 
 
+def _step_ego(x, y, th, sp, action, dt):
+    """csrc/mpc_synth_env.hpp::step_ego over the batch: action [B, 2] -> the next (x, y, th, sp)"""
+    a = np.clip(action[:, 0], ENV_LIMITS[0][0], ENV_LIMITS[0][1])
+    delta = np.clip(action[:, 1], ENV_LIMITS[1][0], ENV_LIMITS[1][1])
+    beta = np.arctan(0.5 * np.tan(delta))
+    nx = x + sp * np.cos(th + beta) * dt
+    ny = y + sp * np.sin(th + beta) * dt
+    nth = th + sp / ENV_WHEELBASE * np.sin(beta) * dt
+    return nx, ny, nth, np.clip(sp + a * dt, 0.0, ENV_MAX_SPEED)
+
+
+class Compensation:
+    """Delay compensation in front of the agent (csrc/mpc_compensate.hpp states the update step by step): the agent's command
+    takes effect `steps` whole policy steps (0..7) after the scene it was computed from, so the agent is handed the scene
+    predicted to that moment.  The compensator keeps the commands still in flight, rolls the ego through them with the
+    environment's own vehicle model behind the NOMINAL actuator - a first-order lag of time constant `tau` [s] per channel
+    (alpha = dt / (tau + dt), formed once here), at most `rate` per second, clamped to `limits` (None, "env" or
+    ((lo, hi), (lo, hi)), as `Actuation` reads them); no gain, offset, noise or hold: a compensator knows its nominal
+    actuator, not its errors - and moves every other vehicle on with its observed velocity, re-ordered by distance to the
+    predicted ego.  With steps = 0 the output is the input bit for bit.  `Compensation.matching(actuation)` takes the delay,
+    tau, rate and limits of an `Actuation`.  The parameters are fixed at construction.
+
+    `apply(obs, out, command, done)` fills `out` [B, R, 8] f32 (not `obs`) from the observation `obs` and the agent's command
+    [B, 2] f64 of the step that just ran, and returns it; done [B]: the environments whose episode ended on that step (their
+    memory is cleared, their command is not read).  `apply(obs, out, reset=True)` starts every environment anew on its first
+    scene and needs no command; `reset()` only clears.  `pred` [B, 4] f64 is the predicted ego (x, y, heading, speed) of the
+    last launch; `ring` [8, B, 2] f64 the last eight commands, `prev` [B, 2] f64 the nominal applied action of the step that
+    just ran, `age` [B] i32 the commands of the episode, `pring` [8, B, 2] f64 the predicted (x, y) of the last eight
+    launches; `counts` [B] i64 the predictions scored against the ego observed `steps` launches later, `sums` [2, B] f64 the
+    sum and the maximum of that position error [m].  Backend "hip" is the kernel (mpc_compensate, enqueue only, capturable);
+    backend "torch" is the same update in numpy for the CPU environment: the same bits wherever only + - * and comparisons
+    are involved, and equal to the rounding of the library's sqrt, sin, cos, tan and atan in the ego's rollout."""
+
+    def __init__(self, B: int, device, backend: str = "torch", R: int = VEHICLES_COUNT, dt: float = 0.1, steps: int = 0,
+                 tau=(0.0, 0.0), rate=(math.inf, math.inf), limits=None):
+        if backend not in ("hip", "torch"):
+            raise ValueError("backend must be 'hip' or 'torch'")
+        if int(B) < 0:
+            raise ValueError("B must be >= 0")
+        if not 1 <= int(R) <= MAX_ROWS:
+            raise ValueError(f"R must be in 1..{MAX_ROWS}")
+        if not float(dt) > 0.0:
+            raise ValueError("dt must be > 0")
+        if int(steps) != steps or not 0 <= int(steps) <= COMP_MAX_STEPS:
+            raise ValueError(f"steps must be an integer 0..{COMP_MAX_STEPS}")
+        tau, rate = _pair("tau", tau), _pair("rate", rate)
+        if limits is None:
+            limits = ((-math.inf, math.inf), (-math.inf, math.inf))
+        elif isinstance(limits, str):
+            if limits != "env":
+                raise ValueError("limits must be None, 'env' or ((lo, hi), (lo, hi))")
+            limits = ENV_LIMITS
+        limits = tuple(_pair("limits", v) for v in _pair_of_pairs(limits))
+        for c in (0, 1):
+            if not (tau[c] >= 0.0 and math.isfinite(tau[c])):
+                raise ValueError("tau must be >= 0 and finite")
+            if not rate[c] > 0.0:
+                raise ValueError("rate must be > 0 (inf: no limit)")
+            if not limits[c][0] <= limits[c][1]:
+                raise ValueError("limits must be lo <= hi")
+        self.B, self.R, self.device, self.backend = int(B), int(R), torch.device(device), backend
+        self.dt, self.steps, self.tau, self.rate, self.limits = float(dt), int(steps), tau, rate, limits
+        self.alpha = tuple(self.dt / (t + self.dt) for t in tau)
+        if not all(0.0 < a <= 1.0 for a in self.alpha):
+            raise ValueError("tau is too large for dt: alpha = dt / (tau + dt) must be in (0, 1]")
+        z = lambda *s, dt: torch.zeros(s, dtype=dt, device=self.device)
+        self.ring, self.pring = z(COMP_RING, self.B, 2, dt=torch.float64), z(COMP_RING, self.B, 2, dt=torch.float64)
+        self.prev, self.pred = z(self.B, 2, dt=torch.float64), z(self.B, 4, dt=torch.float64)
+        self.age, self.counts, self.sums = z(self.B, dt=torch.int32), z(self.B, dt=torch.int64), z(2, self.B, dt=torch.float64)
+        pair = lambda v: (ctypes.c_double * 2)(*v)
+        self._params = _engine.CompensatorParams(
+            struct_size=ctypes.sizeof(_engine.CompensatorParams), steps=self.steps, dt=self.dt, alpha=pair(self.alpha),
+            rate=pair(rate), lo=pair((limits[0][0], limits[1][0])), hi=pair((limits[0][1], limits[1][1])))
+
+    @classmethod
+    def matching(cls, actuation, R: int = VEHICLES_COUNT) -> "Compensation":
+        """The compensator of `actuation`'s nominal model: its batch, device, backend and dt, its delay as `steps`, its tau,
+        rate and limits - and none of its errors (gain, offset, noise, hold)."""
+        return cls(actuation.B, actuation.device, actuation.backend, R=R, dt=actuation.dt, steps=actuation.delay,
+                   tau=actuation.tau, rate=actuation.rate, limits=actuation.limits)
+
+    @property
+    def config(self) -> dict:
+        """The keyword arguments that make a Compensation with the same model."""
+        return dict(R=self.R, dt=self.dt, steps=self.steps, tau=self.tau, rate=self.rate, limits=self.limits)
+
+    def reset(self) -> None:
+        """Forget everything: the commands in flight, the nominal actuator's state, the predictions, the counts, the sums.
+        `apply(..., reset=True)` does the same and then compensates the first scene."""
+        for t in (self.ring, self.pring, self.prev, self.age, self.counts, self.sums):
+            t.zero_()
+
+    def apply(self, obs, out, command=None, done=None, reset: bool = False):
+        B, R, dev = self.B, self.R, self.device
+        _check(obs, "obs", (B, R, 8), torch.float32, dev)
+        _check(out, "out", (B, R, 8), torch.float32, dev)
+        if out is obs or (B > 0 and out.data_ptr() == obs.data_ptr()):
+            raise ValueError("out must not be obs")
+        if not reset:
+            _check(command, "command", (B, 2), torch.float64, dev)
+        if done is not None:
+            done = _check(done, "done", (B,), torch.uint8, dev)
+        if self.backend == "torch":
+            o, pred = self._numpy_apply(obs.cpu().numpy(), None if reset else command.cpu().numpy(),
+                                        None if done is None else done.cpu().numpy(), bool(reset))
+            out.copy_(torch.from_numpy(o))
+            if self.pred is not None:
+                self.pred.copy_(torch.from_numpy(pred))
+        else:
+            _engine.caller("mpc_compensate")(
+                device=dev.index, B=B, R=R, reset=1 if reset else 0, params=self._params, obs=obs,
+                command=None if reset else command, done=None if reset else done, out=out, pred=self.pred, ring=self.ring,
+                prev=self.prev, age=self.age, pring=self.pring, counts=self.counts, sums=self.sums,
+                stream=_engine.current_stream(dev))
+        return out
+
+    def _shape(self, delayed, prev):
+        """act::shape of the nominal actuator (steps 6 - 8 of csrc/mpc_actuator.hpp) on [B, 2], the channels one after the other"""
+        y = np.empty_like(delayed)
+        for c in (0, 1):
+            v, p = delayed[:, c], prev[:, c]
+            yc = v
+            if self.alpha[c] != 1.0:                                               # 6
+                yc = p + self.alpha[c] * (v - p)
+            if math.isfinite(self.rate[c]):                                        # 7
+                m, d = self.rate[c] * self.dt, yc - p
+                yc = np.where(d > m, p + m, np.where(d < -m, p - m, yc))
+            lo, hi = self.limits[c]                                                # 8
+            yc = np.where(yc < lo, lo, yc)
+            y[:, c] = np.where(yc > hi, hi, yc)
+        return y
+
+    def _numpy_apply(self, obs, cmd, done, reset):
+        """csrc/mpc_compensate.hpp over the batch: every statement acts on all environments -> (out, pred)"""
+        B, d, dt, f64 = self.B, self.steps, self.dt, np.float64
+        ring, pring, prev, age, counts, sums = (t.cpu().numpy() for t in (self.ring, self.pring, self.prev, self.age,
+                                                                          self.counts, self.sums))
+        env, last = np.arange(B), COMP_RING - 1
+        clear = np.ones(B, bool) if reset else np.zeros(B, bool) if done is None else done != 0
+        ring[:, clear], pring[:, clear], prev[clear], age[clear] = 0.0, 0.0, 0.0, 0    # 1
+        if reset:
+            counts[:], sums[:] = 0, 0.0
+        push = ~clear
+        with np.errstate(invalid="ignore", over="ignore"):
+            if push.any():                                                         # 2
+                u = np.where((cmd - cmd) == 0.0, cmd, 0.0)
+                ring[(age & last)[push], env[push]] = u[push]
+                delayed = np.where((age >= d)[:, None], ring[(age - d) & last, env], 0.0)
+                prev[push] = self._shape(delayed, prev)[push]
+                age[push] += 1
+            x0, y0 = obs[:, 0, 1].astype(f64), obs[:, 0, 2].astype(f64)
+            if d > 0:                                                              # 3
+                scored = age >= d
+                p = pring[(age - d) & last, env]
+                dx, dy = p[:, 0] - x0, p[:, 1] - y0
+                e = np.sqrt(dx * dx + dy * dy)
+                counts[scored] += 1
+                sums[0, scored] += e[scored]
+                sums[1] = np.where(scored & (e > sums[1]), e, sums[1])
+            vx, vy = obs[:, 0, 3].astype(f64), obs[:, 0, 4].astype(f64)                # 4
+            x, y, th, sp = x0, y0, obs[:, 0, 5].astype(f64), np.sqrt(vx * vx + vy * vy)
+            p = prev.copy()
+            for k in range(d):
+                i = age - d + k
+                p = self._shape(np.where((i >= 0)[:, None], ring[i & last, env], 0.0), p)
+                x, y, th, sp = _step_ego(x, y, th, sp, p, dt)
+            pring[age & last, env] = np.stack([x, y], axis=1)
+            pred = np.stack([x, y, th, sp], axis=1)
+            if d == 0:                                                             # 8
+                out = obs.copy()
+            else:
+                s, c = np.sin(th), np.cos(th)                                          # 5
+                out = np.zeros_like(obs)
+                out[:, 0] = np.stack([np.ones(B), x, y, sp * c, sp * s, th, s, c], axis=1).astype(np.float32)
+                h = float(d) * dt                                                  # 6
+                rows = obs[:, 1:]
+                present = rows[:, :, 0] != 0.0
+                moved = rows.copy()
+                moved[:, :, 0] = 1.0
+                moved[:, :, 1] = (rows[:, :, 1].astype(f64) + rows[:, :, 3].astype(f64) * h).astype(np.float32)
+                moved[:, :, 2] = (rows[:, :, 2].astype(f64) + rows[:, :, 4].astype(f64) * h).astype(np.float32)
+                moved[~present] = 0.0
+                kx = moved[:, :, 1].astype(f64) - out[:, 0, 1].astype(f64)[:, None]        # 7
+                ky = moved[:, :, 2].astype(f64) - out[:, 0, 2].astype(f64)[:, None]
+                key = np.where(present, kx * kx + ky * ky, np.inf)
+                order = np.argsort(key, axis=1, kind="stable")                     # ties, and the absent rows, in row order
+                out[:, 1:] = np.take_along_axis(moved, order[:, :, None], axis=1)
+        _write_back(((self.ring, ring), (self.pring, pring), (self.prev, prev), (self.age, age), (self.counts, counts),
+                     (self.sums, sums)))
+        return out, pred
+
+    def totals(self) -> dict:
+        """Since the reset, over the environments: scored (the predictions that were compared with the ego observed `steps`
+        launches later), pos_err_mean and pos_err_max [m]: the mean and the maximum of their position error."""
+        scored = int(self.counts.sum().item())
+        s = self.sums.cpu().numpy()
+        return dict(scored=scored, pos_err_mean=float(s[0].sum()) / max(scored, 1), pos_err_max=float(s[1].max(initial=0.0)))
+
+
 def _keep_bits(keep) -> int:
     names = (keep,) if isinstance(keep, str) else tuple(keep)
     bits = 0
@@ -1665,7 +1873,8 @@ class EvalResult:
     totals of the actuator model (`Actuation.totals()`: steps, held, rate_limited, saturated, nonfinite, mean_abs_dev and
     max_abs_dev per channel, idle steps included) when the evaluation ran with one, else None; plan: the plan metrics'
     records (`PlanMetrics.records()`: dict of numpy arrays [B, Q], keys PLAN_I32 + PLAN_F64, the same slots, and `leads`) when
-    the evaluation ran with plan=, else None."""
+    the evaluation ran with plan=, else None; compensation: the totals of the delay compensator (`Compensation.totals()`:
+    scored, pos_err_mean, pos_err_max) when the evaluation ran with one, else None."""
     records: dict
     dt: float
     steps: int
@@ -1678,6 +1887,7 @@ class EvalResult:
     tracker: dict | None = None
     actuation: dict | None = None
     plan: dict | None = None
+    compensation: dict | None = None
 
     @property
     def travel_time(self):
@@ -1705,7 +1915,9 @@ class EvalResult:
         plan_conflict_frac (steps whose planned clearance was below the gap, over the steps with a valid plan), min_plan_gap
         (the smallest of any episode, inf when there is none), pred_err_lead{h}_mean for every lead h in use (the mean
         distance between the ego and where the plan of h steps before put it, over all scored steps; 0 when there is none)
-        and replan_accel_mean [m/s^2], replan_steer_mean [rad] (the mean replanning jump over all scored steps)."""
+        and replan_accel_mean [m/s^2], replan_steer_mean [rad] (the mean replanning jump over all scored steps).  With a
+        delay compensator also comp_pos_err_mean and comp_pos_err_max [m]: the mean and the largest distance between the ego
+        it predicted and the ego observed `steps` steps later."""
         out = self._base_summary()
         if self.drive is not None:
             out.update(self._drive_summary())
@@ -1723,6 +1935,8 @@ class EvalResult:
             out.update(act_mean_abs_dev_accel=float(a["mean_abs_dev"][0]), act_mean_abs_dev_steer=float(a["mean_abs_dev"][1]))
         if self.plan is not None:
             out.update(self._plan_summary())
+        if self.compensation is not None:
+            out.update(comp_pos_err_mean=self.compensation["pos_err_mean"], comp_pos_err_max=self.compensation["pos_err_max"])
         return out
 
     def _plan_summary(self) -> dict:
@@ -1797,7 +2011,7 @@ def _instance(cls, given, defaults: dict, *args):
 def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = False, reset_mpc_on_done: bool = False,
                    use_graph: bool | None = None, poll_every: int = 16, seed: int = 0, on_step=None,
                    metrics: bool = False, perception=None, interaction: bool = False, trace=None,
-                   tracker=None, actuation=None, plan=None) -> EvalResult:
+                   tracker=None, actuation=None, plan=None, compensation=None) -> EvalResult:
     """Run `agent` in closed loop on the B environments of `env` (a SyntheticIntersectionEnv) until each environment has
     finished `episodes_per_env` episodes; returns their records.
 
@@ -1849,6 +2063,16 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     on is the previous call's obs, or seen).  A trace recorder with
     plan=True (a dict of its arguments gets horizon from the agent) asks for the plan in the same way.  ValueError for an
     agent without a plan (PPOAgent) and for leads beyond the horizon.  None: no launch, no buffer, nothing changes.
+    compensation: a `Compensation` for this environment's batch, a dict of its keyword arguments (dt defaults to the
+    environment's), or True for `Compensation.matching(actuation)` (ValueError without an actuator model).  The agent then
+    acts on a buffer of its own, `ahead` = compensation.apply(what it would otherwise act on), filled right after perception
+    and tracker: after the reset with reset=True, which also clears the compensator, so the graph's warm-up and capture steps
+    leave no trace, and inside the step (so inside the captured graph) with the step's `done` and the agent's command - not
+    the applied action: the compensator knows the nominal actuator, not the real one.  `seen` - on_step's, the frame's and
+    the trace recorder's (seen=True is then allowed with a compensator alone) - is `ahead`, what the agent acted on; on_step's
+    dict also holds it as ahead.  EvalResult.compensation holds the totals.  ValueError with plan= or a trace with plan=True
+    when steps > 0: the plan then starts `steps` later than the plan metrics' leads assume.  None: no launch, no buffer,
+    nothing changes.
     Every episode ends by EPISODE_STEPS (200) steps, so Q * 200 steps bound the loop; RuntimeError if the episodes are not
     all recorded by then."""
     Q = int(episodes_per_env)
@@ -1885,8 +2109,19 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     # with an actuator model: what the environment is handed, and the `done` of the previous step (zero after the reset)
     applied = torch.zeros((B, 2), dtype=torch.float64, device=dev) if actuation is not None else None
     ended = torch.zeros(B, dtype=torch.uint8, device=dev) if actuation is not None else None
-    filtered = perception is not None or tracker is not None       # the agent acts on something other than the true scene
+    if compensation is True:
+        if actuation is None:
+            raise ValueError("compensation=True is Compensation.matching(actuation): it needs an actuator model")
+        compensation = Compensation.matching(actuation, R=VEHICLES_COUNT)
+    compensation = _instance(Compensation, compensation, dict(R=VEHICLES_COUNT, dt=float(env.dt)), B, dev, backend)
+    if compensation is not None and (compensation.B != B or compensation.R != VEHICLES_COUNT or compensation.device != dev):
+        raise ValueError(f"compensation must be built for {B} environments of {VEHICLES_COUNT} rows on {dev}")
+    sensing = perception is not None or tracker is not None        # `obs` is something other than the true scene
+    filtered = sensing or compensation is not None                 # the agent acts on something other than the true scene
     sensed = torch.zeros_like(obs) if perception is not None and tracker is not None else None    # between the two
+    # with a compensator: the predicted scene, what the agent acts on
+    ahead = torch.zeros_like(obs) if compensation is not None else None
+    acting = obs if compensation is None else ahead
     horizon = getattr(eng, "horizon", None)
     plan = {} if plan is True else None if plan is False else plan
     trace_plan = bool(trace.get("plan")) if isinstance(trace, dict) else bool(getattr(trace, "plan", False))
@@ -1894,13 +2129,16 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     if wants_plan and (not getattr(agent, "HAS_PLAN", True) or horizon is None or
                        "plan" not in inspect.signature(agent.act_batch_torch).parameters):
         raise ValueError(f"{type(agent).__name__} has no plan: plan= and a trace with plan=True need an MPC agent")
+    if wants_plan and compensation is not None and compensation.steps > 0:
+        raise ValueError("plan= and a trace with plan=True are not supported with a compensator of steps > 0: the plan then "
+                         "starts `steps` later than the plan metrics' leads assume")
     trace = _instance(EpisodeTrace, trace, dict(R=VEHICLES_COUNT, env_offset=offset, seen=filtered,
                                                 **(dict(horizon=horizon) if trace_plan else {})), B, Q, dev, backend)
     if trace is not None:
         if (trace.B, trace.Q, trace.R, trace.device) != (B, Q, VEHICLES_COUNT, dev):
             raise ValueError(f"trace must be built for {B} environments, {Q} episodes each, {VEHICLES_COUNT} rows, on {dev}")
         if trace.seen and not filtered:
-            raise ValueError("trace records seen=True only with a perception model or a tracker")
+            raise ValueError("trace records seen=True only with a perception model, a tracker or a compensator")
         if trace.plan and trace.N != horizon:
             raise ValueError(f"trace keeps plans of horizon {trace.N}, the agent's is {horizon}")
     planm = _instance(PlanMetrics, plan, dict(N=horizon, R=VEHICLES_COUNT, dt=float(env.dt)), B, Q, dev, backend)
@@ -1922,7 +2160,7 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     # perception model also the true observation, what the agent gets next and (below) the class of every row
     shown = ("ego", "done", "truncated", "crashed", "arrived", "reward", "status", "iters") + \
         (("terminal_obs", "obs", "act") if metrics else ()) + (("obs", "seen") if filtered else ()) + \
-        (("act", "command") if actuation is not None else ()) + \
+        (("act", "command") if actuation is not None else ()) + (("ahead",) if compensation is not None else ()) + \
         (("plan_X", "plan_U", "plan_order") if wants_plan else ())
 
     def show(frame, **first):
@@ -1935,7 +2173,7 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
 
     def sense(true, reset=False, done=None):
         """`obs` <- what the agent gets of the true observation"""
-        if not filtered:
+        if not sensing:
             obs.copy_(true)
         elif tracker is None:
             perception.apply(true, obs, reset=reset)
@@ -1944,7 +2182,7 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
             tracker.apply(meas, obs, done=done, reset=reset)
 
     def step():
-        out = agent.act_batch_torch(obs, **kw)
+        out = agent.act_batch_torch(acting, **kw)
         act = out["act"] if actuation is None else actuation.apply(out["act"], applied, done_prev=ended)
         new_obs, reward, done, info = env.step(act)
         if reset_mpc_on_done and eng is not None:
@@ -1955,21 +2193,27 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
                      done=done, truncated=info["truncated"], crashed=info["crashed"], arrived=info["arrived"],
                      status=out["status"], iters=out["iters"], step=out.get("step"))
         if filtered:
-            frame["seen"] = obs       # still what the agent acted on while the observers run; what it gets next after them
+            frame["seen"] = acting    # still what the agent acted on while the observers run; what it gets next after them
         if actuation is not None:
             frame["command"] = out["act"]
+        if compensation is not None:
+            frame["ahead"] = ahead
         if wants_plan:                # `acted`: the observation the agent acted on, until `sense` overwrites it
-            frame.update(plan_X=out["plan_X"], plan_U=out["plan_U"], plan_order=out["plan_order"], acted=obs)
+            frame.update(plan_X=out["plan_X"], plan_U=out["plan_U"], plan_order=out["plan_order"], acted=acting)
         for o in observers:
             o.observe(frame)
         if actuation is not None:
             ended.copy_(done)
         sense(new_obs, done=done)
+        if compensation is not None:
+            compensation.apply(obs, ahead, command=out["act"], done=done)
         return out, frame
 
     def first_obs(reset):
         true = env.reset()
         sense(true, reset=reset)
+        if compensation is not None:  # a scene without a command: always a reset launch, which also clears the compensator
+            compensation.apply(obs, ahead, reset=True)
         return true if filtered else obs
 
     graph = None
@@ -2007,7 +2251,9 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
         agent.restart_actions()
     frame = dict(env=env, ego=env.ego, obs=true0)
     if filtered:
-        frame["seen"] = obs
+        frame["seen"] = acting
+    if compensation is not None:
+        frame["ahead"] = ahead
     for o in observers:
         o.observe(frame, reset=True)
     if actuation is not None:
@@ -2044,11 +2290,13 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
                       traces=None if trace is None else trace.traces(),
                       tracker=None if tracker is None else tracker.totals(),
                       actuation=None if actuation is None else actuation.totals(),
-                      plan=None if planm is None else planm.records())
+                      plan=None if planm is None else planm.records(),
+                      compensation=None if compensation is None else compensation.totals())
 
 
 def compare(agents: dict, make_env, episodes_per_env: int = 1, metrics: bool = False, perception=None,
-            interaction: bool = False, trace=None, results=None, tracker=None, actuation=None, plan=None, **kw) -> dict:
+            interaction: bool = False, trace=None, results=None, tracker=None, actuation=None, plan=None, compensation=None,
+            **kw) -> dict:
     """Evaluate every agent on a fresh environment from make_env() (same seed: the HIP environment keys its draws by seed and
     environment id, so every agent meets the same initial episodes) -> {name: summary}; metrics=True adds the drive metrics'
     keys to every summary.  perception (a dict of `Perception`'s keyword arguments, or a Perception whose configuration is
@@ -2058,10 +2306,12 @@ def compare(agents: dict, make_env, episodes_per_env: int = 1, metrics: bool = F
     the same settings.  tracker (a dict of `Tracker`'s keyword arguments, or a Tracker whose configuration is copied): every
     agent gets a fresh tracker.  actuation (a dict of `Actuation`'s keyword arguments, or an Actuation whose configuration is
     copied): every agent gets a fresh actuator model with the same seed, hence the same draws on the same steps.  plan (True, a dict of `PlanMetrics`'s keyword arguments, or a PlanMetrics whose settings are
-    copied): every agent gets fresh plan metrics; an agent without a plan (PPOAgent) is evaluated without them.  results: a dict that receives every agent's EvalResult by name (its traces, its records)."""
-    perception, trace, tracker, actuation, plan = (
-        x.config if isinstance(x, (Perception, EpisodeTrace, Tracker, Actuation, PlanMetrics)) else x
-        for x in (perception, trace, tracker, actuation, plan))
+    copied): every agent gets fresh plan metrics; an agent without a plan (PPOAgent) is evaluated without them.  compensation
+    (True, a dict of `Compensation`'s keyword arguments, or a Compensation whose configuration is copied): every agent gets a
+    fresh compensator; True is the one that matches every agent's fresh actuator model.  results: a dict that receives every agent's EvalResult by name (its traces, its records)."""
+    perception, trace, tracker, actuation, plan, compensation = (
+        x.config if isinstance(x, (Perception, EpisodeTrace, Tracker, Actuation, PlanMetrics, Compensation)) else x
+        for x in (perception, trace, tracker, actuation, plan, compensation))
     plan = {} if plan is True else None if plan is False else plan
     fresh = lambda settings: None if settings is None else dict(settings)
     out = {}
@@ -2072,7 +2322,8 @@ def compare(agents: dict, make_env, episodes_per_env: int = 1, metrics: bool = F
             settings.pop("plan", None), settings.pop("horizon", None)
         res = evaluate_agent(agent, make_env(), episodes_per_env, metrics=metrics, perception=fresh(perception),
                              interaction=interaction, trace=settings, tracker=fresh(tracker), actuation=fresh(actuation),
-                             plan=fresh(plan) if planned else None, **kw)
+                             plan=fresh(plan) if planned else None,
+                             compensation=compensation if compensation is True else fresh(compensation), **kw)
         if results is not None:
             results[name] = res
         out[name] = res.summary()

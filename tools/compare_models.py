@@ -14,6 +14,9 @@ are echoed in the JSON line, which then also holds coasted_frac, the share of th
 between every agent and the environment (evaluate.Actuation: transport delay in policy steps, first-order lag, rate limit,
 noise, lost commands, a steering offset, saturation); any of them switches it on; they are echoed in the JSON line, which then
 also holds the act_* shares and mean deviations.  tools/robustness_sweep.py runs the comparison over a grid of them.
+--compensate puts the delay compensator that matches that actuator model in front of every agent (evaluate.Compensation.matching:
+the agents act on the scene predicted to the moment their command takes effect); the JSON line then also holds the
+compensator's own prediction error, comp_pos_err_mean and comp_pos_err_max [m].
 
 Agents: pure MPC with the collision cost off and on, the iterative-linear (LTV) agent, and MPC-RL - an SB3 `.zip` given with
 --mpcrl, or with --fixture the v0 PPO (gSDE) policy rebuilt from tests/golden/sb3_policies.npz.  --ppo PATH adds the reference's
@@ -25,6 +28,7 @@ in the layout ActorCritic.save_sb3 writes; --ppo-random adds it with a seeded un
   python tools/compare_models.py --metrics --traffic idm --occlusion buildings --range 60 --sigma-pos 0.2
   python tools/compare_models.py --metrics --traffic idm --occlusion buildings --dropout 0.05 --track-coast 10
   python tools/compare_models.py --metrics --traffic idm --act-delay 2 --act-tau-steer 0.2 --act-limits env
+  python tools/compare_models.py --metrics --traffic idm --act-delay 3 --act-limits env --compensate
   python tools/compare_models.py --metrics --traffic idm --interaction --envs 256
   python tools/compare_models.py --envs 256 --fixture --ppo baseline.zip
   python tools/compare_models.py --traffic idm --trace failed --trace-window 50 --trace-dir out
@@ -139,6 +143,9 @@ def main():
     ap.add_argument("--track-alpha-pos", type=float, metavar="A", help="tracker: gain on the measured position, (0, 1]")
     ap.add_argument("--track-alpha-vel", type=float, metavar="A", help="tracker: gain on the measured velocity, (0, 1]")
     add_actuation_flags(ap)
+    ap.add_argument("--compensate", action="store_true",
+                    help="delay compensation: every agent acts on the scene predicted --act-delay steps ahead through the "
+                         "nominal actuator (its lag, rate limit and limits); needs an --act-* flag")
     add_agent_flags(ap)
     ap.add_argument("--plan", action="store_true",
                     help="also score every MPC agent's plan against what happened (evaluate.PlanMetrics): planned clearance, "
@@ -181,6 +188,10 @@ def main():
     actuation = actuation_of(args)
     if actuation is not None:
         echo["actuation"] = {k: [finite(x) for x in v] if isinstance(v, tuple) else v for k, v in actuation.items()}
+    if args.compensate and actuation is None:
+        ap.error("--compensate matches the actuator model: give at least one --act-* flag, such as --act-delay")
+    if args.compensate:
+        echo["compensate"] = True
     plan = None                          # no flag given: no plan is asked for, the launches of before
     if args.plan or args.plan_leads or args.plan_gap is not None:
         plan = {k: v for k, v in dict(leads=args.plan_leads and tuple(args.plan_leads), gap=args.plan_gap).items() if v is not None}
@@ -195,7 +206,7 @@ def main():
         s = evaluate.compare({name: agent}, make_env, args.episodes_per_env, deterministic=args.deterministic,
                              seed=args.seed, metrics=args.metrics, perception=perception,
                              interaction=args.interaction, trace=trace, tracker=tracker, actuation=actuation,
-                             plan=plan, results=results)[name]
+                             plan=plan, compensation=True if args.compensate else None, results=results)[name]
         s = {k: finite(v) for k, v in s.items()}
         if trace is not None:
             path = os.path.join(args.trace_dir, f"{name}.npz")

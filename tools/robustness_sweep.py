@@ -5,9 +5,15 @@ environment seed in every cell, every agent a fresh environment and a fresh actu
 rate, collision rate, mean steps per cell) and one JSON line with every cell's numbers.  --plan also scores every MPC agent's
 plan against what happened (evaluate.PlanMetrics) and adds per cell the prediction error at the first and the last lead, the
 share of steps with a planned conflict and the replanning jump: whether the plans were bad or the outcome merely left them.
+--compensate runs every cell twice on the same episodes, without and with the delay compensator that matches the cell's actuator
+(evaluate.Compensation.matching: the agent acts on the scene predicted to the moment its command takes effect), and prints
+both rows per model, the compensated one with the compensator's own prediction error; a cell without delay has a look-ahead of
+0 steps, for which the compensator hands the scene on unchanged, so its two rows are identical.  The uncompensated rows are
+this run's own baseline.
 
   python tools/robustness_sweep.py --envs 256 --traffic idm --fixture
   python tools/robustness_sweep.py --delays 0 2 4 6 --taus 0 1.0 --act-limits env
+  python tools/robustness_sweep.py --envs 256 --traffic idm --fixture --ppo-random --compensate
 
 One run of --envs episodes per cell: a rate carries the sampling noise of that many episodes (at 256, a standard error of up
 to 3.1 points), so differences of a few points between cells are within it.
@@ -38,8 +44,12 @@ def main():
                     help="steering time constants [s], each without delay")
     ap.add_argument("--act-limits", choices=("env",), help="saturate at the environment's clamp in every cell")
     ap.add_argument("--plan", action="store_true", help="also the plan metrics of every MPC agent, per cell")
+    ap.add_argument("--compensate", action="store_true",
+                    help="every cell also with the delay compensator that matches its actuator; both rows per model")
     compare_models.add_agent_flags(ap)
     args = ap.parse_args()
+    if args.plan and args.compensate:
+        ap.error("--plan and --compensate exclude each other: the plan metrics' leads assume a plan that starts now")
 
     import torch
     from mpc_rl_for_avs_amd import evaluate, rollout
@@ -52,21 +62,33 @@ def main():
     table = {name: [] for name in agents}
     for delay, tau in cells:
         model = dict(delay=delay, tau=(0.0, tau), limits=args.act_limits, seed=args.seed)
-        out = evaluate.compare(agents, make_env, args.episodes_per_env, deterministic=args.deterministic, seed=args.seed,
-                               actuation=model, plan=True if args.plan else None)
-        for name, s in out.items():
-            table[name].append(dict(delay=delay, tau_steer=tau, success_rate=s["success_rate"],
-                                    collision_rate=s["collision_rate"], avg_steps=s["avg_steps"],
-                                    act_mean_abs_dev_accel=s["act_mean_abs_dev_accel"],
-                                    act_mean_abs_dev_steer=s["act_mean_abs_dev_steer"],
-                                    **{k: v if math.isfinite(v) else None for k, v in s.items()
-                                       if k.startswith(("pred_err_", "plan", "replan_", "min_plan"))}))
+        for compensated in (False, True) if args.compensate else (False,):
+            out = evaluate.compare(agents, make_env, args.episodes_per_env, deterministic=args.deterministic, seed=args.seed,
+                                   actuation=model, plan=True if args.plan else None,
+                                   compensation=True if compensated else None)
+            for name, s in out.items():
+                table[name].append(dict(delay=delay, tau_steer=tau, compensated=compensated, success_rate=s["success_rate"],
+                                        collision_rate=s["collision_rate"], avg_steps=s["avg_steps"],
+                                        mean_return=s["mean_return"],
+                                        act_mean_abs_dev_accel=s["act_mean_abs_dev_accel"],
+                                        act_mean_abs_dev_steer=s["act_mean_abs_dev_steer"],
+                                        **{k: v if math.isfinite(v) else None for k, v in s.items()
+                                           if k.startswith(("pred_err_", "plan", "replan_", "min_plan", "comp_"))}))
     for name, rows in table.items():
         print(f"{name}: {args.envs * args.episodes_per_env} episodes per cell, traffic {args.traffic}, seed {args.seed}")
-        print("  delay [steps]  tau_steer [s]  success %  collision %  mean steps  mean |applied - command| accel, steer")
+        print("  delay [steps]  tau_steer [s]  success %  collision %  mean steps  mean |applied - command| accel, steer" +
+              ("  compensated  prediction error mean, max [m]" if args.compensate else ""))
         for r in rows:
             print(f"  {r['delay']:13d}  {r['tau_steer']:13.2f}  {r['success_rate']:9.1f}  {r['collision_rate']:11.1f}  "
-                  f"{r['avg_steps']:10.1f}  {r['act_mean_abs_dev_accel']:.3f}, {r['act_mean_abs_dev_steer']:.4f}")
+                  f"{r['avg_steps']:10.1f}  {r['act_mean_abs_dev_accel']:.3f}, {r['act_mean_abs_dev_steer']:.4f}" +
+                  ("" if not args.compensate else f"  {'yes' if r['compensated'] else 'no':>11}" +
+                   (f"  {r['comp_pos_err_mean']:.2e}, {r['comp_pos_err_max']:.2e}" if r["compensated"] else "")))
+        if args.compensate:                  # a look-ahead of 0 steps hands the scene on unchanged: the same episodes, bit for bit
+            same = lambda a, b: all(a[k] == b[k] for k in ("success_rate", "collision_rate", "avg_steps", "mean_return",
+                                                           "act_mean_abs_dev_accel", "act_mean_abs_dev_steer"))
+            zero = [(a, b) for a, b in zip(rows[::2], rows[1::2]) if a["delay"] == 0]
+            print(f"  cells without delay identical with and without compensation: {all(same(a, b) for a, b in zero)}"
+                  if zero else "  no cell without delay")
         leads = sorted(int(k[len("pred_err_lead"):-len("_mean")]) for k in rows[0] if k.startswith("pred_err_lead"))
         if leads:
             lo, hi = leads[0], leads[-1]
@@ -77,7 +99,7 @@ def main():
                       f"{r[f'pred_err_lead{hi}_mean']:16.3e}  {r['plan_conflict_frac']:16.4f}  {r['replan_accel_mean']:.3f}, "
                       f"{r['replan_steer_mean']:.4f}  {r['plans_valid_frac']:.4f}")
     print(json.dumps(dict(envs=args.envs, episodes_per_env=args.episodes_per_env, traffic=args.traffic, seed=args.seed,
-                          limits=args.act_limits, cells=table)), flush=True)
+                          limits=args.act_limits, compensate=args.compensate, cells=table)), flush=True)
     if tmp is not None:
         tmp.cleanup()
 
