@@ -783,6 +783,44 @@ int mpc_compensate(int32_t device, int32_t B, int32_t R, int32_t reset, const mp
                    int32_t *age, double *pring, int64_t *counts, double *sums, void *stream);
 
 /*
+ * mpc_compensate_stale (an addition within ABI 8: old clients never call it, nothing else changes) - mpc_compensate for a
+ * scene that is itself `latency` policy steps old (mpc_delay_scene below, or a deployment's own sensing latency): the same
+ * arguments, the same state, the same update, with the ego rolled through steps + min(latency, age) commands - the ones issued
+ * since the scene shown and the ones still in flight - and the others moved on by as much.  prev is then the nominal applied
+ * action of the step before the scene shown, and a prediction is scored against the ego that arrives steps + latency launches
+ * later (csrc/mpc_compensate.hpp states every change; with latency == 0 it computes what mpc_compensate computes).
+ * mpc_compensate stays and means latency 0; it launches a build of the kernel of its own.  A deployment that knows both its
+ * sensing latency and its actuation delay calls this in front of mpc_predict_batch.  With steps + latency == 0, out is obs bit
+ * for bit; with steps + latency > 0 every environment's out is written by the prediction's formulas, also while its own
+ * look-ahead is still 0.
+ * Errors (MPC_ERR_INVALID_ARG): those of mpc_compensate, and latency < 0 or steps + latency > 7.  B == 0 is a no-op.
+ */
+int mpc_compensate_stale(int32_t device, int32_t B, int32_t R, int32_t reset, const mpc_compensator *params, int32_t latency,
+                         const float *obs, const double *command, const uint8_t *done, float *out, double *pred, double *ring,
+                         double *prev, int32_t *age, double *pring, int64_t *counts, double *sums, void *stream);
+
+/*
+ * mpc_delay_scene (an addition within ABI 8: old clients never call it, nothing else changes) - sensing latency in front of the
+ * agent's pipeline of a closed-loop evaluation: `out` is the true scene of `steps` policy steps ago, bit for bit, every row,
+ * whatever its order (every statement, in evaluation order, in csrc/mpc_latency.hpp).  Launched in front of mpc_perceive and
+ * mpc_track_rows, which then see the old frame from where the ego was then.  The first `steps` steps of an episode show the
+ * episode's first scene, growing older: a frame of a finished episode is never shown in the next one.  Device pointers,
+ * enqueue only on `stream`, never synchronises (capturable in a hipGraph); sixteen lanes per environment, four environments
+ * per wave, no LDS, no atomics, no scratch.
+ *
+ * obs, out [B][R][8] f32 (out must not be obs); done [B] u8 or NULL: the environments whose episode ended on this step, so
+ * that obs is the first scene of a new one; stale [B] i32 or NULL <- the age, in steps, of the frame handed out:
+ * min(steps, frames of this episode before this one).  State: frames [8][B][R][8] f32 the last eight scenes; age [B] i32 the
+ * frames pushed in this episode.  counts [B] i64 += 1 per launch; sums [3][B] f64: the sum of stale, the sum and the maximum
+ * of the ego lag [m], the distance between row 0 of obs and row 0 of out.  reset != 0: every environment starts anew, counts
+ * and sums become 0 before this launch is counted, done is not read.  With steps == 0, out is obs.
+ * Errors (MPC_ERR_INVALID_ARG): B < 0, R outside 1 .. 17, steps outside 0 .. 7, a NULL obs / out / frames / age / counts /
+ * sums, out == obs.  B == 0 is a no-op.
+ */
+int mpc_delay_scene(int32_t device, int32_t B, int32_t R, int32_t reset, int32_t steps, const float *obs, const uint8_t *done,
+                    float *out, int32_t *stale, float *frames, int32_t *age, int64_t *counts, double *sums, void *stream);
+
+/*
  * Diagnostics: the NLP's functions at GIVEN points, evaluated by the solve kernel's own code (csrc/mpc_wave.hpp:
  * Solver::evaluate - stage_terms / track / dist, which judge every line-search trial, and the model step of the rollouts),
  * so that f(z) and g(z) computed by the reference's statements (agents/pure_mpc.py:128-283; tests/golden/

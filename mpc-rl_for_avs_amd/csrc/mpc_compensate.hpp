@@ -15,14 +15,15 @@
 //   out     [B][R][8] f32  the scene the agent acts on (must not alias obs)
 //   pred    [B][4] f64     the predicted ego x, y, heading, speed (may be NULL)
 //
-// PARAMETERS (Params): steps 0..7 whole policy steps to look ahead; dt > 0; per channel (0 acceleration, 1 steering) the
+// PARAMETERS (Params): steps 0..7 whole policy steps to look ahead (d below); latency >= 0 whole policy steps by which the
+// scene handed in is old (L below; mpc_latency.hpp), steps + latency <= 7; dt > 0; per channel (0 acceleration, 1 steering) the
 // nominal actuator's alpha in (0, 1], rate > 0 per second (+inf: no limit), lo <= hi.  `refusal` below is the check, written
-// so that NaN fails every comparison.
+// so that NaN fails every comparison.  mpc_compensate is latency 0; mpc_compensate_stale takes it as an argument.
 //
 // STATE per environment: ring [8][B][2] f64 the last eight commands (the compensator's own memory); prev [B][2] f64 the nominal
-// applied action of the step that just ran; age [B] i32 the commands pushed in this episode; pring [8][B][2] f64 the predicted
-// (x, y) of the last eight launches; counts [B] i64 the predictions scored; sums [2][B] f64 the sum and the maximum of the
-// prediction error [m].
+// applied action of the step before the scene shown; age [B] i32 the commands pushed in this episode; pring [8][B][2] f64 the
+// predicted (x, y) of the last eight launches; counts [B] i64 the predictions scored; sums [2][B] f64 the sum and the maximum
+// of the prediction error [m].
 //
 // ARITHMETIC: f64 on the f32 inputs widened exactly.  Steps 1, 2, 6, 7 and the counts use only + - *, comparisons and integer
 // operations without contraction (the pragma), so they agree bit for bit between the kernel, the host build, the evaluator's
@@ -30,37 +31,46 @@
 // plant's function as it stands), whose last bits belong to the library: pred, the ego's row, pring and the sums agree to
 // rounding.
 //
+// THE STALE SCENE.  Let d = steps, L = latency, n the age after the push, s = min(L, n) and m = n - s: the scene shown is the
+// episode's scene after m steps (the latency stage shows the episode's first scene until L steps have passed).  With L = 0,
+// s = 0 and m = n, and every statement below is the one it was before the latency existed.
+//
 // THE UPDATE of environment b, in evaluation order.  c runs over both channels.
 //   1 clear    when reset or done[b]: the ring, prev and pring become +0.0 and age 0; no command is pushed (it belonged to the
 //              old episode).  A reset launch also zeroes counts and sums.
-//   2 push     otherwise: u = command[b][c]; when !(u - u == 0.0) (NaN or +-inf): u = 0.0 (the actuator's step 2).
-//              ring[age & 7][c] = u; delayed = age >= steps ? ring[(age - steps) & 7][c] : +0.0;
-//              prev[c] = shape(delayed, prev[c]) - act::shape, steps 5 - 8 of mpc_actuator.hpp with gain 1, offset 0, sigma 0:
-//              the nominal applied action of the step that just ran; then age += 1.
-//   3 score    only when steps > 0 and age >= steps: (px, py) = pring[(age - steps) & 7], the prediction made `steps` launches
-//              ago, which targeted this moment; dx = px - x0, dy = py - y0 against row 0's (x, y) widened;
-//              e = sqrt(dx * dx + dy * dy); counts += 1, sums[0] += e, sums[1] = e > sums[1] ? e : sums[1].
+//   2 push     otherwise, with age0 the age before: u = command[b][c]; when !(u - u == 0.0) (NaN or +-inf): u = 0.0 (the
+//              actuator's step 2).  ring[age0 & 7][c] = u.  prev advances only when the scene did: when age0 >= L,
+//              j = age0 - L - d, delayed = j >= 0 ? ring[j & 7][c] : +0.0 and prev[c] = shape(delayed, prev[c]) - act::shape,
+//              steps 5 - 8 of mpc_actuator.hpp with gain 1, offset 0, sigma 0: the nominal applied action of the step
+//              before the scene; otherwise prev is unchanged, which is +0.0 since the clear.  Then age = age0 + 1.
+//   3 score    only when d + L > 0 and age >= d + L: (px, py) = pring[(age - d - L) & 7] - the prediction of launch n' targets
+//              step n' + d, and the scene of that step arrives at launch n' + d + L; dx = px - x0, dy = py - y0 against row
+//              0's (x, y) widened; e = sqrt(dx * dx + dy * dy); counts += 1, sums[0] += e, sums[1] = e > sums[1] ? e : sums[1].
 //   4 rollout  from row 0: x = obs[1], y = obs[2], th = obs[5], sp = sqrt(vx * vx + vy * vy) of obs[3], obs[4] (|v|, as the
-//              preamble reads the speed); p = prev.  For k = 0 .. steps - 1: i = age - steps + k;
-//              p[c] = shape(i >= 0 ? ring[i & 7][c] : +0.0, p[c]); (x, y, th, sp) = env::step_ego((x, y, th, sp), p, dt) - the
-//              plant's own function: its clamps and its speed limits are part of the prediction.
-//              pring[age & 7] = (x, y); pred[b] = (x, y, th, sp) when given.
+//              preamble reads the speed); p = prev.  d + s steps: for k = 0 .. d + s - 1: i = age - s - d + k;
+//              p[c] = shape(i >= 0 ? ring[i & 7][c] : +0.0, p[c]) (i == age - 1 is the command just pushed);
+//              (x, y, th, sp) = env::step_ego((x, y, th, sp), p, dt) - the plant's own function: its clamps and its speed
+//              limits are part of the prediction.  pring[age & 7] = (x, y); pred[b] = (x, y, th, sp) when given.
 //   5 ego row  out row 0, by the formulas of env::observe: 1, (float)x, (float)y, (float)(sp * cos th), (float)(sp * sin th),
 //              (float)th, (float)sin th, (float)cos th.
-//   6 others   h = steps * dt, formed once.  Every present row i >= 1: x' = (float)(x + vx * h), y' = (float)(y + vy * h) (a
-//              product, then a sum, in f64, narrowed once); presence becomes 1, velocity and the three heading values are
-//              copied.
+//   6 others   h = (double)(d + s) * dt, formed once per environment.  Every present row i >= 1: x' = (float)(x + vx * h),
+//              y' = (float)(y + vy * h) (a product, then a sum, in f64, narrowed once); presence becomes 1, velocity and the
+//              three heading values are copied.
 //   7 order    kx = x' - ex, ky = y' - ey, key = kx * kx + ky * ky with (ex, ey) the f32 values just written to row 0, all
 //              widened.  The present rows become rows 1, 2, ... by ascending key, ties to the lower input row; the remaining
 //              rows are +0.0f in all eight columns.  So "others sorted by distance, present rows contiguous" holds for what
 //              the agent gets.
-//   8 identity with steps == 0 steps 5 - 7 are replaced by a copy: every row of obs goes to the same row of out, bit for bit,
-//              whatever its order.  Nothing is scored; the ring, prev, age, pring and pred are kept as above (the rollout has
-//              no step, so pred is the observed ego).
+//   8 identity with d + L == 0 (launch arguments, hence the same for every environment) steps 5 - 7 are replaced by a copy:
+//              every row of obs goes to the same row of out, bit for bit, whatever its order.  Nothing is scored; the ring,
+//              prev, age, pring and pred are kept as above (the rollout has no step, so pred is the observed ego).  With
+//              d + L > 0 an environment whose own look-ahead d + s is 0 is still written by the formulas of steps 5 - 7.
 //
-// With the delay, alpha, rate and limits of a noise-free actuator model (no gain, offset, noise or hold) `prev` reproduces that
-// actuator's applied action bit for bit, and the predicted ego is the plant's state `steps` steps on, to the rounding of the
-// f32 observation.
+// With the delay, alpha, rate and limits of a noise-free actuator model (no gain, offset, noise or hold) `prev` at launch n
+// reproduces that actuator's applied action of step n - 1 - L bit for bit, and the predicted ego is the plant's state after
+// n + d steps of the episode, to the rounding of the f32 observation.
+//
+// TWO BUILDS.  Every function that depends on the latency takes a template constant kStale: with kStale false the latency is the
+// constant 0 (`if constexpr`), which is the code mpc_compensate has always launched; with kStale true P.latency is read.
 #pragma once
 
 #include <math.h>
@@ -79,6 +89,7 @@ struct Params {
     double dt;
     double alpha[kChannels], rate[kChannels], lo[kChannels], hi[kChannels];
     int32_t steps;
+    int32_t latency;             // trailing: an aggregate initialiser that stops at steps leaves it 0
 };
 
 struct Buffers {
@@ -99,6 +110,7 @@ struct Buffers {
 // why the library and the host build refuse P (each comparison written so that NaN fails it); nullptr when they accept it
 inline const char *refusal(const Params &P) {
     if (P.steps < 0 || P.steps > kMaxSteps) return "0 <= steps <= 7";
+    if (P.latency < 0 || P.latency > kMaxSteps - P.steps) return "0 <= latency, steps + latency <= 7";
     if (!(P.dt > 0.0)) return "dt > 0, not NaN";
     for (int c = 0; c < kChannels; ++c) {
         if (!(P.alpha[c] > 0.0 && P.alpha[c] <= 1.0)) return "0 < alpha <= 1, not NaN";
@@ -135,11 +147,16 @@ MPC_HD double speed(float vx, float vy) {
     return sqrt(a + c);
 }
 
-// steps 1 - 4 of environment b: the predicted ego.  Every load comes before every store, and the command just pushed is taken
-// from its register, so the lanes of a group may all call this and one of them, `write`, keep the state.
-MPC_HD env::Ego predict_ego(const Params &P, const Buffers &buf, int b, bool reset, bool write) {
+// steps 1 - 4 of environment b: the predicted ego, and in `ahead` its look-ahead d + s.  Every load comes before every store,
+// and the command just pushed is taken from its register, so the lanes of a group may all call this and one of them, `write`,
+// keep the state.  kStale false: the latency is the constant 0.
+template <bool kStale>
+MPC_HD env::Ego predict_ego(const Params &P, const Buffers &buf, int b, bool reset, bool write, int &ahead) {
 #pragma clang fp contract(off)
     const int B = buf.B, steps = P.steps;
+    int L = 0;
+    if constexpr (kStale) L = P.latency;
+    const int back = steps + L;                                  // how far the push and the score reach back
     const float *row0 = buf.obs + (size_t)b * buf.R * kCols;
     const bool clear = reset || (buf.done != nullptr && buf.done[b] != 0);                   // 1
     const int32_t age0 = clear ? 0 : buf.age[b];
@@ -150,28 +167,38 @@ MPC_HD env::Ego predict_ego(const Params &P, const Buffers &buf, int b, bool res
         u1 = buf.command[act::at(0, B, b, 1)];
         u0 = act::is_finite(u0) ? u0 : 0.0;
         u1 = act::is_finite(u1) ? u1 : 0.0;
-        double d0 = u0, d1 = u1;                             // steps == 0: the slot just pushed
-        if (steps > 0) {
-            const int slot = (age0 - steps) & (kRing - 1);   // another slot than the one pushed
+        double d0 = u0, d1 = u1;                             // back == 0: the slot just pushed
+        if (back > 0) {
+            const int slot = (age0 - back) & (kRing - 1);    // another slot than the one pushed
             const double r0 = buf.ring[act::at(slot, B, b, 0)], r1 = buf.ring[act::at(slot, B, b, 1)];
-            d0 = age0 >= steps ? r0 : 0.0;
-            d1 = age0 >= steps ? r1 : 0.0;
+            d0 = age0 >= back ? r0 : 0.0;
+            d1 = age0 >= back ? r1 : 0.0;
         }
-        prev0 = shape(P, 0, d0, buf.prev[act::at(0, B, b, 0)]);
-        prev1 = shape(P, 1, d1, buf.prev[act::at(0, B, b, 1)]);
+        if constexpr (kStale) {                              // while the scene has not moved, neither does prev
+            const double q0 = buf.prev[act::at(0, B, b, 0)], q1 = buf.prev[act::at(0, B, b, 1)];
+            const double y0 = shape(P, 0, d0, q0), y1 = shape(P, 1, d1, q1);
+            prev0 = age0 >= L ? y0 : q0;
+            prev1 = age0 >= L ? y1 : q1;
+        } else {
+            prev0 = shape(P, 0, d0, buf.prev[act::at(0, B, b, 0)]);
+            prev1 = shape(P, 1, d1, buf.prev[act::at(0, B, b, 1)]);
+        }
         age = age0 + 1;
     }
-    const bool scored = steps > 0 && age >= steps;                                           // 3 (never after a clear)
+    const bool scored = back > 0 && age >= back;                                             // 3 (never after a clear)
     double err = 0.0;
     if (scored) {
-        const int slot = (age - steps) & (kRing - 1);
+        const int slot = (age - back) & (kRing - 1);
         err = miss(buf.pring[act::at(slot, B, b, 0)], buf.pring[act::at(slot, B, b, 1)], row0[1], row0[2]);
     }
+    int old = 0;                                             // s: how many steps old the scene shown is
+    if constexpr (kStale) old = L < age ? L : age;
+    ahead = steps + old;
     env::Ego e;                                                                              // 4
     e.x = (double)row0[1], e.y = (double)row0[2], e.th = (double)row0[5], e.sp = speed(row0[3], row0[4]);
     double p[kChannels] = {prev0, prev1};
-    for (int k = 0; k < steps; ++k) {
-        const int i = age - steps + k;                       // i == age - 1 is the command just pushed (only without a clear)
+    for (int k = 0; k < ahead; ++k) {
+        const int i = age - ahead + k;                       // i == age - 1 is the command just pushed (only without a clear)
         const int slot = i & (kRing - 1);
         const double r0 = buf.ring[act::at(slot, B, b, 0)], r1 = buf.ring[act::at(slot, B, b, 1)];
         const double d0 = i < 0 ? 0.0 : (i == age - 1 ? u0 : r0), d1 = i < 0 ? 0.0 : (i == age - 1 ? u1 : r1);
@@ -224,7 +251,7 @@ MPC_HD void ego_row(const env::Ego &e, float *row) {
     row[7] = (float)c;
 }
 
-// step 6: one coordinate of a present row, h = steps * dt
+// step 6: one coordinate of a present row, h = (d + s) * dt
 MPC_HD float advance(float x, float v, double h) {
 #pragma clang fp contract(off)
     const double s = (double)v * h;
@@ -244,18 +271,22 @@ MPC_HD double order_key(float x, float y, float ex, float ey) {
 MPC_HD bool before(double key_a, int a, double key_b, int b) { return key_a < key_b || (key_a == key_b && a < b); }
 
 // one environment, serially: the host build, and the statement the kernel's lanes split between them
+template <bool kStale = false>
 MPC_HD void compensate_env(const Params &P, const Buffers &buf, int b, bool reset) {
 #pragma clang fp contract(off)
     const int R = buf.R;
     const float *in = buf.obs + (size_t)b * R * kCols;
     float *out = buf.out + (size_t)b * R * kCols;
-    const env::Ego e = predict_ego(P, buf, b, reset, true);                  // 1 - 4
-    if (P.steps == 0) {                                                      // 8
+    int ahead;
+    const env::Ego e = predict_ego<kStale>(P, buf, b, reset, true, ahead);   // 1 - 4
+    int back = P.steps;
+    if constexpr (kStale) back = P.steps + P.latency;
+    if (back == 0) {                                                         // 8
         for (int i = 0; i < R * kCols; ++i) out[i] = in[i];
         return;
     }
     ego_row(e, out);                                                         // 5
-    const double h = (double)P.steps * P.dt;
+    const double h = (double)ahead * P.dt;
     float moved[kMaxRows][kCols];
     double key[kMaxRows];
     bool present[kMaxRows];

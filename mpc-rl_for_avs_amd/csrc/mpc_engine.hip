@@ -34,6 +34,7 @@
 #include "mpc_tracker.hpp"
 #include "mpc_actuator.hpp"
 #include "mpc_compensate.hpp"
+#include "mpc_latency.hpp"
 #include "mpc_interaction.hpp"
 #include "mpc_episode_stats.hpp"
 #include "mpc_episode_trace.hpp"
@@ -1324,6 +1325,12 @@ __global__ __launch_bounds__(kTraceFrameThreads) void mpc_plan_trace_kernel(mpc:
 // slice of one ballot.  Every shuffle and the ballot sit in wave-uniform control flow (P.steps and R are launch arguments): a
 // lane without a row counts as absent, a group past the end computes on the last environment; only stores are predicated.  No
 // LDS, no atomics, no scratch.
+// TWO BUILDS on a template constant: <false> is mpc_compensate's, the latency the constant 0; <true> is mpc_compensate_stale's,
+// for a scene that is P.latency steps old.  There the rollout's trip count, steps + min(latency, age), differs between the four
+// environments of a wave, so nothing inside comp::predict_ego may shuffle - and nothing does: every shuffle and the ballot
+// come after it, where control flow is uniform again (P.steps + P.latency is a launch argument too).  A run-time flag instead
+// of the constant would be one kernel less and a different register allocation for the latency-0 path.
+template <bool kStale>
 __global__ __launch_bounds__(64) void mpc_compensate_kernel(mpc::comp::Params P, mpc::comp::Buffers buf, int reset) {
 #pragma clang fp contract(off)
     namespace comp = mpc::comp;
@@ -1337,9 +1344,12 @@ __global__ __launch_bounds__(64) void mpc_compensate_kernel(mpc::comp::Params P,
     float row[comp::kCols];
 #pragma unroll
     for (int c = 0; c < comp::kCols; ++c) row[c] = in[(has ? i : 0) * comp::kCols + c];
-    const mpc::env::Ego e = comp::predict_ego(P, buf, b, reset != 0, live && l == 0);    // 1 - 4
+    int ahead;
+    const mpc::env::Ego e = comp::predict_ego<kStale>(P, buf, b, reset != 0, live && l == 0, ahead);    // 1 - 4
+    int back = P.steps;
+    if constexpr (kStale) back = P.steps + P.latency;
     float *out = buf.out + (size_t)b * R * comp::kCols;
-    if (P.steps == 0) {                                      // 8, wave-uniform: every row in place
+    if (back == 0) {                                         // 8, wave-uniform: every row in place
         if (!live) return;
         if (has) {
 #pragma unroll
@@ -1353,7 +1363,7 @@ __global__ __launch_bounds__(64) void mpc_compensate_kernel(mpc::comp::Params P,
     }
     float ego[comp::kCols];
     comp::ego_row(e, ego);                                                               // 5
-    const double h = (double)P.steps * P.dt;
+    const double h = (double)ahead * P.dt;
     const bool present = has && row[0] != 0.0f;              // no row: absent
     const float nx = comp::advance(row[1], row[3], h), ny = comp::advance(row[2], row[4], h);        // 6
     const double key = present ? comp::order_key(nx, ny, ego[1], ego[2]) : __builtin_huge_val();     // 7
@@ -1379,6 +1389,29 @@ __global__ __launch_bounds__(64) void mpc_compensate_kernel(mpc::comp::Params P,
     if (l == 0) {
 #pragma unroll
         for (int c = 0; c < comp::kCols; ++c) out[c] = ego[c];
+    }
+}
+
+
+// sensing latency of a closed-loop evaluation (mpc_latency.hpp): the mapping of mpc_track_kernel, sixteen lanes per
+// environment, four environments per wave.  Lane l moves row l + 1 (R <= 17), lane 0 also row 0, and lane 0 alone keeps the
+// state.  All lanes of an environment sit in one wave and every one of them loads age (lat::select) before lane 0 stores it.
+// The frames stay in memory and are indexed by address; the slot shown is another than the slot pushed whenever it is read.  A
+// group past the end works on the last environment and stores nothing.  No shuffles, no LDS, no atomics, no scratch.
+__global__ __launch_bounds__(64) void mpc_delay_scene_kernel(mpc::lat::Buffers buf, int steps, int reset) {
+    namespace lat = mpc::lat;
+    const int l = threadIdx.x & 15, g = threadIdx.x >> 4;
+    const int b_ = blockIdx.x * 4 + g;
+    const bool live = b_ < buf.B;
+    const int b = live ? b_ : buf.B - 1;
+    const int i = l + 1;
+    const lat::Pick p = lat::select(buf, steps, b, reset != 0);                          // 1, 3
+    if (!live) return;                                        // nothing but stores below
+    float fresh[lat::kCols], shown[lat::kCols];
+    if (i < buf.R) lat::move_row(buf, p, b, i, fresh, shown);                            // 2, 3
+    if (l == 0) {
+        lat::move_row(buf, p, b, 0, fresh, shown);
+        lat::keep_state(buf, p, b, reset != 0, fresh, shown);                            // 4, 5
     }
 }
 
@@ -2584,8 +2617,53 @@ int mpc_compensate(int32_t device, int32_t B, int32_t R, int32_t reset, const mp
     if (B == 0) return MPC_OK;
     HIP_TRY(hipSetDevice(device));
     const comp::Buffers buf{(int)B, (int)R, obs, command, done, out, pred, ring, prev, age, pring, counts, sums};
-    hipLaunchKernelGGL(mpc_compensate_kernel, dim3((unsigned)((B + 3) / 4)), dim3(64), 0, reinterpret_cast<hipStream_t>(stream_),
-                       P, buf, (int)reset);
+    hipLaunchKernelGGL(mpc_compensate_kernel<false>, dim3((unsigned)((B + 3) / 4)), dim3(64), 0,
+                       reinterpret_cast<hipStream_t>(stream_), P, buf, (int)reset);
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_compensate_stale(int32_t device, int32_t B, int32_t R, int32_t reset, const mpc_compensator *params, int32_t latency,
+                         const float *obs, const double *command, const uint8_t *done, float *out, double *pred, double *ring,
+                         double *prev, int32_t *age, double *pring, int64_t *counts, double *sums, void *stream_) {
+    namespace comp = mpc::comp;
+    if (B < 0 || R < 1 || R > comp::kMaxRows)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_compensate_stale: bad size (B >= 0, 1 <= R <= 17)");
+    if (!params || !obs || !out || !ring || !prev || !age || !pring || !counts || !sums)
+        return fail(MPC_ERR_INVALID_ARG,
+                    "mpc_compensate_stale: null params / obs / out / ring / prev / age / pring / counts / sums pointer");
+    if (reset == 0 && !command)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_compensate_stale: null command pointer in a launch without reset");
+    if (out == obs) return fail(MPC_ERR_INVALID_ARG, "mpc_compensate_stale: out must not be obs");
+    if (params->struct_size != (int32_t)sizeof(mpc_compensator))
+        return fail(MPC_ERR_INVALID_ARG, "mpc_compensate_stale: mpc_compensator.struct_size mismatch");
+    const mpc_compensator &p = *params;
+    const comp::Params P{p.dt, {p.alpha[0], p.alpha[1]}, {p.rate[0], p.rate[1]}, {p.lo[0], p.lo[1]}, {p.hi[0], p.hi[1]}, p.steps,
+                         latency};
+    if (const char *why = comp::refusal(P))
+        return fail(MPC_ERR_INVALID_ARG, std::string("mpc_compensate_stale: bad parameter (") + why + ")");
+    if (B == 0) return MPC_OK;
+    HIP_TRY(hipSetDevice(device));
+    const comp::Buffers buf{(int)B, (int)R, obs, command, done, out, pred, ring, prev, age, pring, counts, sums};
+    hipLaunchKernelGGL(mpc_compensate_kernel<true>, dim3((unsigned)((B + 3) / 4)), dim3(64), 0,
+                       reinterpret_cast<hipStream_t>(stream_), P, buf, (int)reset);
+    HIP_TRY(hipGetLastError());
+    return MPC_OK;
+}
+
+int mpc_delay_scene(int32_t device, int32_t B, int32_t R, int32_t reset, int32_t steps, const float *obs, const uint8_t *done,
+                    float *out, int32_t *stale, float *frames, int32_t *age, int64_t *counts, double *sums, void *stream_) {
+    namespace lat = mpc::lat;
+    if (const char *why = lat::refusal((int)B, (int)R, (int)steps))
+        return fail(MPC_ERR_INVALID_ARG, std::string("mpc_delay_scene: bad argument (") + why + ")");
+    if (!obs || !out || !frames || !age || !counts || !sums)
+        return fail(MPC_ERR_INVALID_ARG, "mpc_delay_scene: null obs / out / frames / age / counts / sums pointer");
+    if (out == obs) return fail(MPC_ERR_INVALID_ARG, "mpc_delay_scene: out must not be obs");
+    if (B == 0) return MPC_OK;
+    HIP_TRY(hipSetDevice(device));
+    const lat::Buffers buf{(int)B, (int)R, obs, done, out, stale, frames, age, counts, sums};
+    hipLaunchKernelGGL(mpc_delay_scene_kernel, dim3((unsigned)((B + 3) / 4)), dim3(64), 0,
+                       reinterpret_cast<hipStream_t>(stream_), buf, (int)steps, (int)reset);
     HIP_TRY(hipGetLastError());
     return MPC_OK;
 }

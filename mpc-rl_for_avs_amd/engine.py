@@ -149,13 +149,20 @@ _TABLES = (SIGNATURES, EVALUATION_SIGNATURES, TRACKER_SIGNATURES, PLAN_SIGNATURE
 COMPENSATION_SIGNATURES = {name: tuple(tuple(word.split(":")) for word in text.split()) for name, text in dict(
     mpc_compensate="device:i32 B:i32 R:i32 reset:i32 params:compensator obs:ptr command:ptr done:ptr out:ptr pred:ptr "
                    "ring:ptr prev:ptr age:ptr pring:ptr counts:ptr sums:ptr stream:ptr").items()}
-_ALL_TABLES = _TABLES + (COMPENSATION_SIGNATURES,)
+# The sensing latency of the evaluation (csrc/mpc_latency.hpp) and the compensator that knows of it, likewise, in a table of
+# their own; tests/test_latency_cpu.py holds this one against the header.
+LATENCY_SIGNATURES = {name: tuple(tuple(word.split(":")) for word in text.split()) for name, text in dict(
+    mpc_delay_scene="device:i32 B:i32 R:i32 reset:i32 steps:i32 obs:ptr done:ptr out:ptr stale:ptr frames:ptr age:ptr "
+                    "counts:ptr sums:ptr stream:ptr",
+    mpc_compensate_stale="device:i32 B:i32 R:i32 reset:i32 params:compensator latency:i32 obs:ptr command:ptr done:ptr "
+                         "out:ptr pred:ptr ring:ptr prev:ptr age:ptr pring:ptr counts:ptr sums:ptr stream:ptr").items()}
+_ALL_TABLES = _TABLES + (COMPENSATION_SIGNATURES, LATENCY_SIGNATURES)
 
 _EXPORTS = ["mpc_version", "mpc_last_error", "mpc_default_config", "mpc_default_config_sized", "mpc_create", "mpc_destroy",
             "mpc_set_reference", "mpc_solve_batch", "mpc_workspace_bytes", "mpc_predict_batch", "mpc_predict_batch_plan",
             "mpc_reset_env_state", "mpc_reset_env_mask", "mpc_get_env_state", "mpc_get_last_inputs",
             "mpc_ltv_solve_batch", "mpc_ltv_predict_batch", "mpc_ltv_predict_batch_plan", "mpc_env_state_bytes", "mpc_save_env_state",
-            "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_policy_control", "mpc_policy_control_tile", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_interaction_metrics", "mpc_episode_trace", "mpc_plan_metrics", "mpc_plan_trace", "mpc_perceive", "mpc_track_rows", "mpc_actuate", "mpc_compensate", "mpc_eval_nlp", "mpc_streams_overlap"]
+            "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_policy_control", "mpc_policy_control_tile", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_interaction_metrics", "mpc_episode_trace", "mpc_plan_metrics", "mpc_plan_trace", "mpc_perceive", "mpc_track_rows", "mpc_actuate", "mpc_compensate", "mpc_compensate_stale", "mpc_delay_scene", "mpc_eval_nlp", "mpc_streams_overlap"]
 ABI_VERSION = 8          # MPC_ABI_VERSION of include/mpc_mi355x.h this binding is written for
 MAX_OTHERS = 16
 _lib = None
@@ -278,10 +285,10 @@ _CALLERS = {name: _caller(name, sig) for table in _ALL_TABLES for name, sig in t
 
 def caller(name: str):
     """The handle-less entry point `name` as a function of keywords alone: every one of SIGNATURES[name] (or
-    EVALUATION_SIGNATURES[name], TRACKER_SIGNATURES[name], PLAN_SIGNATURES[name], ACTUATION_SIGNATURES[name], COMPENSATION_SIGNATURES[name]) and no other (TypeError
+    EVALUATION_SIGNATURES[name], TRACKER_SIGNATURES[name], PLAN_SIGNATURES[name], ACTUATION_SIGNATURES[name], COMPENSATION_SIGNATURES[name], LATENCY_SIGNATURES[name]) and no other (TypeError
     naming the entry point and the parameter otherwise, before anything is called).  Python ints and floats pass through;
     a pointer is a torch tensor (its address; a bool tensor's bytes are the uint8 the kernels read) or None; `stream` is a
-    torch stream, its raw handle or None; `params` of mpc_perceive a PerceptionParams, of mpc_actuate an ActuatorParams, of mpc_compensate a CompensatorParams.  Enqueue only; EngineError with the
+    torch stream, its raw handle or None; `params` of mpc_perceive a PerceptionParams, of mpc_actuate an ActuatorParams, of mpc_compensate and mpc_compensate_stale a CompensatorParams.  Enqueue only; EngineError with the
     library's text when the entry point refuses.  lib: the library, load_library() by default."""
     return _CALLERS[name]
 

@@ -55,6 +55,11 @@ takes effect `steps` policy steps after the scene it was computed from, so the a
 - the ego rolled through the commands still in flight with the environment's own vehicle model behind the nominal actuator, the
 others moved on with their observed velocity - inside the same captured step (mpc_compensate), or by the same update in numpy
 on the CPU path.
+
+`latency=` puts a sensing latency (csrc/mpc_latency.hpp, `Latency`) in front of all of that: the perception model, the tracker
+and the agent are handed the true scene of `steps` policy steps ago, inside the same captured step (mpc_delay_scene), or by the
+same update in numpy on the CPU path.  A compensator that is told of it (`Compensation(latency=...)`, mpc_compensate_stale)
+rolls the ego through the commands issued since that scene as well.
 """
 from __future__ import annotations
 
@@ -111,6 +116,8 @@ ENV_LIMITS = ((-5.0, 5.0), (-math.pi / 4, math.pi / 4))
 # csrc/mpc_compensate.hpp: the ring's length, the longest look-ahead; csrc/mpc_synth_env.hpp::step_ego: the wheelbase and the
 # largest speed
 COMP_RING, COMP_MAX_STEPS, ENV_WHEELBASE, ENV_MAX_SPEED = 8, 7, 2.5, 30.0
+# csrc/mpc_latency.hpp: the ring's length, the longest latency
+LAT_RING, LAT_MAX_STEPS = 8, 7
 # csrc/mpc_plan.hpp: the records of mpc_plan_metrics (lead{i}: the i-th of its four leads), the planes of its running state,
 # the leads per launch, MPC_MAX_HORIZON
 PLAN_I32 = ("steps", "plans_valid", "plan_conflict_steps", "replan_n") + tuple(f"lead{i}_n" for i in range(4))   # rec_i32 [8][B][Q]
@@ -1395,6 +1402,13 @@ class Compensation:
     predicted ego.  With steps = 0 the output is the input bit for bit.  `Compensation.matching(actuation)` takes the delay,
     tau, rate and limits of an `Actuation`.  The parameters are fixed at construction.
 
+    `latency` (0 .. 7 - steps): the scene handed in is itself that many policy steps old (`Latency`, or a deployment's own
+    sensing latency); the ego is then rolled through steps + min(latency, age) commands - those issued since the scene and those
+    in flight -, the others move on by as much, `prev` is the nominal applied action of the step before the scene shown and a
+    prediction is scored against the ego that arrives steps + latency launches later (mpc_compensate_stale).  With latency = 0
+    everything here is what it is without the argument, and the kernel launched is mpc_compensate's.  With steps + latency = 0
+    the output is the input bit for bit.  `Compensation.matching(actuation, latency)` takes the latency of a `Latency`.
+
     `apply(obs, out, command, done)` fills `out` [B, R, 8] f32 (not `obs`) from the observation `obs` and the agent's command
     [B, 2] f64 of the step that just ran, and returns it; done [B]: the environments whose episode ended on that step (their
     memory is cleared, their command is not read).  `apply(obs, out, reset=True)` starts every environment anew on its first
@@ -1407,7 +1421,7 @@ class Compensation:
     are involved, and equal to the rounding of the library's sqrt, sin, cos, tan and atan in the ego's rollout."""
 
     def __init__(self, B: int, device, backend: str = "torch", R: int = VEHICLES_COUNT, dt: float = 0.1, steps: int = 0,
-                 tau=(0.0, 0.0), rate=(math.inf, math.inf), limits=None):
+                 tau=(0.0, 0.0), rate=(math.inf, math.inf), limits=None, latency: int = 0):
         if backend not in ("hip", "torch"):
             raise ValueError("backend must be 'hip' or 'torch'")
         if int(B) < 0:
@@ -1418,6 +1432,8 @@ class Compensation:
             raise ValueError("dt must be > 0")
         if int(steps) != steps or not 0 <= int(steps) <= COMP_MAX_STEPS:
             raise ValueError(f"steps must be an integer 0..{COMP_MAX_STEPS}")
+        if int(latency) != latency or not 0 <= int(latency) <= COMP_MAX_STEPS - int(steps):
+            raise ValueError(f"latency must be an integer >= 0 with steps + latency <= {COMP_MAX_STEPS}")
         tau, rate = _pair("tau", tau), _pair("rate", rate)
         if limits is None:
             limits = ((-math.inf, math.inf), (-math.inf, math.inf))
@@ -1435,6 +1451,7 @@ class Compensation:
                 raise ValueError("limits must be lo <= hi")
         self.B, self.R, self.device, self.backend = int(B), int(R), torch.device(device), backend
         self.dt, self.steps, self.tau, self.rate, self.limits = float(dt), int(steps), tau, rate, limits
+        self.latency = int(latency)
         self.alpha = tuple(self.dt / (t + self.dt) for t in tau)
         if not all(0.0 < a <= 1.0 for a in self.alpha):
             raise ValueError("tau is too large for dt: alpha = dt / (tau + dt) must be in (0, 1]")
@@ -1448,16 +1465,29 @@ class Compensation:
             rate=pair(rate), lo=pair((limits[0][0], limits[1][0])), hi=pair((limits[0][1], limits[1][1])))
 
     @classmethod
-    def matching(cls, actuation, R: int = VEHICLES_COUNT) -> "Compensation":
+    def matching(cls, actuation=None, latency=None, R: int = VEHICLES_COUNT, dt: float | None = None) -> "Compensation":
         """The compensator of `actuation`'s nominal model: its batch, device, backend and dt, its delay as `steps`, its tau,
-        rate and limits - and none of its errors (gain, offset, noise, hold)."""
+        rate and limits - and none of its errors (gain, offset, noise, hold) -, and of `latency`'s steps (a `Latency`) as its
+        latency.  Either may be None (not both): without an actuator model the batch, device and backend are the latency
+        model's, there is no delay, lag or limit to know of, and dt is the argument (0.1 when None)."""
+        if actuation is None and latency is None:
+            raise ValueError("matching needs an actuator model or a latency model")
+        old = 0 if latency is None else latency.steps
+        if actuation is None:
+            return cls(latency.B, latency.device, latency.backend, R=R, dt=0.1 if dt is None else dt, latency=old)
+        if latency is not None and (latency.B, latency.device, latency.backend) != (actuation.B, actuation.device,
+                                                                                     actuation.backend):
+            raise ValueError("the actuator model and the latency model must share batch, device and backend")
         return cls(actuation.B, actuation.device, actuation.backend, R=R, dt=actuation.dt, steps=actuation.delay,
-                   tau=actuation.tau, rate=actuation.rate, limits=actuation.limits)
+                   tau=actuation.tau, rate=actuation.rate, limits=actuation.limits, latency=old)
 
     @property
     def config(self) -> dict:
-        """The keyword arguments that make a Compensation with the same model."""
-        return dict(R=self.R, dt=self.dt, steps=self.steps, tau=self.tau, rate=self.rate, limits=self.limits)
+        """The keyword arguments that make a Compensation with the same model (latency only when it is not 0)."""
+        out = dict(R=self.R, dt=self.dt, steps=self.steps, tau=self.tau, rate=self.rate, limits=self.limits)
+        if self.latency:
+            out["latency"] = self.latency
+        return out
 
     def reset(self) -> None:
         """Forget everything: the commands in flight, the nominal actuator's state, the predictions, the counts, the sums.
@@ -1481,9 +1511,15 @@ class Compensation:
             out.copy_(torch.from_numpy(o))
             if self.pred is not None:
                 self.pred.copy_(torch.from_numpy(pred))
-        else:
+        elif self.latency == 0:
             _engine.caller("mpc_compensate")(
                 device=dev.index, B=B, R=R, reset=1 if reset else 0, params=self._params, obs=obs,
+                command=None if reset else command, done=None if reset else done, out=out, pred=self.pred, ring=self.ring,
+                prev=self.prev, age=self.age, pring=self.pring, counts=self.counts, sums=self.sums,
+                stream=_engine.current_stream(dev))
+        else:
+            _engine.caller("mpc_compensate_stale")(
+                device=dev.index, B=B, R=R, reset=1 if reset else 0, params=self._params, latency=self.latency, obs=obs,
                 command=None if reset else command, done=None if reset else done, out=out, pred=self.pred, ring=self.ring,
                 prev=self.prev, age=self.age, pring=self.pring, counts=self.counts, sums=self.sums,
                 stream=_engine.current_stream(dev))
@@ -1507,10 +1543,10 @@ class Compensation:
 
     def _numpy_apply(self, obs, cmd, done, reset):
         """csrc/mpc_compensate.hpp over the batch: every statement acts on all environments -> (out, pred)"""
-        B, d, dt, f64 = self.B, self.steps, self.dt, np.float64
+        B, d, L, dt, f64 = self.B, self.steps, self.latency, self.dt, np.float64
         ring, pring, prev, age, counts, sums = (t.cpu().numpy() for t in (self.ring, self.pring, self.prev, self.age,
                                                                           self.counts, self.sums))
-        env, last = np.arange(B), COMP_RING - 1
+        env, last, back = np.arange(B), COMP_RING - 1, d + L
         clear = np.ones(B, bool) if reset else np.zeros(B, bool) if done is None else done != 0
         ring[:, clear], pring[:, clear], prev[clear], age[clear] = 0.0, 0.0, 0.0, 0    # 1
         if reset:
@@ -1520,13 +1556,14 @@ class Compensation:
             if push.any():                                                         # 2
                 u = np.where((cmd - cmd) == 0.0, cmd, 0.0)
                 ring[(age & last)[push], env[push]] = u[push]
-                delayed = np.where((age >= d)[:, None], ring[(age - d) & last, env], 0.0)
-                prev[push] = self._shape(delayed, prev)[push]
+                delayed = np.where((age >= back)[:, None], ring[(age - back) & last, env], 0.0)
+                moved = push & (age >= L)                                          # prev advances only when the scene did
+                prev[moved] = self._shape(delayed, prev)[moved]
                 age[push] += 1
             x0, y0 = obs[:, 0, 1].astype(f64), obs[:, 0, 2].astype(f64)
-            if d > 0:                                                              # 3
-                scored = age >= d
-                p = pring[(age - d) & last, env]
+            if back > 0:                                                           # 3
+                scored = age >= back
+                p = pring[(age - back) & last, env]
                 dx, dy = p[:, 0] - x0, p[:, 1] - y0
                 e = np.sqrt(dx * dx + dy * dy)
                 counts[scored] += 1
@@ -1535,19 +1572,23 @@ class Compensation:
             vx, vy = obs[:, 0, 3].astype(f64), obs[:, 0, 4].astype(f64)                # 4
             x, y, th, sp = x0, y0, obs[:, 0, 5].astype(f64), np.sqrt(vx * vx + vy * vy)
             p = prev.copy()
-            for k in range(d):
-                i = age - d + k
-                p = self._shape(np.where((i >= 0)[:, None], ring[i & last, env], 0.0), p)
-                x, y, th, sp = _step_ego(x, y, th, sp, p, dt)
+            ahead = d + np.minimum(L, age)                                         # d + s, per environment
+            for k in range(int(ahead.max(initial=0))):
+                i = age - ahead + k
+                run = k < ahead
+                q = self._shape(np.where((i >= 0)[:, None], ring[i & last, env], 0.0), p)
+                nx, ny, nth, nsp = _step_ego(x, y, th, sp, q, dt)
+                p = np.where(run[:, None], q, p)
+                x, y, th, sp = np.where(run, nx, x), np.where(run, ny, y), np.where(run, nth, th), np.where(run, nsp, sp)
             pring[age & last, env] = np.stack([x, y], axis=1)
             pred = np.stack([x, y, th, sp], axis=1)
-            if d == 0:                                                             # 8
+            if back == 0:                                                          # 8
                 out = obs.copy()
             else:
                 s, c = np.sin(th), np.cos(th)                                          # 5
                 out = np.zeros_like(obs)
                 out[:, 0] = np.stack([np.ones(B), x, y, sp * c, sp * s, th, s, c], axis=1).astype(np.float32)
-                h = float(d) * dt                                                  # 6
+                h = (ahead.astype(f64) * dt)[:, None]                              # 6
                 rows = obs[:, 1:]
                 present = rows[:, :, 0] != 0.0
                 moved = rows.copy()
@@ -1570,6 +1611,99 @@ class Compensation:
         scored = int(self.counts.sum().item())
         s = self.sums.cpu().numpy()
         return dict(scored=scored, pos_err_mean=float(s[0].sum()) / max(scored, 1), pos_err_max=float(s[1].max(initial=0.0)))
+
+
+class Latency:
+    """Sensing latency in front of the agent's pipeline (csrc/mpc_latency.hpp states the update step by step): the scene handed
+    on is the true scene of `steps` whole policy steps ago (0..7), bit for bit, every row.  A perception model and a tracker
+    behind it then see the old frame from where the ego was then.  The first `steps` steps of an episode show the episode's
+    first scene, growing older; a frame of a finished episode is never shown in the next one.
+
+    `apply(obs, out, done, reset)` fills `out` [B, R, 8] f32 (not `obs`) from the true scene `obs` and returns it; done [B]:
+    the environments whose episode ended on this step, so that obs is the first scene of a new one; reset=True starts every
+    environment anew and zeroes the totals.  `stale` [B] i32 is the age, in steps, of the frame handed out by the last launch;
+    `frames` [8, B, R, 8] f32 the last eight scenes, `age` [B] i32 the frames of the episode, `counts` [B] i64 the launches,
+    `sums` [3, B] f64 the sum of stale, the sum and the maximum of the ego lag [m]: the distance between row 0 of obs and row
+    0 of out.  Backend "hip" is the kernel (mpc_delay_scene, enqueue only, capturable); backend "torch" is the same update in
+    numpy: the same bits but for the last bit of the lag's sqrt."""
+
+    def __init__(self, B: int, device, backend: str = "torch", R: int = VEHICLES_COUNT, steps: int = 0):
+        if backend not in ("hip", "torch"):
+            raise ValueError("backend must be 'hip' or 'torch'")
+        if int(B) < 0:
+            raise ValueError("B must be >= 0")
+        if not 1 <= int(R) <= MAX_ROWS:
+            raise ValueError(f"R must be in 1..{MAX_ROWS}")
+        if isinstance(steps, bool) or int(steps) != steps or not 0 <= int(steps) <= LAT_MAX_STEPS:
+            raise ValueError(f"steps must be an integer 0..{LAT_MAX_STEPS}")
+        self.B, self.R, self.device, self.backend, self.steps = int(B), int(R), torch.device(device), backend, int(steps)
+        z = lambda *s, dt: torch.zeros(s, dtype=dt, device=self.device)
+        self.frames = z(LAT_RING, self.B, self.R, 8, dt=torch.float32)
+        self.age, self.stale, self.counts = z(self.B, dt=torch.int32), z(self.B, dt=torch.int32), z(self.B, dt=torch.int64)
+        self.sums = z(3, self.B, dt=torch.float64)
+
+    @property
+    def config(self) -> dict:
+        """The keyword arguments that make a Latency with the same model."""
+        return dict(R=self.R, steps=self.steps)
+
+    def reset(self) -> None:
+        """Forget every frame and the totals.  `apply(..., reset=True)` does the same and then hands on the first scene."""
+        for t in (self.frames, self.age, self.stale, self.counts, self.sums):
+            t.zero_()
+
+    def apply(self, obs, out, done=None, reset: bool = False):
+        B, R, dev = self.B, self.R, self.device
+        _check(obs, "obs", (B, R, 8), torch.float32, dev)
+        _check(out, "out", (B, R, 8), torch.float32, dev)
+        if out is obs or (B > 0 and out.data_ptr() == obs.data_ptr()):
+            raise ValueError("out must not be obs")
+        if done is not None:
+            done = _check(done, "done", (B,), torch.uint8, dev)
+        if self.backend == "torch":
+            out.copy_(torch.from_numpy(self._numpy_apply(obs.cpu().numpy(), None if done is None else done.cpu().numpy(),
+                                                         bool(reset))))
+        else:
+            _engine.caller("mpc_delay_scene")(
+                device=dev.index, B=B, R=R, reset=1 if reset else 0, steps=self.steps, obs=obs,
+                done=None if reset else done, out=out, stale=self.stale, frames=self.frames, age=self.age,
+                counts=self.counts, sums=self.sums, stream=_engine.current_stream(dev))
+        return out
+
+    def _numpy_apply(self, obs, done, reset):
+        """csrc/mpc_latency.hpp over the batch: every statement acts on all environments -> out"""
+        B, f64 = self.B, np.float64
+        frames, age, stale, counts, sums = (t.cpu().numpy() for t in (self.frames, self.age, self.stale, self.counts,
+                                                                      self.sums))
+        env, last = np.arange(B), LAT_RING - 1
+        clear = np.ones(B, bool) if reset else np.zeros(B, bool) if done is None else done != 0
+        age[clear] = 0                                                             # 1
+        if reset:
+            counts[:], sums[:] = 0, 0.0
+        frames[age & last, env] = obs                                              # 2
+        s = np.minimum(self.steps, age)                                            # 3
+        out = frames[(age - s) & last, env]
+        stale[:] = s
+        dx = obs[:, 0, 1].astype(f64) - out[:, 0, 1].astype(f64)                   # 4
+        dy = obs[:, 0, 2].astype(f64) - out[:, 0, 2].astype(f64)
+        with np.errstate(invalid="ignore", over="ignore"):
+            e = np.sqrt(dx * dx + dy * dy)
+            counts += 1
+            sums[0] += s
+            sums[1] += e
+            sums[2] = np.where(e > sums[2], e, sums[2])
+        age += 1                                                                   # 5
+        _write_back(((self.frames, frames), (self.age, age), (self.stale, stale), (self.counts, counts), (self.sums, sums)))
+        return out
+
+    def totals(self) -> dict:
+        """Since the reset, over the environments: frames (the launches), stale_mean (the mean age of the frame handed out,
+        in steps), ego_lag_mean and ego_lag_max [m]: the mean and the largest distance between the ego of the true scene and
+        the ego of the frame handed out."""
+        frames = int(self.counts.sum().item())
+        s = self.sums.cpu().numpy()
+        return dict(frames=frames, stale_mean=float(s[0].sum()) / max(frames, 1),
+                    ego_lag_mean=float(s[1].sum()) / max(frames, 1), ego_lag_max=float(s[2].max(initial=0.0)))
 
 
 def _keep_bits(keep) -> int:
@@ -1874,7 +2008,9 @@ class EvalResult:
     max_abs_dev per channel, idle steps included) when the evaluation ran with one, else None; plan: the plan metrics'
     records (`PlanMetrics.records()`: dict of numpy arrays [B, Q], keys PLAN_I32 + PLAN_F64, the same slots, and `leads`) when
     the evaluation ran with plan=, else None; compensation: the totals of the delay compensator (`Compensation.totals()`:
-    scored, pos_err_mean, pos_err_max) when the evaluation ran with one, else None."""
+    scored, pos_err_mean, pos_err_max) when the evaluation ran with one, else None; latency: the totals of the latency model
+    (`Latency.totals()`: frames, stale_mean, ego_lag_mean, ego_lag_max, idle steps included) when the evaluation ran with one,
+    else None."""
     records: dict
     dt: float
     steps: int
@@ -1888,6 +2024,7 @@ class EvalResult:
     actuation: dict | None = None
     plan: dict | None = None
     compensation: dict | None = None
+    latency: dict | None = None
 
     @property
     def travel_time(self):
@@ -1917,7 +2054,9 @@ class EvalResult:
         distance between the ego and where the plan of h steps before put it, over all scored steps; 0 when there is none)
         and replan_accel_mean [m/s^2], replan_steer_mean [rad] (the mean replanning jump over all scored steps).  With a
         delay compensator also comp_pos_err_mean and comp_pos_err_max [m]: the mean and the largest distance between the ego
-        it predicted and the ego observed `steps` steps later."""
+        it predicted and the ego observed `steps` steps later.  With a latency model also sense_stale_mean (the mean age, in
+        steps, of the frame the agent's pipeline was handed) and sense_ego_lag_mean, sense_ego_lag_max [m]: how far the ego
+        had moved on from that frame."""
         out = self._base_summary()
         if self.drive is not None:
             out.update(self._drive_summary())
@@ -1937,6 +2076,9 @@ class EvalResult:
             out.update(self._plan_summary())
         if self.compensation is not None:
             out.update(comp_pos_err_mean=self.compensation["pos_err_mean"], comp_pos_err_max=self.compensation["pos_err_max"])
+        if self.latency is not None:
+            out.update(sense_stale_mean=self.latency["stale_mean"], sense_ego_lag_mean=self.latency["ego_lag_mean"],
+                       sense_ego_lag_max=self.latency["ego_lag_max"])
         return out
 
     def _plan_summary(self) -> dict:
@@ -2011,7 +2153,7 @@ def _instance(cls, given, defaults: dict, *args):
 def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = False, reset_mpc_on_done: bool = False,
                    use_graph: bool | None = None, poll_every: int = 16, seed: int = 0, on_step=None,
                    metrics: bool = False, perception=None, interaction: bool = False, trace=None,
-                   tracker=None, actuation=None, plan=None, compensation=None) -> EvalResult:
+                   tracker=None, actuation=None, plan=None, compensation=None, latency=None) -> EvalResult:
     """Run `agent` in closed loop on the B environments of `env` (a SyntheticIntersectionEnv) until each environment has
     finished `episodes_per_env` episodes; returns their records.
 
@@ -2073,6 +2215,17 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     dict also holds it as ahead.  EvalResult.compensation holds the totals.  ValueError with plan= or a trace with plan=True
     when steps > 0: the plan then starts `steps` later than the plan metrics' leads assume.  None: no launch, no buffer,
     nothing changes.
+    latency: a `Latency` for this environment's batch, a dict of its keyword arguments, or an int, its `steps`: the sensing
+    stages and the agent are handed the true scene of `steps` steps ago, `latency.apply(true observation)`, the first launch
+    of what the agent gets: after the reset (always with reset=True, like the compensator, with which it has to count the
+    episode's steps alike) and inside the step with the step's `done` (so inside the captured graph), in front of the
+    perception model and the tracker, which see the old frame from where the ego was then.  It counts as a filter: on_step's
+    dict then holds obs (the true observation), seen (what the agent gets) and stale (the age of that frame per
+    environment), and a trace may record seen=True with it alone.  EvalResult.latency holds the totals.  The accounting and
+    every metric keep reading the true scene.  compensation=True is then `Compensation.matching(actuation, latency)`, of
+    whichever of the two is present.  ValueError with plan= or a trace with plan=True when latency.steps > 0, for the
+    compensator's reason: the plan starts from another step than the plan metrics' leads assume.  None: no launch, no buffer,
+    nothing changes.
     Every episode ends by EPISODE_STEPS (200) steps, so Q * 200 steps bound the loop; RuntimeError if the episodes are not
     all recorded by then."""
     Q = int(episodes_per_env)
@@ -2109,16 +2262,26 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     # with an actuator model: what the environment is handed, and the `done` of the previous step (zero after the reset)
     applied = torch.zeros((B, 2), dtype=torch.float64, device=dev) if actuation is not None else None
     ended = torch.zeros(B, dtype=torch.uint8, device=dev) if actuation is not None else None
+    if isinstance(latency, int) and not isinstance(latency, bool):
+        latency = dict(steps=latency)
+    latency = _instance(Latency, latency, dict(R=VEHICLES_COUNT), B, dev, backend)
+    if latency is not None and (not isinstance(latency, Latency) or latency.B != B or latency.R != VEHICLES_COUNT or
+                                latency.device != dev):
+        raise ValueError(f"latency must be built for {B} environments of {VEHICLES_COUNT} rows on {dev}")
     if compensation is True:
-        if actuation is None:
-            raise ValueError("compensation=True is Compensation.matching(actuation): it needs an actuator model")
-        compensation = Compensation.matching(actuation, R=VEHICLES_COUNT)
+        if actuation is None and latency is None:
+            raise ValueError("compensation=True is Compensation.matching(actuation, latency): it needs an actuator model or "
+                             "a latency model")
+        compensation = Compensation.matching(actuation, latency, R=VEHICLES_COUNT, dt=float(env.dt))
     compensation = _instance(Compensation, compensation, dict(R=VEHICLES_COUNT, dt=float(env.dt)), B, dev, backend)
     if compensation is not None and (compensation.B != B or compensation.R != VEHICLES_COUNT or compensation.device != dev):
         raise ValueError(f"compensation must be built for {B} environments of {VEHICLES_COUNT} rows on {dev}")
     sensing = perception is not None or tracker is not None        # `obs` is something other than the true scene
-    filtered = sensing or compensation is not None                 # the agent acts on something other than the true scene
+    # the agent acts on something other than the true scene
+    filtered = sensing or compensation is not None or latency is not None
     sensed = torch.zeros_like(obs) if perception is not None and tracker is not None else None    # between the two
+    # with a latency model and a sensing stage behind it: the old true scene, between the two
+    late = torch.zeros_like(obs) if latency is not None and sensing else None
     # with a compensator: the predicted scene, what the agent acts on
     ahead = torch.zeros_like(obs) if compensation is not None else None
     acting = obs if compensation is None else ahead
@@ -2132,13 +2295,16 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
     if wants_plan and compensation is not None and compensation.steps > 0:
         raise ValueError("plan= and a trace with plan=True are not supported with a compensator of steps > 0: the plan then "
                          "starts `steps` later than the plan metrics' leads assume")
+    if wants_plan and latency is not None and latency.steps > 0:
+        raise ValueError("plan= and a trace with plan=True are not supported with a latency of steps > 0: the plan then "
+                         "starts from another step than the plan metrics' leads assume")
     trace = _instance(EpisodeTrace, trace, dict(R=VEHICLES_COUNT, env_offset=offset, seen=filtered,
                                                 **(dict(horizon=horizon) if trace_plan else {})), B, Q, dev, backend)
     if trace is not None:
         if (trace.B, trace.Q, trace.R, trace.device) != (B, Q, VEHICLES_COUNT, dev):
             raise ValueError(f"trace must be built for {B} environments, {Q} episodes each, {VEHICLES_COUNT} rows, on {dev}")
         if trace.seen and not filtered:
-            raise ValueError("trace records seen=True only with a perception model, a tracker or a compensator")
+            raise ValueError("trace records seen=True only with a perception model, a tracker, a compensator or a latency model")
         if trace.plan and trace.N != horizon:
             raise ValueError(f"trace keeps plans of horizon {trace.N}, the agent's is {horizon}")
     planm = _instance(PlanMetrics, plan, dict(N=horizon, R=VEHICLES_COUNT, dt=float(env.dt)), B, Q, dev, backend)
@@ -2169,12 +2335,18 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
             first["row_class"] = perception.row_class
         if tracker is not None:
             first["row_slot"], first["row_miss"] = tracker.row_slot, tracker.row_miss
+        if latency is not None:
+            first["stale"] = latency.stale
         on_step(first)
 
     def sense(true, reset=False, done=None):
         """`obs` <- what the agent gets of the true observation"""
+        if latency is not None:       # first: every stage behind it sees the true scene of `steps` steps ago; a scene without
+            # a step's `done` is a first scene: always a reset launch, like the compensator's, so both count the same steps
+            true = latency.apply(true, late if sensing else obs, done=done, reset=done is None)
         if not sensing:
-            obs.copy_(true)
+            if latency is None:
+                obs.copy_(true)
         elif tracker is None:
             perception.apply(true, obs, reset=reset)
         else:
@@ -2291,12 +2463,13 @@ def evaluate_agent(agent, env, episodes_per_env: int = 1, deterministic: bool = 
                       tracker=None if tracker is None else tracker.totals(),
                       actuation=None if actuation is None else actuation.totals(),
                       plan=None if planm is None else planm.records(),
-                      compensation=None if compensation is None else compensation.totals())
+                      compensation=None if compensation is None else compensation.totals(),
+                      latency=None if latency is None else latency.totals())
 
 
 def compare(agents: dict, make_env, episodes_per_env: int = 1, metrics: bool = False, perception=None,
             interaction: bool = False, trace=None, results=None, tracker=None, actuation=None, plan=None, compensation=None,
-            **kw) -> dict:
+            latency=None, **kw) -> dict:
     """Evaluate every agent on a fresh environment from make_env() (same seed: the HIP environment keys its draws by seed and
     environment id, so every agent meets the same initial episodes) -> {name: summary}; metrics=True adds the drive metrics'
     keys to every summary.  perception (a dict of `Perception`'s keyword arguments, or a Perception whose configuration is
@@ -2308,10 +2481,11 @@ def compare(agents: dict, make_env, episodes_per_env: int = 1, metrics: bool = F
     copied): every agent gets a fresh actuator model with the same seed, hence the same draws on the same steps.  plan (True, a dict of `PlanMetrics`'s keyword arguments, or a PlanMetrics whose settings are
     copied): every agent gets fresh plan metrics; an agent without a plan (PPOAgent) is evaluated without them.  compensation
     (True, a dict of `Compensation`'s keyword arguments, or a Compensation whose configuration is copied): every agent gets a
-    fresh compensator; True is the one that matches every agent's fresh actuator model.  results: a dict that receives every agent's EvalResult by name (its traces, its records)."""
-    perception, trace, tracker, actuation, plan, compensation = (
-        x.config if isinstance(x, (Perception, EpisodeTrace, Tracker, Actuation, PlanMetrics, Compensation)) else x
-        for x in (perception, trace, tracker, actuation, plan, compensation))
+    fresh compensator; True is the one that matches every agent's fresh actuator model and latency model.  latency (an int, a dict of `Latency`'s keyword
+    arguments, or a Latency whose configuration is copied): every agent gets a fresh latency model.  results: a dict that receives every agent's EvalResult by name (its traces, its records)."""
+    perception, trace, tracker, actuation, plan, compensation, latency = (
+        x.config if isinstance(x, (Perception, EpisodeTrace, Tracker, Actuation, PlanMetrics, Compensation, Latency)) else x
+        for x in (perception, trace, tracker, actuation, plan, compensation, latency))
     plan = {} if plan is True else None if plan is False else plan
     fresh = lambda settings: None if settings is None else dict(settings)
     out = {}
@@ -2323,7 +2497,8 @@ def compare(agents: dict, make_env, episodes_per_env: int = 1, metrics: bool = F
         res = evaluate_agent(agent, make_env(), episodes_per_env, metrics=metrics, perception=fresh(perception),
                              interaction=interaction, trace=settings, tracker=fresh(tracker), actuation=fresh(actuation),
                              plan=fresh(plan) if planned else None,
-                             compensation=compensation if compensation is True else fresh(compensation), **kw)
+                             compensation=compensation if compensation is True else fresh(compensation),
+                             latency=fresh(latency) if isinstance(latency, dict) else latency, **kw)
         if results is not None:
             results[name] = res
         out[name] = res.summary()

@@ -17,6 +17,9 @@ also holds the act_* shares and mean deviations.  tools/robustness_sweep.py runs
 --compensate puts the delay compensator that matches that actuator model in front of every agent (evaluate.Compensation.matching:
 the agents act on the scene predicted to the moment their command takes effect); the JSON line then also holds the
 compensator's own prediction error, comp_pos_err_mean and comp_pos_err_max [m].
+--sense-delay N hands every agent's pipeline (perception model, tracker, agent) the true scene of N policy steps ago
+(evaluate.Latency); the JSON line then also holds sense_stale_mean and sense_ego_lag_mean / sense_ego_lag_max [m].  With
+--compensate the compensator matches the actuator model and the sensing delay, whichever is given.
 
 Agents: pure MPC with the collision cost off and on, the iterative-linear (LTV) agent, and MPC-RL - an SB3 `.zip` given with
 --mpcrl, or with --fixture the v0 PPO (gSDE) policy rebuilt from tests/golden/sb3_policies.npz.  --ppo PATH adds the reference's
@@ -29,6 +32,7 @@ in the layout ActorCritic.save_sb3 writes; --ppo-random adds it with a seeded un
   python tools/compare_models.py --metrics --traffic idm --occlusion buildings --dropout 0.05 --track-coast 10
   python tools/compare_models.py --metrics --traffic idm --act-delay 2 --act-tau-steer 0.2 --act-limits env
   python tools/compare_models.py --metrics --traffic idm --act-delay 3 --act-limits env --compensate
+  python tools/compare_models.py --metrics --traffic idm --sense-delay 2 --act-delay 1 --act-limits env --compensate
   python tools/compare_models.py --metrics --traffic idm --interaction --envs 256
   python tools/compare_models.py --envs 256 --fixture --ppo baseline.zip
   python tools/compare_models.py --traffic idm --trace failed --trace-window 50 --trace-dir out
@@ -145,7 +149,10 @@ def main():
     add_actuation_flags(ap)
     ap.add_argument("--compensate", action="store_true",
                     help="delay compensation: every agent acts on the scene predicted --act-delay steps ahead through the "
-                         "nominal actuator (its lag, rate limit and limits); needs an --act-* flag")
+                         "nominal actuator (its lag, rate limit and limits), and --sense-delay steps more for the age of "
+                         "the scene; needs an --act-* flag or --sense-delay")
+    ap.add_argument("--sense-delay", type=int, metavar="N",
+                    help="sensing latency: the agent's pipeline is handed the true scene of N policy steps ago (0..7)")
     add_agent_flags(ap)
     ap.add_argument("--plan", action="store_true",
                     help="also score every MPC agent's plan against what happened (evaluate.PlanMetrics): planned clearance, "
@@ -188,8 +195,11 @@ def main():
     actuation = actuation_of(args)
     if actuation is not None:
         echo["actuation"] = {k: [finite(x) for x in v] if isinstance(v, tuple) else v for k, v in actuation.items()}
-    if args.compensate and actuation is None:
-        ap.error("--compensate matches the actuator model: give at least one --act-* flag, such as --act-delay")
+    if args.sense_delay is not None:         # no flag given: no latency stage, the launches of before
+        echo["sense_delay"] = args.sense_delay
+    if args.compensate and actuation is None and args.sense_delay is None:
+        ap.error("--compensate matches the actuator model and the sensing delay: give at least one --act-* flag, such as "
+                 "--act-delay, or --sense-delay")
     if args.compensate:
         echo["compensate"] = True
     plan = None                          # no flag given: no plan is asked for, the launches of before
@@ -206,7 +216,8 @@ def main():
         s = evaluate.compare({name: agent}, make_env, args.episodes_per_env, deterministic=args.deterministic,
                              seed=args.seed, metrics=args.metrics, perception=perception,
                              interaction=args.interaction, trace=trace, tracker=tracker, actuation=actuation,
-                             plan=plan, compensation=True if args.compensate else None, results=results)[name]
+                             plan=plan, compensation=True if args.compensate else None, latency=args.sense_delay,
+                             results=results)[name]
         s = {k: finite(v) for k, v in s.items()}
         if trace is not None:
             path = os.path.join(args.trace_dir, f"{name}.npz")
