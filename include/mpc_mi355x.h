@@ -288,6 +288,12 @@ int mpc_reserve_envs(mpc_handle *h, int32_t B);
 int mpc_get_last_inputs(mpc_handle *h, int32_t B, double *state, int32_t *ego_index, double *vref,
                         uint8_t *is_collide, double *others, int32_t *nveh);
 
+/* Diagnostics / tests: the launch order of the last ORDERED solve of B instances on this handle (a batch of more than one wave
+ * per SIMD without MPC_FLAG_THROUGHPUT) - order [B]: workgroup p solved instance order[p]; tier [B]: the tier of each
+ * instance, 0 = the seat tier, 1..4 (host arrays, either may be NULL; synchronises).  What a launch that was not ordered
+ * leaves there is unspecified. */
+int mpc_get_launch_order(mpc_handle *h, int32_t B, int32_t *order, int32_t *tier);
+
 /* Diagnostics for parity tests: with on != 0 every following mpc_predict_batch also keeps the polylines its detector
  * worked on.  mpc_get_last_paths then returns (host arrays, any may be NULL; synchronises), for environments 0..B-1 of that
  * call: ego_path [B][31][2] and ego_len [B] - what predict_ego_future_positions returns (agents/pure_mpc.py:459-527; 0

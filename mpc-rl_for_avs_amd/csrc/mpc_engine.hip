@@ -39,6 +39,7 @@
 #include "mpc_episode_stats.hpp"
 #include "mpc_episode_trace.hpp"
 #include "mpc_plan.hpp"
+#include "mpc_order.hpp"
 
 namespace {
 
@@ -227,76 +228,89 @@ __global__ __launch_bounds__(64) void mpc_timer_kernel(long long ticks) {
 // 45 - 50 without; of the instances with >= 50 iterations 90 - 100 % have is_collide = 0) unless the ego stands still (speed on
 // its bound 0: every exception found); and with the collision cost on, an instance without a vehicle within 15 m of the ego is
 // the easy live objective in all but name (no instance with >= 70 iterations had its nearest vehicle farther away, unless it
-// stood still).  Tiers, each in its original order (a stable partition): 0 = standing ego, or no predicted collision
-// and (collision cost off or a vehicle within kNear); 1 = the other instances without a predicted collision; 2 = a predicted
-// collision while the route turns; 3 = the rest.  (Tier 3, round 6: with a predicted collision the instances that still need
+// stood still).  Tiers, each in its original order (a stable partition): 1 = standing ego, or no predicted collision
+// and (collision cost off or a vehicle within kNear); 2 = the other instances without a predicted collision; 3 = a predicted
+// collision while the route turns; 4 = the rest; tier 0 is the seat tier below.  (Tier 4, round 6: with a predicted collision the instances that still need
 // >= 60 iterations - 3 to 6 of 65 536, one or two of them at the cap - sit where the reference heading changes between five rows
 // behind the ego and the end of the look-ahead, 15 of 16 over four draws; started last, one of them alone is 13 % of a bulk
-// launch.  The straight-route half of tier 2, 28 % of a batch with a maximum of 41 - 58 iterations, now ends the launch:
+// launch.  The straight-route half of what was one tier, 28 % of a batch with a maximum of 41 - 58 iterations, now ends the launch:
 // 65 536 instances 21.2 -> 19.6 ms in the occupancy model that reproduced the three-tier measurements to 0.2 ms.)
 // (Round 5 also built "what the same environment needed one step ago" as the first key for the closed loop; measured neutral to
 // negative - profiles/r05_launch_order_prev.txt, docs/NOT_ADOPTED.md - and removed in round 6 together with its per-environment
 // record and the environment variable that switched it on.)
-constexpr double kOrderStanding = 0.1, kOrderNear = 15.0, kOrderTurn = 0.05;
-constexpr int kOrderBehind = 5;
-__device__ __forceinline__ int order_tier(const uint8_t *is_collide, const double *state, const double *others, int V,
-                                          const int32_t *nveh, const int32_t *ego, const double *ref5, int M, int N, int i) {
-    const double *x = state + (size_t)i * 4;
-    if (x[3] < kOrderStanding) return 0;
-    if (is_collide[i] != 0) {
-        const int e0 = mpc::ego_row0(ego[i], M);
-        const int a = min(M - 1, max(0, e0 - kOrderBehind)), b = min(M - 1, max(0, e0 + N));
-        const double d = ref5[(size_t)b * mpc::REF_COLS + mpc::R_H] - ref5[(size_t)a * mpc::REF_COLS + mpc::R_H];
-        return fabs(remainder(d, 6.283185307179586)) > kOrderTurn ? 2 : 3;      // (NaN compares false: tier 3)
-    }
-    if (!others || V <= 0) return 0;
-    const int nv = nveh ? min(V, max(0, nveh[i])) : V;
-    bool near = false;
-    for (int j = 0; j < nv; ++j) {
-        const double *o = others + ((size_t)i * V + j) * 4;
-        const double dx = o[0] - x[0], dy = o[1] - x[1];
-        near = near || dx * dx + dy * dy < kOrderNear * kOrderNear;
-    }
-    return near ? 0 : 1;
+// (The tier functions live in mpc_order.hpp, host and device: tests/test_order_tiers_cpu.py calls them on the CPU.)
+//
+// The seat tier (tier 0, `seats`): the latency build holds two waves per SIMD, and workgroups p and p + 1024 share one
+// (tools/ubench/seat_probe.hip, profiles/seat_probe.txt: on 930 - 1024 of the 1024 SIMDs, the rest at a distance of 768;
+// the lower index is the one that runs near the lone rate, x 1.06 - 1.08 against x 1.29 - 1.31 for its mate on an FP64 chain).
+// The first of the tiers above holds 1550 - 1700 of 4096, so a third of it sits in the younger seats, where a cap-runner
+// runs beside a mate of its own tier at the leftover rate.  Where ONE batch of the latency build is solved with the collision
+// cost on, a narrower tier goes in front (mpc::order::first_seat: standing ego, or no predicted collision, a moving ego and a
+// vehicle whose closest approach within the horizon is below 5 m): 950 - 1074 of 4096 (seeds 0 - 23) with the recall of the wider tier on
+// the instances with >= 60 iterations (tools/seat_model.py, profiles/seat_tier_model.txt).  Bulk launches, launches without
+// vehicles and the live objective keep the four tiers: with tier 0 empty the order is the one they always had.
+// Measured against the four tiers alone (profiles/seat_tier.txt, builds alternating, five fresh processes each): the headline batch
+// 3.731 - 3.739 -> 3.556 - 3.572 ms (-4.5 %), results equal array for array; seeds 0 - 7 mean -2.9 %, seed 6 +1.8 %; caps 40 / 60
+// not slower / -7 %.
+// The seat tier's closest approach costs two FP64 sin / cos and a reciprocal per vehicle: computed inside the one workgroup of
+// mpc_order_kernel it made that kernel 61 us on the headline batch (one CU, issue-bound; the parent's took 19), so where the seat
+// tier applies the tiers are written by this kernel first, one wave per 64 instances over as many CUs: 8.7 us, and the order
+// kernel behind it 7.7 us (rocprofv3 kernel trace, profiles/seat_tier.txt).
+__global__ __launch_bounds__(64) void mpc_tier_kernel(int B, const uint8_t *__restrict__ is_collide,
+                                                      const double *__restrict__ state, const double *__restrict__ others, int V,
+                                                      const int32_t *__restrict__ nveh, const int32_t *__restrict__ ego,
+                                                      const double *__restrict__ ref5, int M, int N, double T,
+                                                      int32_t *__restrict__ tier) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i < B) tier[i] = mpc::order::tier_of(is_collide, state, others, V, nveh, ego, ref5, M, N, i, true, T);
 }
+// `tiers_given`: mpc_tier_kernel has filled `tier` (the seat tier applies); otherwise the four tiers are computed here, as ever.
 __global__ __launch_bounds__(1024) void mpc_order_kernel(int B, const uint8_t *__restrict__ is_collide,
                                                          const double *__restrict__ state, const double *__restrict__ others,
                                                          int V, const int32_t *__restrict__ nveh, const int32_t *__restrict__ ego,
-                                                         const double *__restrict__ ref5, int M, int N,
-                                                         int32_t *__restrict__ order, int32_t *__restrict__ tier) {
-    __shared__ int s_c0[1024], s_c1[1024], s_c2[1024];
+                                                         const double *__restrict__ ref5, int M, int N, int tiers_given,
+                                                         int32_t *__restrict__ order, int32_t *tier) {
+    __shared__ int s_c0[1024], s_c1[1024], s_c2[1024], s_c3[1024];
     const int t = threadIdx.x, chunk = (B + 1023) / 1024, lo = min(B, t * chunk), hi = min(B, lo + chunk);
     // tiers first, every thread an interleaved share (neighbouring threads read neighbouring instances), kept in scratch
-    for (int i = t; i < B; i += 1024) tier[i] = order_tier(is_collide, state, others, V, nveh, ego, ref5, M, N, i);
+    if (!tiers_given)
+        for (int i = t; i < B; i += 1024)
+            tier[i] = mpc::order::tier_of(is_collide, state, others, V, nveh, ego, ref5, M, N, i, false, 0.0);
     __syncthreads();
-    int n0 = 0, n1 = 0, n2 = 0;
+    int n0 = 0, n1 = 0, n2 = 0, n3 = 0;
     for (int i = lo; i < hi; ++i) {
         const int k = tier[i];
         n0 += k == 0;
         n1 += k == 1;
         n2 += k == 2;
+        n3 += k == 3;
     }
     s_c0[t] = n0;
     s_c1[t] = n1;
     s_c2[t] = n2;
+    s_c3[t] = n3;
     __syncthreads();
     for (int d = 1; d < 1024; d <<= 1) {          // inclusive scans of the tier counts
-        const int v0 = t >= d ? s_c0[t - d] : 0, v1 = t >= d ? s_c1[t - d] : 0, v2 = t >= d ? s_c2[t - d] : 0;
+        const int v0 = t >= d ? s_c0[t - d] : 0, v1 = t >= d ? s_c1[t - d] : 0, v2 = t >= d ? s_c2[t - d] : 0,
+                  v3 = t >= d ? s_c3[t - d] : 0;
         __syncthreads();
         s_c0[t] += v0;
         s_c1[t] += v1;
         s_c2[t] += v2;
+        s_c3[t] += v3;
         __syncthreads();
     }
-    const int tot0 = s_c0[1023], tot1 = s_c1[1023], tot2 = s_c2[1023];
-    const int b0 = s_c0[t] - n0, b1 = s_c1[t] - n1, b2 = s_c2[t] - n2;     // members of tier 0 / 1 / 2 before this chunk
-    int p0 = b0, p1 = tot0 + b1, p2 = tot0 + tot1 + b2, p3 = tot0 + tot1 + tot2 + (lo - b0 - b1 - b2);
+    const int tot0 = s_c0[1023], tot1 = s_c1[1023], tot2 = s_c2[1023], tot3 = s_c3[1023];
+    const int b0 = s_c0[t] - n0, b1 = s_c1[t] - n1, b2 = s_c2[t] - n2, b3 = s_c3[t] - n3;   // members of tiers 0..3 before this chunk
+    int p0 = b0, p1 = tot0 + b1, p2 = tot0 + tot1 + b2, p3 = tot0 + tot1 + tot2 + b3,
+        p4 = tot0 + tot1 + tot2 + tot3 + (lo - b0 - b1 - b2 - b3);
     for (int i = lo; i < hi; ++i) {
         const int k = tier[i];
         if (k == 0) order[p0++] = i;
         else if (k == 1) order[p1++] = i;
         else if (k == 2) order[p2++] = i;
-        else order[p3++] = i;
+        else if (k == 3) order[p3++] = i;
+        else order[p4++] = i;
     }
 }
 
@@ -1672,8 +1686,17 @@ int dispatch_solve(const mpc_handle *h, int B, bool cc, int V, uint32_t flags, h
     // on four draws (profiles/r06_bulk_order.txt; tools/sim_schedule.py's occupancy model predicts each to 0.2 ms)
     const int32_t *d_order = nullptr;
     if (!throughput && B > simds && h->d_order && h->order_cap >= B) {
+        // the seat tier in front (see mpc_order_kernel): only where the latency build (a compiled horizon, `spare`) solves this
+        // one batch two waves per SIMD, with vehicles and the collision cost
+        const int seats = spare && cc && d_others && Vuse > 0 ? 1 : 0;
+        int32_t *d_tier = h->d_order + h->order_cap;
+        if (seats) {
+            hipLaunchKernelGGL(mpc_tier_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, stream, (int)B, d_coll, d_state,
+                               d_others, (int)Vuse, d_nveh, d_ego, h->d_ref, h->M, N, N * h->cfg.dt, d_tier);
+            HIP_TRY(hipGetLastError());
+        }
         hipLaunchKernelGGL(mpc_order_kernel, dim3(1), dim3(1024), 0, stream, (int)B, d_coll, d_state, cc ? d_others : nullptr,
-                           (int)Vuse, d_nveh, d_ego, h->d_ref, h->M, N, h->d_order, h->d_order + h->order_cap);
+                           (int)Vuse, d_nveh, d_ego, h->d_ref, h->M, N, seats, h->d_order, d_tier);
         HIP_TRY(hipGetLastError());
         d_order = h->d_order;
     }
@@ -2784,6 +2807,17 @@ int mpc_get_last_inputs(mpc_handle *h, int32_t B, double *state, int32_t *ego_in
     if (is_collide) HIP_TRY(hipMemcpy(is_collide, h->p_coll, (size_t)B, hipMemcpyDeviceToHost));
     if (others) HIP_TRY(hipMemcpy(others, h->p_others, (size_t)B * V * 4 * 8, hipMemcpyDeviceToHost));
     if (nveh) HIP_TRY(hipMemcpy(nveh, h->p_nveh, (size_t)B * 4, hipMemcpyDeviceToHost));
+    return MPC_OK;
+}
+
+int mpc_get_launch_order(mpc_handle *h, int32_t B, int32_t *order, int32_t *tier) {
+    if (!h || B < 0) return fail(MPC_ERR_INVALID_ARG, "mpc_get_launch_order: bad argument");
+    if (B == 0) return MPC_OK;
+    if (!h->d_order || B > h->order_cap) return fail(MPC_ERR_INVALID_ARG, "mpc_get_launch_order: no launch order of that size");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());
+    if (order) HIP_TRY(hipMemcpy(order, h->d_order, (size_t)B * 4, hipMemcpyDeviceToHost));
+    if (tier) HIP_TRY(hipMemcpy(tier, h->d_order + h->order_cap, (size_t)B * 4, hipMemcpyDeviceToHost));
     return MPC_OK;
 }
 

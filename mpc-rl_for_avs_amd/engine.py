@@ -160,7 +160,7 @@ _ALL_TABLES = _TABLES + (COMPENSATION_SIGNATURES, LATENCY_SIGNATURES)
 
 _EXPORTS = ["mpc_version", "mpc_last_error", "mpc_default_config", "mpc_default_config_sized", "mpc_create", "mpc_destroy",
             "mpc_set_reference", "mpc_solve_batch", "mpc_workspace_bytes", "mpc_predict_batch", "mpc_predict_batch_plan",
-            "mpc_reset_env_state", "mpc_reset_env_mask", "mpc_get_env_state", "mpc_get_last_inputs",
+            "mpc_reset_env_state", "mpc_reset_env_mask", "mpc_get_env_state", "mpc_get_last_inputs", "mpc_get_launch_order",
             "mpc_ltv_solve_batch", "mpc_ltv_predict_batch", "mpc_ltv_predict_batch_plan", "mpc_env_state_bytes", "mpc_save_env_state",
             "mpc_set_env_state", "mpc_reserve_envs", "mpc_synth_env_step", "mpc_synth_env_step_idm", "mpc_set_diagnostics", "mpc_get_last_paths", "mpc_policy_act", "mpc_policy_act_sde", "mpc_policy_control", "mpc_policy_control_tile", "mpc_rollout_record", "mpc_rollout_finish", "mpc_episode_stats", "mpc_drive_metrics", "mpc_interaction_metrics", "mpc_episode_trace", "mpc_plan_metrics", "mpc_plan_trace", "mpc_perceive", "mpc_track_rows", "mpc_actuate", "mpc_compensate", "mpc_compensate_stale", "mpc_delay_scene", "mpc_eval_nlp", "mpc_streams_overlap"]
 ABI_VERSION = 8          # MPC_ABI_VERSION of include/mpc_mi355x.h this binding is written for
@@ -241,6 +241,8 @@ def load_library(path: str | None = None):
     lib.mpc_reserve_envs.restype = ctypes.c_int
     lib.mpc_get_last_inputs.argtypes = [vp, ctypes.c_int32, dp, ip, dp, vp, dp, ip]
     lib.mpc_get_last_inputs.restype = ctypes.c_int
+    lib.mpc_get_launch_order.argtypes = [vp, ctypes.c_int32, ip, ip]
+    lib.mpc_get_launch_order.restype = ctypes.c_int
     lib.mpc_set_diagnostics.argtypes = [vp, ctypes.c_int32]
     lib.mpc_set_diagnostics.restype = ctypes.c_int
     lib.mpc_get_last_paths.argtypes = [vp, ctypes.c_int32, dp, ip, vp]
@@ -723,6 +725,13 @@ class MPCEngine:
         rc = self._lib.mpc_get_last_inputs(self._h, B, _ptr(o["state"]), _ptr(o["ego_index"]), _ptr(o["vref"]),
                                            _ptr(o["is_collide"]), _ptr(o["others"]), _ptr(o["nveh"]))
         self._check(rc, "mpc_get_last_inputs")
+        return o
+
+    def launch_order(self, B):
+        """Launch order of the last ordered solve of B instances (host copies): order [B] (workgroup p solved instance
+        order[p]) and tier [B] (0 = the seat tier, 1..4)."""
+        o = dict(order=np.empty(B, np.int32), tier=np.empty(B, np.int32))
+        self._check(self._lib.mpc_get_launch_order(self._h, B, _ptr(o["order"]), _ptr(o["tier"])), "mpc_get_launch_order")
         return o
 
     def set_diagnostics(self, on=True):

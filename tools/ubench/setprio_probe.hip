@@ -9,7 +9,9 @@
 #include <vector>
 
 __global__ __launch_bounds__(512) void probe(long long *ticks, int *simd, double *sink, int iters, int prio_mode, int active_waves) {
-    const int wave = threadIdx.x >> 6;
+    // the wave index as a scalar: s_setprio ignores EXEC, so under a per-lane condition (threadIdx.x >> 6 < 4) EVERY wave that
+    // reaches the branch executes it and both modes raise all eight waves (profiles/r02_setprio.txt was recorded that way)
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (wave >= active_waves) return;
     if (prio_mode == 1 && wave < 4) __builtin_amdgcn_s_setprio(3);
     if (prio_mode == 2 && wave >= 4) __builtin_amdgcn_s_setprio(3);
